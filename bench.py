@@ -3,7 +3,15 @@
 synthetic graph (BASELINE.json metric; configs[2] at N=1, configs[3] at N>1).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfgL|...] [--scaling strong|weak]
-                  [--rotate K]
+                  [--rotate K] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, checks the warm-up's results against the oracle, times K steps, checks
+what they wrote, and prints the line (`value`, `ms_per_step`).  Everything else -- the one-call-at-a-time
+loop (`one_call_ms`), the per-kernel samples and `roofline`, the cold plan and region, the all-reduce
+alone, `extras` and `cpu_baseline` -- runs only with --full (the --no-* options below apply there).
+--dump-outputs DIR writes what the last timed step computed, [depth | uniq] as the caller receives it,
+to DIR/depth.npy and DIR/uniq.npy (float64; above 64 MB in all a fixed sample of segments, seed 0, with
+their indices in DIR/index.npy).  Inputs are seeded: the same arguments give the same graph.
 
 One "step" = one pass of the hot path (seg_depth_with_uniq, ops/depth.rs:15-39) over the rank's
 resident graph image: run the HIP kernels, and -- for N > 1 -- one RCCL sum all-reduce of the
@@ -115,6 +123,24 @@ def git_head():
         return None
 
 
+DUMP_LIMIT_BYTES = 64_000_000  # all files of a dump together, headers included
+NPY_HEADER_BYTES = 4096        # at most, per file (a 1-D float64 array's is 128)
+
+
+def dump_outputs(out_dir, depth, uniq):
+    """--dump-outputs: the last timed step's depth and uniq vectors (u32) as float64 .npy files, exact for every u32.
+    Where both together would pass DUMP_LIMIT_BYTES, a fixed sample of segments (seed 0), with its indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    depth, uniq = np.asarray(depth), np.asarray(uniq)
+    arrays = {"depth": depth, "uniq": uniq}
+    if 2 * (8 * len(depth) + NPY_HEADER_BYTES) > DUMP_LIMIT_BYTES:
+        draws = (DUMP_LIMIT_BYTES - 3 * NPY_HEADER_BYTES) // (3 * 8)
+        idx = np.unique(np.random.default_rng(0).integers(0, len(depth), size=draws))
+        arrays = {"index": idx, "depth": depth[idx], "uniq": uniq[idx]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+
+
 T_PROCESS0 = time.perf_counter()
 
 
@@ -144,7 +170,14 @@ def main():
                          "the warm plan's launches alone (tools/profile_round.sh)")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the secondary measurements (depth-only, path depth, rotation, end-to-end, copy bandwidth)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the one-call-at-a-time loop, per-kernel samples and roofline, the cold plan and "
+                         "region, the all-reduce alone, the secondary measurements and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's depth and uniq vectors to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -351,30 +384,36 @@ def main():
     elapsed, kernels_region = timed_loop(lambda i: op.run(), args.steps, in_flight == 1)
     status_all()
     check_bufs(op.bufs, f"behind the timed region ({args.steps} steps, {in_flight} in flight)")  # (what the region's calls wrote, not the warm-up's)
+    if args.dump_outputs and rank == 0:  # (every rank holds the same reduced vector)
+        torch.cuda.synchronize(device)
+        last = op.buf.cpu().numpy().view(np.uint32)
+        dump_outputs(args.dump_outputs, last[:S], last[S:])
     n_region_samples = len([i for i in range(args.steps) if i % EVENT_EVERY == EVENT_AT]) if in_flight == 1 else 0
     if in_flight > 1:
         SAMPLE_STEPS = 18
     serial_elapsed = None
-    if in_flight > 1:  # the same loop with one call in flight (no event records either)
+    if in_flight > 1 and args.full:  # the same loop with one call in flight (no event records either)
         for _ in range(2):
             op1.run()
         serial_elapsed, _ = timed_loop(lambda i: op1.run(), args.steps, False)
         plan.status()
         check_bufs(op1.bufs, "behind the one-call-at-a-time loop")
     # the sampled pass behind the region
-    for _ in range(2):
-        op1.run()
-    dev.profile_enable(True)
-    for _ in range(SAMPLE_STEPS):
-        op1.run()
-    sync_all()
-    dev.profile_enable(False)
-    kernels_post = dev.profile_read()
+    kernels_post = []
+    if args.full:
+        for _ in range(2):
+            op1.run()
+        dev.profile_enable(True)
+        for _ in range(SAMPLE_STEPS):
+            op1.run()
+        sync_all()
+        dev.profile_enable(False)
+        kernels_post = dev.profile_read()
+        status_all()
+        plan.status()
+        check_bufs(op1.bufs, "behind the sampled pass (the calls whose kernels `roofline` prices)")
     kernels = kernels_region + kernels_post
     n_timed_steps = n_region_samples + SAMPLE_STEPS
-    status_all()
-    plan.status()
-    check_bufs(op1.bufs, "behind the sampled pass (the calls whose kernels `roofline` prices)")
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -382,7 +421,7 @@ def main():
 
     # N > 1: the all-reduce alone (8 MB, latency-bound), for reading the scaling numbers
     allreduce_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         sync_all()
         c0 = time.perf_counter()
         for _ in range(10):
@@ -402,7 +441,7 @@ def main():
     B_call = algorithmic_bytes(N_local, P_local, S, 2)
     device_ms_per_step = sum(kern_avg_ms[k] * len(per[k]) for k in per) / max(n_timed_steps, 1)
     roofline = None
-    if dom:
+    if dom and args.full:
         B_dom = kernel_bytes(dom, N_local, P_local, S, 2)
         # A kernel that is launched several times per call on different paths (k_scan_short: once for the paths read
         # forwards, once for the reversed copies) reads its share of the steps per launch; a plan with segment ranges
@@ -541,7 +580,7 @@ def main():
 
     # ---- secondary measurements, rank 0 at N=1 only, outside the timed region ----
     extras = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and not args.no_extras and args.full:
         extras = {}
 
         def timed(fn, reps=5):
@@ -930,7 +969,7 @@ def main():
 
     # ---- CPU baseline: the oracle, one core, same arrays (rank 0, N=1 only) ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.full:
         from oracle import flatgfa_oracle as fo
         pools = fo.Pools(**{n: g.pool(n) for n in fo.POOL_ORDER})
         fo.seg_depth_with_uniq(pools)  # warm-up: page in, build the .so
@@ -999,8 +1038,9 @@ def main():
                        "ranks_seen": ranks_seen, "uses_rccl": bool(world > 1 and backend == "nccl")},
             "bit_exact_vs_oracle": verified,
             # one whole query with nothing else in flight (the loop of the same process that runs one call after the other);
-            # `ms_per_step` is the throughput of `calls_in_flight` overlapped queries
-            "one_call_ms": round(serial_elapsed / args.steps * 1e3, 5) if serial_elapsed else round(elapsed / args.steps * 1e3, 5),
+            # `ms_per_step` is the throughput of `calls_in_flight` overlapped queries (null: calls in flight and no --full)
+            "one_call_ms": (round(serial_elapsed / args.steps * 1e3, 5) if serial_elapsed else
+                            round(elapsed / args.steps * 1e3, 5) if in_flight == 1 else None),
             "verified_after": checked if verified else None,
             "roofline": roofline, "cpu_baseline": cpu, "commit": git_head(),
         }
@@ -1064,15 +1104,18 @@ def main_host_c(args, torch, dist, pa, dev):
             sh.enqueue(True)
         sh.sync()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *sh.fetch(0))  # (every shard holds the reduced vectors)
         # kernel durations of a few more steps, outside the timed region (the event records are process-wide)
-        dev.profile_enable(True)
-        for _ in range(3):
-            sh.enqueue(True)
-        sh.sync()
-        dev.profile_enable(False)
         per = {}
-        for name, ms in dev.profile_read():
-            per.setdefault(name, []).append(ms)
+        if args.full:
+            dev.profile_enable(True)
+            for _ in range(3):
+                sh.enqueue(True)
+            sh.sync()
+            dev.profile_enable(False)
+            for name, ms in dev.profile_read():
+                per.setdefault(name, []).append(ms)
         kern = {k: round(float(np.mean(v)), 5) for k, v in per.items()}
         dom = max(kern, key=lambda k: kern[k]) if kern else None
         N_local = max(x["step_end"] - x["step_begin"] for x in lay)

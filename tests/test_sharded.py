@@ -163,7 +163,7 @@ def test_bench_multirank_control_flow_on_one_gpu(scaling):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
                         os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--workload", "cfgS", "--scaling", scaling],
+                        "--workload", "cfgS", "--scaling", scaling, "--full"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -175,20 +175,21 @@ def test_bench_multirank_control_flow_on_one_gpu(scaling):
 
 
 @pytest.mark.gpu
-def test_bench_host_c_two_shards_on_one_gpu():
+def test_bench_host_c_two_shards_on_one_gpu(tmp_path):
     """bench.py --host c under the launcher: rank 0 alone drives both shards through
     flatgfa_sharded_* (here on one device, so the exchange is the device-side add; on a node it is
     RCCL inside the library), rank 1 only keeps the barriers.  bench.py checks every shard's
-    reduced vectors against the oracle before it prints a line."""
+    reduced vectors against the oracle before it prints a line, and --dump-outputs writes the last timed step's."""
     import json
     import subprocess
     import sys
+    import pollen_amd as pa
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, FLATGFA_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
                         os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--workload", "cfgS", "--host", "c"],
+                        "--workload", "cfgS", "--host", "c", "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -200,6 +201,11 @@ def test_bench_host_c_two_shards_on_one_gpu():
     # the same cut as the torch route's (shard_paths): both put the even cut at a path boundary here
     assert line["config"]["steps_per_gpu_all_ranks"] == [500_000, 500_000]
     assert line["config"]["collective_bytes"] == 8 * 10_000  # (no path cut: [depth | uniq] alone)
+    g = pa.synth(1, 10_000, 100, 10_000, "pangenome", False)
+    want_d, want_u = fo.seg_depth_with_uniq(fo.Pools(**{n: g.pool(n) for n in fo.POOL_ORDER}))
+    assert sorted(os.listdir(tmp_path)) == ["depth.npy", "uniq.npy"]
+    d, u = np.load(tmp_path / "depth.npy"), np.load(tmp_path / "uniq.npy")
+    assert d.dtype == np.float64 and (d == want_d).all() and (u == want_u).all()
 
 
 @pytest.mark.gpu
@@ -219,6 +225,60 @@ def test_bench_one_rank_under_the_launcher_is_the_plain_run():
     la, lb = (json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]) for r in (a, b))
     for k in ("metric", "unit", "n_gpus", "steps", "warmup", "scaling", "dtype", "config", "bit_exact_vs_oracle"):
         assert la[k] == lb[k], k
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_last_step_and_full_adds_the_rest(tmp_path):
+    """A plain run's line holds the headline alone, and --dump-outputs writes what its last timed step computed:
+    depth and uniq, equal to the oracle's.  --full brings back the one-call loop and the per-kernel roofline."""
+    import json
+    import subprocess
+    import sys
+    import pollen_amd as pa
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--workload", "cfgS"]
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    r = subprocess.run(base + ["--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 5 and line["ms_per_step"] > 0 and line["bit_exact_vs_oracle"] is True
+    assert line["metric"].endswith("; bit-exact vs flatgfa CPU") and line["unit"] == "path-steps/s" and line["dtype"] == "u32"
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "extras" not in line
+    g = pa.synth(1, 10_000, 100, 10_000, "pangenome", False)
+    want_d, want_u = fo.seg_depth_with_uniq(fo.Pools(**{n: g.pool(n) for n in fo.POOL_ORDER}))
+    assert sorted(os.listdir(tmp_path)) == ["depth.npy", "uniq.npy"]
+    d, u = np.load(tmp_path / "depth.npy"), np.load(tmp_path / "uniq.npy")
+    assert d.dtype == np.float64 and (d == want_d).all() and (u == want_u).all()
+    r = subprocess.run(base + ["--full", "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    full = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert full["roofline"]["kernel"] and full["one_call_ms"] > 0 and full["metric"] == line["metric"]
+
+
+def test_bench_dump_of_a_large_output_is_a_fixed_sample(tmp_path):
+    """Where depth and uniq would pass 64 MB (64,000,000 bytes, headers included), --dump-outputs writes a sample of
+    segments that is the same from run to run, with its indices; just below that it writes them whole."""
+    import bench
+
+    def size(d):
+        return sum(os.path.getsize(d / f) for f in os.listdir(d))
+    S = 3_999_000
+    bench.dump_outputs(str(tmp_path / "whole"), np.arange(S, dtype=np.uint32), np.zeros(S, dtype=np.uint32))
+    assert sorted(os.listdir(tmp_path / "whole")) == ["depth.npy", "uniq.npy"] and size(tmp_path / "whole") <= 64_000_000
+    assert (np.load(tmp_path / "whole" / "depth.npy") == np.arange(S)).all()
+    S = 4_000_000  # (cfgL-4Mseg, hap-chr20: whole, 64,000,256 bytes)
+    depth = np.arange(S, dtype=np.uint32) * np.uint32(7)
+    uniq = np.arange(S, dtype=np.uint32) + np.uint32(4_000_000_000)
+    for out in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(out), depth, uniq)
+    assert sorted(os.listdir(tmp_path / "a")) == ["depth.npy", "index.npy", "uniq.npy"]
+    assert size(tmp_path / "a") <= 64_000_000
+    idx = np.load(tmp_path / "a" / "index.npy")
+    for name in ("depth", "uniq", "index"):
+        assert np.load(tmp_path / "a" / f"{name}.npy").tobytes() == np.load(tmp_path / "b" / f"{name}.npy").tobytes()
+    i = idx.astype(np.int64)
+    assert (np.diff(i) > 0).all() and len(i) > 1_000_000
+    assert (np.load(tmp_path / "a" / "depth.npy") == depth[i]).all() and (np.load(tmp_path / "a" / "uniq.npy") == uniq[i]).all()
 
 
 @pytest.mark.gpu

@@ -7,7 +7,7 @@ for rep in $(seq ${REPS:-2}); do
   for flags in "$@"; do
     touch pollen_amd/csrc/depth_fast_kernels.hpp
     make -C pollen_amd/csrc CXXFLAGS="$BASE $flags" > /tmp/build.log 2>&1 || { echo "[$flags]: build failed"; tail -3 /tmp/build.log; continue; }
-    for wl in ${WLS:-cfgL}; do timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --workload $wl 2>/dev/null | tail -1 | python -c "
+    for wl in ${WLS:-cfgL}; do timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras --workload $wl 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('[$flags] $wl', d['ms_per_step'], d['bit_exact_vs_oracle'], d['roofline']['kernels_avg_ms'])"; done
   done

@@ -3,7 +3,7 @@
 WLS=$1; shift
 O=gpurun_out/ab; mkdir -p $O
 for r in 1 2; do for w in $WLS; do i=0; for e in "$@"; do i=$((i+1))
-  env $e python3 bench.py --steps 40 --warmup 3 --workload $w --no-cpu-baseline --no-extras 2>$O/err_$i.txt | tail -1 | python3 -c "
+  env $e python3 bench.py --full --steps 40 --warmup 3 --workload $w --no-cpu-baseline --no-extras 2>$O/err_$i.txt | tail -1 | python3 -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read()); r=d['roofline']

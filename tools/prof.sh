@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof
 mkdir -p $OUT
 cd $R
-ARGS="bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-verify --workload ${1:-cfgL}"
+ARGS="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-verify --workload ${1:-cfgL}"
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- python3 $ARGS > $OUT/trace.log 2>&1
 rocprofv3 -L > $OUT/counters.txt 2>&1
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA" \

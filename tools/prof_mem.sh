@@ -2,7 +2,7 @@
 # HBM traffic counters for the depth kernels (run via gpurun):  tools/prof_mem.sh [workload] [steps]
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/prof_mem; rm -rf $OUT; mkdir -p $OUT; cd $R
-ARGS="bench.py --steps ${2:-5} --warmup 2 --in-flight 1 --no-cpu-baseline --no-verify --no-extras --workload ${1:-cfgL}"
+ARGS="bench.py --full --steps ${2:-5} --warmup 2 --in-flight 1 --no-cpu-baseline --no-verify --no-extras --workload ${1:-cfgL}"
 for set in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $set -d $OUT/$set -o pmc -- python3 $ARGS > $OUT/$set.log 2>&1
 done

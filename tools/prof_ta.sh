@@ -4,7 +4,7 @@
 # hangs after "Request exceeds the capabilities of the hardware".
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/prof_ta; rm -rf $OUT; mkdir -p $OUT; cd $R
-ARGS="bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-verify --no-extras --workload ${1:-cfgL}"
+ARGS="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-verify --no-extras --workload ${1:-cfgL}"
 i=0
 for set in "TA_TA_BUSY_sum TA_BUSY_avr" "TA_FLAT_READ_WAVEFRONTS_sum TA_FLAT_WRITE_WAVEFRONTS_sum" "TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum" "TCP_PENDING_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum" "TCP_TOTAL_ACCESSES_sum TCP_TCC_READ_REQ_sum" "TCP_TCC_WRITE_REQ_sum TCP_GATE_EN1_sum"; do
   i=$((i+1))

@@ -4,8 +4,8 @@
 TAG=${1:-r04}
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/profiles; mkdir -p $OUT; cd $R
-timeout 900 python3 bench.py --steps 20 --warmup 5 2>$OUT/_bench_cfgL.err | tail -1 > $OUT/${TAG}_bench_cfgL.json
-rm -rf $OUT/_trace; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/_trace -o t -- python3 bench.py --steps 40 --warmup 3 --no-cpu-baseline --no-extras > $OUT/_trace.log 2>&1
+timeout 900 python3 bench.py --full --steps 20 --warmup 5 2>$OUT/_bench_cfgL.err | tail -1 > $OUT/${TAG}_bench_cfgL.json
+rm -rf $OUT/_trace; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/_trace -o t -- python3 bench.py --full --steps 40 --warmup 3 --no-cpu-baseline --no-extras > $OUT/_trace.log 2>&1
 f=$(find $OUT/_trace -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/${TAG}_rocprofv3_kernel_stats.csv
 rm -rf $OUT/_trace
 python3 -c "

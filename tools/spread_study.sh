@@ -4,7 +4,7 @@
 # per-workgroup timeline (FLATGFA_SCAN_TIME=<file>: XCC, items taken, start/end).  Output: gpurun_out/spread/.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/spread; mkdir -p $OUT; cd $R
-CMD="bench.py --steps 60 --warmup 3 --no-cpu-baseline --no-extras --no-verify"
+CMD="bench.py --full --steps 60 --warmup 3 --no-cpu-baseline --no-extras --no-verify"
 rm -rf $OUT/_trace; rocprofv3 --kernel-trace --output-format csv -d $OUT/_trace -o t -- python3 $CMD > $OUT/trace.log 2>&1
 f=$(find $OUT/_trace -name "*kernel_trace.csv" | head -1); [ -n "$f" ] && cp $f $OUT/kernel_trace.csv
 rm -rf $OUT/_pmc; rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE -d $OUT/_pmc -o p -- python3 $CMD > $OUT/pmc.log 2>&1
@@ -23,6 +23,6 @@ for d in sorted(glob.glob("$OUT/_pmc/**/*.db", recursive=True)):
             print(",".join(str(x) for x in r))
 PY
 rm -f $OUT/wg_timeline.csv
-FLATGFA_SCAN_TIME=$OUT/wg_timeline.csv python3 bench.py --steps 12 --warmup 2 --no-cpu-baseline --no-extras --no-verify > $OUT/timeline_bench.json 2> $OUT/timeline.log
+FLATGFA_SCAN_TIME=$OUT/wg_timeline.csv python3 bench.py --full --steps 12 --warmup 2 --no-cpu-baseline --no-extras --no-verify > $OUT/timeline_bench.json 2> $OUT/timeline.log
 rm -rf $OUT/_trace $OUT/_pmc
 ls -la $OUT; head -3 $OUT/kernel_trace.csv; head -5 $OUT/pmc_per_dispatch.csv; tail -2 $OUT/timeline.log
