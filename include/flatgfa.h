@@ -188,6 +188,24 @@ int flatgfa_interval_depth(flatgfa_t gfa, uint32_t path_index, const uint64_t *s
                            uint64_t n_intervals, double *depth_out);
 /* The bytes `fgfa window-depth PATH SIZE` prints (window_depth.rs:183-200, cli/cmds.rs:488-496). */
 int flatgfa_window_depth_table(flatgfa_t gfa, uint32_t path_index, uint64_t window, char **text, size_t *len);
+/* The pangenotype matrix (flatgfa/src/ops/pangenotype.rs:11-70; flatgfa-py's make_pangenotype_matrix):
+ * row f says, for every segment id s, whether some line of GAF text gaf[f][0, gaf_len[f]) names s in its
+ * path field.  A line is the bytes before a '\n' (what follows the last '\n' is not one); empty lines and
+ * lines that start with '#' are skipped; the path field is what follows the 5th tab, up to the next tab;
+ * every '>' or '<' in it starts a name, its digits read as a u64 (wrapping) and looked up in the graph's
+ * NameMap.  bits_out holds n_files rows of ceil(S / 64) words: bit s & 63 of word s >> 6 of row f is
+ * segment s (np.unpackbits(..., bitorder="little") order).  Each buffer goes to the device in chunks cut
+ * after a '\n', through the process's pinned staging, copies overlapping the scan of the chunk before;
+ * device memory is two chunks and one row, all freed before the call returns.  A name the graph does not
+ * have (name 0 included: a '>' with no digits), where the reference panics: FLATGFA_ERR_BOUNDS, and
+ * flatgfa_last_error() names the file's index and the byte offset of the first such line.  The graph need
+ * not be resident, and this does not make it so. */
+int flatgfa_pangenotype_matrix(flatgfa_t gfa, const uint8_t *const *gaf, const size_t *gaf_len, uint32_t n_files,
+                               uint64_t *bits_out);
+/* The bytes `fgfa matrix GAF` prints (cli/cmds.rs:465-474) for these files: one line per file, a '0' or
+ * '1' per segment id.  *text is malloc'd; release with flatgfa_free_text. */
+int flatgfa_pangenotype_table(flatgfa_t gfa, const uint8_t *const *gaf, const size_t *gaf_len, uint32_t n_files,
+                              char **text, size_t *len);
 /* The bytes `fgfa depth -b FILE.bed` prints (window_depth.rs:203-211, cli/cmds.rs:246-255); the BED
  * text is parsed as flatbed.rs:125-158 does. */
 int flatgfa_bed_depth_table(flatgfa_t gfa, const uint8_t *bed, size_t bed_len, char **text, size_t *len);
@@ -357,6 +375,14 @@ int flatgfa_dev_path_depth_all(flatgfa_dev_plan_t *plan, uint32_t *depth_out, ui
  * number of paths. */
 int flatgfa_dev_path_overlaps(flatgfa_dev_plan_t *plan, const uint32_t *query_ids, uint32_t n_q, uint8_t *touch_out,
                               void *stream);
+/* One pangenotype row on device (as flatgfa_pangenotype_matrix, for one piece of text): d_text[0, len) is
+ * GAF text in device memory of the current device, made of whole lines (what follows its last '\n' is
+ * ignored).  The segments it names are OR-ed into d_row (ceil(S / 64) u64 words, bit s & 63 of word s >> 6),
+ * so a caller may feed a file in pieces of its own; a name the graph does not have lowers *d_first_bad
+ * (atomic min) to the offset of its line in d_text.  The graph's name table is built on the first call
+ * for the device and kept with the handle.  Enqueued on `stream`; returns without waiting. */
+int flatgfa_dev_pangenotype_row(flatgfa_t gfa, const uint8_t *d_text, size_t len, uint64_t *d_row, uint64_t *d_first_bad,
+                                void *stream);
 /* Synchronizes `stream`, then returns FLATGFA_OK, or FLATGFA_ERR_BOUNDS if any kernel since the
  * last call saw a segment id >= n_segs or a path id >= n_paths.  Plans size their scratch for the
  * graph when they are created; should a node-depth call nevertheless have run out of scratch room

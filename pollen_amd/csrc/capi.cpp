@@ -19,11 +19,13 @@
 #include <malloc.h>
 
 #include <climits>
+#include <cstring>
 
 #include "../../include/flatgfa.h"
 #include "device_common.hpp"
 #include "temp_arena.hpp"
 #include "flatgfa_core.hpp"
+#include "gaf_device.hpp"
 
 using fgfa_dev::set_error;
 
@@ -87,6 +89,15 @@ struct CStore {
     flatgfa_dev_plan_t *sub_plan = nullptr;
     uint32_t *d_sub_spans = nullptr;  // the subset's begin[] then end[]
     std::atomic<int> steps_ok{-1};  // -1 = not checked yet: do all step handles name a segment? (host-side walks index by them)
+    // pangenotype: the graph's NameMap on one device (made on first use; it needs the segments only, never the steps), and
+    // the scratch of flatgfa_dev_pangenotype_row with the event after its last use
+    int gaf_device = -1;
+    uint64_t *d_gaf_names = nullptr;  // the `others` names, sorted, then their ids
+    fgfa_dev::GafNameTable gaf_names;
+    int gaf_scratch_device = -1;
+    uint64_t *d_gaf_scratch = nullptr;
+    size_t gaf_scratch_words = 0;
+    hipEvent_t gaf_ev = nullptr;
 
     ~CStore() {
         if (plan) flatgfa_dev_plan_destroy(plan);
@@ -94,6 +105,10 @@ struct CStore {
         if (d_sub_spans) (void)hipFree(d_sub_spans);
         for (uint32_t *p : {d_steps, d_small})
             if (p) (void)hipFree(p);
+        if (gaf_ev) (void)hipEventSynchronize(gaf_ev);
+        for (uint64_t *p : {d_gaf_names, d_gaf_scratch})
+            if (p) (void)hipFree(p);
+        if (gaf_ev) (void)hipEventDestroy(gaf_ev);
         stream_release(device, stream);
     }
 };
@@ -956,6 +971,220 @@ int flatgfa_seg_depth_subset(flatgfa_t gfa, const uint32_t *path_ids, uint32_t n
     if (!rc) rc = fetch_widen(gfa, gfa->d_depth, depth_out);
     if (!rc && uniq_out) rc = fetch_widen(gfa, gfa->d_uniq, uniq_out);
     return rc;
+}
+
+// ---- pangenotype matrix from GAF text (ops/pangenotype.rs) ----
+
+// The handle's name table on `device` (the current device), made once: NameMap::build over the segments (namemap.rs:36-42).
+static int ensure_gaf_names(CStore *cs, int device) {
+    if (cs->gaf_device == device) return FLATGFA_OK;
+    const fgfa::View &v = cs->view;
+    if (v.segs.len > 0x80000000ull) { set_error("pangenotype: more than 2^31 segments"); return FLATGFA_ERR_TOO_LARGE; }
+    fgfa::NameMap names;
+    for (size_t i = 0; i < v.segs.len; ++i) names.insert(v.segs[i].name, (uint32_t)i);
+    uint64_t seq_max = 0;
+    std::vector<std::pair<uint64_t, uint32_t>> others;
+    names.export_sorted(&seq_max, &others);
+    const size_t n = others.size();
+    std::vector<uint64_t> host(n + (n + 1) / 2, 0);
+    uint32_t *ids = reinterpret_cast<uint32_t *>(host.data() + n);
+    for (size_t i = 0; i < n; ++i) {
+        host[i] = others[i].first;
+        ids[i] = others[i].second;
+    }
+    uint64_t *d = nullptr;
+    if (n) {
+        CAPI_HIP(hipMalloc(&d, host.size() * 8));
+        if (hipMemcpy(d, host.data(), host.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            set_error("pangenotype: copying the name table to the device failed");
+            return FLATGFA_ERR_HIP;
+        }
+    }
+    if (cs->d_gaf_names) {
+        if (cs->gaf_ev) (void)hipEventSynchronize(cs->gaf_ev);  // (a device-entry call may still read the old one)
+        (void)hipFree(cs->d_gaf_names);
+    }
+    cs->d_gaf_names = d;
+    cs->gaf_names.keys = d;
+    cs->gaf_names.ids = d ? reinterpret_cast<const uint32_t *>(d + n) : nullptr;
+    cs->gaf_names.n_others = (uint32_t)n;
+    cs->gaf_names.n_segs = (uint32_t)v.segs.len;
+    cs->gaf_names.seq_max = seq_max;
+    cs->gaf_device = device;
+    return FLATGFA_OK;
+}
+
+static int gaf_bad_line(uint32_t file, uint64_t offset) {
+    set_error("pangenotype: GAF file " + std::to_string(file) + ": the line at byte offset " + std::to_string(offset) +
+              " names a segment that is not in the graph");
+    return FLATGFA_ERR_BOUNDS;
+}
+
+// A copy of host bytes to the device, synchronous: large ones as the step pool's upload does (threads staging into the pinned
+// buffers), the rest through plan_memcpy (pinned staging from 4 MB up).
+static hipError_t gaf_copy(void *dst, const void *src, size_t bytes, hipStream_t stream) {
+    if (bytes >= 4 * kChunk) return upload(dst, src, bytes, stream);
+    return fgfa_dev::plan_memcpy(dst, src, bytes, hipMemcpyHostToDevice);
+}
+
+int flatgfa_pangenotype_matrix(flatgfa_t gfa, const uint8_t *const *gaf, const size_t *gaf_len, uint32_t n_files,
+                               uint64_t *bits_out) {
+    if (!gfa || (n_files && (!gaf || !gaf_len || !bits_out))) { set_error("flatgfa_pangenotype_matrix: NULL argument"); return FLATGFA_ERR_ARG; }
+    for (uint32_t f = 0; f < n_files; ++f)
+        if (gaf_len[f] && !gaf[f]) { set_error("flatgfa_pangenotype_matrix: NULL text with a length"); return FLATGFA_ERR_ARG; }
+    if (n_files == 0) return FLATGFA_OK;
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    int device = 0;
+    {
+        std::lock_guard<std::mutex> lk(gfa->dev_mu);
+        if (gfa->on_device) device = gfa->device;  // (beside the graph, when it is resident; it is not made so)
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_error("no HIP device is visible; the pangenotype matrix has no CPU fallback");
+        return FLATGFA_ERR_NO_DEVICE;
+    }
+    CAPI_HIP(hipSetDevice(device));
+    int rc = ensure_gaf_names(gfa, device);
+    if (rc) return rc;
+    const size_t S = gfa->view.segs.len, W = (S + 63) / 64;
+
+    // Chunks cut after a '\n', at most `target` bytes unless one line is longer; the bytes behind a file's last '\n' are dropped.
+    size_t target = (size_t)64 << 20;
+    if (const char *h = test_hook("FLATGFA_GAF_CHUNK_BYTES")) target = std::max<size_t>(1, strtoull(h, nullptr, 10));  // tests
+    struct Piece {
+        uint32_t file;
+        size_t begin, end;
+    };
+    std::vector<Piece> pieces;
+    size_t cap = 16;
+    for (uint32_t f = 0; f < n_files; ++f) {
+        const uint8_t *t = gaf[f];
+        const size_t n = gaf_len[f];
+        const void *last = n ? memrchr(t, '\n', n) : nullptr;
+        const size_t end = last ? (size_t)((const uint8_t *)last - t) + 1 : 0;
+        for (size_t b = 0; b < end;) {
+            size_t e = end;
+            if (end - b > target) {
+                const void *q = memrchr(t + b, '\n', target);
+                if (!q) q = memchr(t + b + target, '\n', end - b - target);  // a line longer than a chunk grows it
+                e = (size_t)((const uint8_t *)q - t) + 1;
+            }
+            pieces.push_back(Piece{f, b, e});
+            cap = std::max(cap, e - b);
+            b = e;
+        }
+    }
+    cap = (cap + 255) & ~(size_t)255;
+    const size_t scratch_words = fgfa_dev::gaf_scratch_words(nullptr, cap);  // (the text buffers are 256-byte aligned)
+
+    // One allocation: two text buffers and their scratch, the row, the first bad offset.  Freed before returning.
+    uint8_t *block = nullptr;
+    const size_t per = (cap + scratch_words * 8 + 255) & ~(size_t)255;
+    CAPI_HIP(hipMalloc(&block, 2 * per + W * 8 + 8));
+    hipStream_t ks = nullptr, cs = nullptr;
+    hipEvent_t done[2] = {nullptr, nullptr};
+    struct Release {
+        int device;
+        uint8_t *&block;
+        hipStream_t &ks, &cs;
+        hipEvent_t *done;
+        ~Release() {
+            if (ks) (void)hipStreamSynchronize(ks);
+            for (int i = 0; i < 2; ++i)
+                if (done[i]) (void)hipEventDestroy(done[i]);
+            (void)hipFree(block);
+            stream_release(device, ks);
+            stream_release(device, cs);
+        }
+    } release{device, block, ks, cs, done};
+    CAPI_HIP(stream_acquire(device, &ks));
+    CAPI_HIP(stream_acquire(device, &cs));
+    for (int i = 0; i < 2; ++i) CAPI_HIP(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
+    uint8_t *d_text[2] = {block, block + per};
+    uint64_t *d_scratch[2] = {reinterpret_cast<uint64_t *>(block + cap), reinterpret_cast<uint64_t *>(block + per + cap)};
+    uint64_t *d_row = reinterpret_cast<uint64_t *>(block + 2 * per), *d_bad = d_row + W;
+    bool used[2] = {false, false};
+    size_t k = 0;  // the next piece
+    std::vector<uint64_t> bad(1);
+    for (uint32_t f = 0; f < n_files; ++f) {
+        if (W) CAPI_HIP(hipMemsetAsync(d_row, 0, W * 8, ks));
+        CAPI_HIP(hipMemsetAsync(d_bad, 0xFF, 8, ks));
+        for (; k < pieces.size() && pieces[k].file == f; ++k) {
+            const int b = (int)(k & 1);
+            if (used[b]) CAPI_HIP(hipEventSynchronize(done[b]));  // the scan that read this buffer is over
+            const size_t len = pieces[k].end - pieces[k].begin;
+            CAPI_HIP(gaf_copy(d_text[b], gaf[f] + pieces[k].begin, len, cs));  // (beside the scan of the piece before, on ks)
+            CAPI_HIP(fgfa_dev::gaf_scan(d_text[b], len, gfa->gaf_names, d_row, d_bad, pieces[k].begin, d_scratch[b], ks));
+            CAPI_HIP(hipEventRecord(done[b], ks));
+            used[b] = true;
+        }
+        if (W) CAPI_HIP(hipMemcpyAsync(bits_out + (size_t)f * W, d_row, W * 8, hipMemcpyDeviceToHost, ks));
+        CAPI_HIP(hipMemcpyAsync(bad.data(), d_bad, 8, hipMemcpyDeviceToHost, ks));
+        CAPI_HIP(hipStreamSynchronize(ks));
+        if (bad[0] != ~0ull) return gaf_bad_line(f, bad[0]);
+    }
+    return FLATGFA_OK;
+}
+
+int flatgfa_pangenotype_table(flatgfa_t gfa, const uint8_t *const *gaf, const size_t *gaf_len, uint32_t n_files, char **text,
+                              size_t *len) {
+    if (!gfa || !text) { set_error("flatgfa_pangenotype_table: NULL argument"); return FLATGFA_ERR_ARG; }
+    const size_t S = gfa->view.segs.len, W = (S + 63) / 64;
+    std::vector<uint64_t> bits((size_t)n_files * W);
+    const int rc = flatgfa_pangenotype_matrix(gfa, gaf, gaf_len, n_files, bits.empty() ? nullptr : bits.data());
+    if (rc) return rc;
+    // cmds.rs:466-474: a '1' or '0' per segment, a newline per file
+    const size_t n = (size_t)n_files * (S + 1);
+    char *p = (char *)malloc(n + 1);
+    if (!p) { set_error("out of memory"); return FLATGFA_ERR_IO; }
+    for (uint32_t f = 0; f < n_files; ++f) {
+        char *o = p + (size_t)f * (S + 1);
+        const uint64_t *row = bits.data() + (size_t)f * W;
+        for (size_t s = 0; s < S; ++s) o[s] = (char)('0' + ((row[s >> 6] >> (s & 63)) & 1u));
+        o[S] = '\n';
+    }
+    p[n] = 0;
+    *text = p;
+    if (len) *len = n;
+    return FLATGFA_OK;
+}
+
+int flatgfa_dev_pangenotype_row(flatgfa_t gfa, const uint8_t *d_text, size_t len, uint64_t *d_row, uint64_t *d_first_bad,
+                                void *stream_) {
+    if (!gfa || (len && (!d_text || !d_first_bad)) || (len && gfa->view.segs.len && !d_row)) {
+        set_error("flatgfa_dev_pangenotype_row: NULL argument");
+        return FLATGFA_ERR_ARG;
+    }
+    if (len == 0) return FLATGFA_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    int device = 0;
+    CAPI_HIP(hipGetDevice(&device));
+    int rc = ensure_gaf_names(gfa, device);
+    if (rc) return rc;
+    const size_t words = fgfa_dev::gaf_scratch_words(d_text, len);
+    if (gfa->gaf_scratch_device != device || gfa->gaf_scratch_words < words) {
+        if (gfa->gaf_ev) {  // the last call's kernels may still read the old scratch
+            (void)hipEventSynchronize(gfa->gaf_ev);
+            (void)hipEventDestroy(gfa->gaf_ev);
+            gfa->gaf_ev = nullptr;
+        }
+        if (gfa->d_gaf_scratch) (void)hipFree(gfa->d_gaf_scratch);
+        gfa->d_gaf_scratch = nullptr;
+        gfa->gaf_scratch_words = 0;
+        gfa->gaf_scratch_device = -1;
+        CAPI_HIP(hipMalloc(&gfa->d_gaf_scratch, words * 8));
+        gfa->gaf_scratch_words = words;
+        gfa->gaf_scratch_device = device;
+        CAPI_HIP(hipEventCreateWithFlags(&gfa->gaf_ev, hipEventDisableTiming));
+    } else {
+        CAPI_HIP(hipStreamWaitEvent(stream, gfa->gaf_ev, 0));  // (the scratch is free once the last call on any stream is done)
+    }
+    CAPI_HIP(fgfa_dev::gaf_scan(d_text, len, gfa->gaf_names, d_row, d_first_bad, 0, gfa->d_gaf_scratch, stream));
+    CAPI_HIP(hipEventRecord(gfa->gaf_ev, stream));
+    return FLATGFA_OK;
 }
 
 }  // extern "C"

@@ -3,11 +3,11 @@
 //
 //   fgfa [-i FILE.flatgfa | -I FILE.gfa] [-o OUT.flatgfa] [-O OUT.gfa] [COMMAND]
 //   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [-s PATHS]
-//            | window-depth PATH SIZE | overlap --paths FILE
+//            | window-depth PATH SIZE | overlap --paths FILE | matrix GAF
 //
 // With no -i/-I the GFA text is read from stdin; with no COMMAND the graph is written out
 // (-o binary, -O text, otherwise text on stdout).  `depth` output is byte-identical to the
-// reference's and is computed on the GPU.  Everything else in the reference CLI is out of scope.
+// reference's and is computed on the GPU, as is `matrix` (cmds.rs:453-475).  Everything else in the reference CLI is out of scope.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -106,7 +106,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "overlap";
+    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "overlap" || cmd == "matrix";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -136,7 +136,7 @@ int main(int argc, char **argv) {
         return die("cannot load graph");
     }
 #ifdef MADV_POPULATE_READ
-    if (wants_device && in_flat) {  // (a freshly mapped file: one call instead of a fault per page inside the upload's copies)
+    if (wants_device && in_flat && cmd != "matrix") {  // (a freshly mapped file: one call instead of a fault per page inside the upload's copies)
         const void *steps = nullptr;
         uint64_t n = 0, es = 0;
         if (flatgfa_pool(g, 4, &steps, &n, &es) == 0 && n) {
@@ -281,6 +281,29 @@ int main(int argc, char **argv) {
         uint32_t dummy = 0;
         if (flatgfa_overlap_table(g, ids.empty() ? &dummy : ids.data(), (uint32_t)ids.size(), &text, &n)) rc = die("overlap");
         else write_all(text, n);
+        flatgfa_free_text(text);
+    } else if (cmd == "matrix") {
+        // cli/cmds.rs:453-475: fgfa matrix GAF -- exactly one GAF file
+        if (i + 1 != argc) { fprintf(stderr, "usage: fgfa matrix GAF\n"); flatgfa_free(g); return 2; }
+        const char *gaf = argv[i];
+        const int fd = open(gaf, O_RDONLY);
+        struct stat sb;
+        if (fd < 0 || fstat(fd, &sb) != 0) {
+            fprintf(stderr, "fgfa: cannot open %s\n", gaf);
+            if (fd >= 0) close(fd);
+            flatgfa_free(g);
+            return 1;
+        }
+        const size_t n = (size_t)sb.st_size;
+        void *m = n ? mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0) : nullptr;
+        close(fd);
+        if (m == MAP_FAILED) { fprintf(stderr, "fgfa: cannot map %s\n", gaf); flatgfa_free(g); return 1; }
+        if (m) (void)madvise(m, n, MADV_SEQUENTIAL);  // (read once, front to back; the copies fault the pages in chunk by chunk)
+        const uint8_t *text_in = (const uint8_t *)m;
+        char *text = nullptr;
+        size_t len = 0;
+        if (flatgfa_pangenotype_table(g, &text_in, &n, 1, &text, &len)) rc = die("matrix");
+        else write_all(text, len);
         flatgfa_free_text(text);
     } else {
         fprintf(stderr, "fgfa: command '%s' is outside the depth path this build covers\n", cmd.c_str());

@@ -114,6 +114,12 @@ bool NameMap::get(uint64_t name, uint32_t *id) const {
     return true;
 }
 
+void NameMap::export_sorted(uint64_t *seq_max, std::vector<std::pair<uint64_t, uint32_t>> *others) const {
+    *seq_max = sequential_max_;
+    others->assign(others_.begin(), others_.end());
+    std::sort(others->begin(), others->end());
+}
+
 // ----------------------------------------------------------------- parser ---
 
 namespace {

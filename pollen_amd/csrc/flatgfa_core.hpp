@@ -17,6 +17,7 @@ inline const char *test_hook(const char *name) { return std::getenv(name); }
 #include <cstring>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 namespace fgfa {
@@ -194,6 +195,8 @@ class NameMap {
     void insert(uint64_t name, uint32_t id);
     // false where the reference would panic on a missing key
     bool get(uint64_t name, uint32_t *id) const;
+    // the table as it stands: names up to *seq_max are id = name - 1; the others, sorted by name
+    void export_sorted(uint64_t *seq_max, std::vector<std::pair<uint64_t, uint32_t>> *others) const;
 
   private:
     uint64_t sequential_max_ = 0;

@@ -282,6 +282,23 @@ class DepthPipeline:
         return buf.value.decode()
 
 
+def pangenotype_row(gfa, text, row, first_bad, stream=None) -> None:
+    """Enqueue one pangenotype row (flatgfa_dev_pangenotype_row): the segments that the whole lines of GAF text in `text`
+    (a uint8 CUDA tensor; what follows its last newline is ignored) name are OR-ed into `row` (int64[ceil(S / 64)]: bit
+    s & 63 of word s >> 6 is segment s), and a name the graph lacks lowers first_bad[0] (int64; set it to -1, all ones,
+    first) to its line's byte offset.  `gfa` is a FlatGFA; `stream` defaults to torch's current stream."""
+    torch = _torch()
+    S = gfa.segment_count
+    assert text.dtype == torch.uint8 and text.is_cuda and text.is_contiguous()
+    assert row.dtype == torch.int64 and row.is_cuda and row.is_contiguous() and row.numel() == (S + 63) // 64
+    assert first_bad.dtype == torch.int64 and first_bad.is_cuda and first_bad.numel() >= 1
+    with torch.cuda.device(text.device):
+        st = stream if stream is not None else torch.cuda.current_stream(text.device)
+        n = int(text.numel())
+        _check(_lib.lib().flatgfa_dev_pangenotype_row(gfa._h, text.data_ptr() if n else None, n, row.data_ptr() if row.numel() else None,
+                                                      first_bad.data_ptr(), ctypes.c_void_p(st.cuda_stream)), "dev_pangenotype_row")
+
+
 def profile_enable(on: bool) -> None:
     _lib.lib().flatgfa_dev_profile_enable(1 if on else 0)
 

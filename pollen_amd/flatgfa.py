@@ -11,6 +11,7 @@ implementation of them in this package.
 from __future__ import annotations
 
 import ctypes
+import mmap
 import os
 from typing import Iterable, List, Optional, Sequence, Tuple, Union
 
@@ -307,6 +308,57 @@ class FlatGFA:
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         _check(_lib.lib().flatgfa_bed_depth_table(self._h, bed, len(bed), ctypes.byref(p), ctypes.byref(n)),
                "bed_depth_table")
+        return _take_text(p, n)
+
+    def _gaf_call(self, gafs, call):
+        """`call(ptrs, lens, n)` over GAF texts: file names are mapped (never read into Python), bytes-likes passed as they are."""
+        maps, arrs = [], []
+        try:
+            for g in gafs:
+                if isinstance(g, (bytes, bytearray, memoryview)):
+                    arrs.append(np.frombuffer(g, dtype=np.uint8))
+                    continue
+                with open(g, "rb") as f:
+                    size = os.fstat(f.fileno()).st_size
+                    if size == 0:  # (mmap cannot map an empty file)
+                        arrs.append(np.zeros(0, dtype=np.uint8))
+                        continue
+                    m = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+                maps.append(m)
+                arrs.append(np.frombuffer(m, dtype=np.uint8))
+            n = len(arrs)
+            ptrs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+            lens = (ctypes.c_size_t * max(n, 1))(*[a.size for a in arrs])
+            return call(ptrs, lens, n)
+        finally:
+            arrs.clear()
+            for m in maps:
+                try:
+                    m.close()
+                except BufferError:  # (a view of it is still alive somewhere: the mapping goes with it)
+                    pass
+
+    def pangenotype_matrix(self, gafs) -> np.ndarray:
+        """bool[len(gafs), segment_count]: which segments some alignment of each GAF names in its path field
+        (flatgfa/src/ops/pangenotype.rs:11-70).  `gafs`: file names or bytes, one per row."""
+        gafs = list(gafs)
+        S = self.segment_count
+        W = (S + 63) // 64
+        bits = np.zeros((len(gafs), W), dtype=np.uint64)
+        self._gaf_call(gafs, lambda p, l, n: _check(
+            _lib.lib().flatgfa_pangenotype_matrix(self._h, p, l, n, bits.ctypes.data if bits.size else None), "pangenotype_matrix"))
+        return np.unpackbits(bits.view(np.uint8), axis=1, bitorder="little")[:, :S].astype(bool)
+
+    def make_pangenotype_matrix(self, gaf_files: Sequence[str]) -> List[List[bool]]:
+        """flatgfa-py's FlatGFA.make_pangenotype_matrix (flatgfa.pyi:89): one list of bools per GAF file."""
+        return self.pangenotype_matrix(gaf_files).tolist()
+
+    def pangenotype_table(self, gafs) -> bytes:
+        """The bytes `fgfa matrix GAF` prints (cli/cmds.rs:465-474), a line per item of `gafs`."""
+        gafs = list(gafs)
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._gaf_call(gafs, lambda ptrs, lens, k: _check(
+            _lib.lib().flatgfa_pangenotype_table(self._h, ptrs, lens, k, ctypes.byref(p), ctypes.byref(n)), "pangenotype_table"))
         return _take_text(p, n)
 
 
