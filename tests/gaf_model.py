@@ -1,10 +1,12 @@
 """A plain-Python restatement of the reference's pangenotype matrix, for the tests only.
 
 cucapra/pollen flatgfa/src/ops/pangenotype.rs:11-70 (make_pangenotype_matrix) and flatgfa/src/namemap.rs:7-43 (NameMap),
-rule by rule; the product (pollen_amd/) never imports it.  It is slow -- a byte at a time -- and meant for small inputs.
+rule by rule; the product (pollen_amd/) never imports it.  row() is slow -- a byte at a time -- and meant for small inputs;
+row_fast() reads a line at a time, for texts of many MB, and tests/test_pangenotype_model.py pins it to row().
 """
 from __future__ import annotations
 
+import re
 from typing import Dict, List, Sequence, Tuple
 
 U64 = (1 << 64) - 1
@@ -93,3 +95,48 @@ def matrix(texts: Sequence[bytes], seg_names: Sequence[int]) -> List[List[bool]]
 def table(texts: Sequence[bytes], seg_names: Sequence[int]) -> bytes:
     """What `fgfa matrix GAF` prints (cmds.rs:465-474)."""
     return b"".join(b"".join(b"1" if c else b"0" for c in r) + b"\n" for r in matrix(texts, seg_names))
+
+
+# ---- the same rules a line at a time, for texts of many MB ----
+
+_TOKEN = re.compile(rb"[<>]([0-9]*)")
+_FOLD = 19  # decimal digits that always fit in a u64
+
+
+def digits_mod_2_64(digits: bytes) -> int:
+    """The u64 that wrapping `num * 10 + d` reads from a run of ASCII digits (pangenotype.rs:55-58).  Python's int() refuses
+    strings of more than sys.get_int_max_str_digits() digits, so the run is folded 19 digits at a time."""
+    digits = digits.lstrip(b"0")
+    v = 0
+    for i in range(0, len(digits), _FOLD):
+        part = digits[i:i + _FOLD]
+        v = (v * 10 ** len(part) + int(part)) & U64
+    return v
+
+
+def row_fast(text: bytes, seg_names: Sequence[int], file: int = 0, nm=None) -> List[bool]:
+    """What row() gives, line by line: split at '\\n' (the tail behind the last one is no line), skip empty and '#' lines,
+    the path field is the 6th tab-separated part, every '>' or '<' in it starts a token."""
+    nm = nm if nm is not None else name_map(seg_names)
+    S = len(seg_names)
+    out = [False] * S
+    off = 0
+    for line in text[:text.rfind(b"\n") + 1].split(b"\n")[:-1]:
+        line_off, off = off, off + len(line) + 1
+        if not line or line[0] == HASH:
+            continue
+        parts = line.split(b"\t", 6)
+        if len(parts) < 6:
+            continue
+        for digits in set(_TOKEN.findall(parts[5])):
+            sid = lookup(nm, digits_mod_2_64(digits))
+            if sid is None or sid >= S:
+                raise GafError(file, line_off)
+            out[sid] = True
+    return out
+
+
+def matrix_fast(texts: Sequence[bytes], seg_names: Sequence[int]) -> List[List[bool]]:
+    """matrix() by row_fast."""
+    nm = name_map(seg_names)
+    return [row_fast(t, seg_names, f, nm) for f, t in enumerate(texts)]

@@ -3,9 +3,11 @@ argument checks of the C ABI, which need no device."""
 import ctypes
 import os
 
+import numpy as np
 import pytest
 
 import gaf_model as gm
+import gaf_shapes as gs
 import pollen_amd as pa
 from conftest import GOLDEN
 from pollen_amd import _lib
@@ -109,3 +111,81 @@ def test_abi_rejects_null_arguments_without_a_device():
         assert lib.flatgfa_dev_pangenotype_row(g._h, None, 16, None, None, None) == -1
     finally:
         g.close()
+
+
+# ---- row_fast (a line at a time) pinned to row (a byte at a time) ----
+
+def test_digits_mod_2_64():
+    for s in (b"", b"0", b"000", b"7", b"0018446744073709551615", b"18446744073709551616", b"9" * 19, b"9" * 20,
+              b"1234567890123456789012345"):
+        assert gm.digits_mod_2_64(s) == int(s or b"0") % (1 << 64), s
+    # past int()'s default limit on digit strings (4 300)
+    assert gm.digits_mod_2_64(b"0" * 100_000 + b"47") == 47
+    assert gm.digits_mod_2_64(b"1" + b"0" * 5000) == pow(10, 5000, 1 << 64)
+    assert gm.digits_mod_2_64(b"3" * 4999) == sum(3 * pow(10, i, 1 << 64) for i in range(4999)) % (1 << 64)
+
+
+def outcome(fn, texts, names):
+    try:
+        return fn(texts, names)
+    except gm.GafError as e:
+        return ("error", e.file, e.offset)
+
+
+def soup(rng, names, n, unknown):
+    """Bytes from the alphabet the rules look at, in runs, naming known segments (and, one token in `unknown`, a name
+    the graph lacks)."""
+    pieces = [b"\t", b"\n", b"\n\n", b"#", b"x", b"\r\n", b"\t\t\t\t\t"]
+    out, size = [], 0
+    while size < n:
+        k = int(rng.integers(0, len(pieces) + 4))
+        if k < len(pieces):
+            out.append(pieces[k])
+        elif unknown and rng.integers(unknown) == 0:
+            out.append(b"<%d" % int(rng.integers(0, 60)) if k % 2 else b">")
+        else:
+            out.append((b">0%d" if k % 3 else b"<%d") % names[int(rng.integers(len(names)))])
+        size += len(out[-1])
+    return b"".join(out)
+
+
+@pytest.mark.parametrize("tile", [64, 128])
+@pytest.mark.parametrize("seed", range(6))
+def test_row_fast_matches_row_on_tile_shapes(tile, seed):
+    # every generator of tests/gaf_shapes.py with tiny tiles, each alone, all in one text in shuffled order, and in several
+    # texts of one matrix; the shapes' own claims (names they set, the error offset) hold for both models
+    shapes = gs.good_shapes(tile, seed) + gs.bad_shapes(tile, seed)
+    idx = {n: i for i, n in enumerate(gs.NAMES)}
+    for label, sh in shapes:
+        want = outcome(gm.matrix, [sh.text], gs.NAMES)
+        assert outcome(gm.matrix_fast, [sh.text], gs.NAMES) == want, label
+        if sh.bad is not None:
+            assert want == ("error", 0, sh.bad), label
+            continue
+        assert not isinstance(want, tuple), (label, want)
+        got = {n for n in gs.NAMES if want[0][idx[n]]}
+        assert sh.sets <= got and (not sh.exact or got == sh.sets), label
+    rng = np.random.default_rng(seed)
+    good = [sh.text for _, sh in shapes[:-2]]
+    mixed = b"".join(good[int(i)] for i in rng.permutation(len(good)))
+    texts = [mixed, b"", good[0]]
+    assert outcome(gm.matrix_fast, texts, gs.NAMES) == outcome(gm.matrix, texts, gs.NAMES)
+    g_text = shapes[-2][1].text
+    texts = [mixed, g_text + mixed, g_text]
+    want = outcome(gm.matrix, texts, gs.NAMES)
+    assert want == ("error", 1, shapes[-2][1].bad)
+    assert outcome(gm.matrix_fast, texts, gs.NAMES) == want
+
+
+@pytest.mark.parametrize("seed", range(100))
+def test_row_fast_matches_row_on_byte_soup(seed):
+    rng = np.random.default_rng(1000 + seed)
+    names = [int(x) for x in rng.permutation([1, 2, 3, 4, 5, 6, 977, 2**63, 2**64 - 1, 0, 5, 40])[:int(rng.integers(4, 12))]]
+    text = soup(rng, [n for n in names if n] + [18446744073709551617] * (1 in names), int(rng.integers(50, 3000)), seed % 3 * 40)
+    assert outcome(gm.matrix_fast, [text], names) == outcome(gm.matrix, [text], names)
+
+
+@pytest.mark.parametrize("name", sorted(EDGE_LINES))
+def test_row_fast_on_edge_lines(name):
+    text, want = EDGE_LINES[name]
+    assert gm.row_fast(text, TINY) == want
