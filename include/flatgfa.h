@@ -206,6 +206,18 @@ int flatgfa_pangenotype_matrix(flatgfa_t gfa, const uint8_t *const *gaf, const s
  * '1' per segment id.  *text is malloc'd; release with flatgfa_free_text. */
 int flatgfa_pangenotype_table(flatgfa_t gfa, const uint8_t *const *gaf, const size_t *gaf_len, uint32_t n_files,
                               char **text, size_t *len);
+/* chop (flatgfa/src/ops/chop.rs; `fgfa chop -c max_size [-l]`, cli/main.rs:139-159): every segment longer
+ * than max_size becomes ceil(len / max_size) segments -- max_size bases each, the remainder last -- numbered in
+ * segment order and named id + 1; a step becomes the steps of its pieces (reversed, all backward, for a backward
+ * step); paths keep their names and lose their overlaps.  links != 0: the forward links between the pieces of each
+ * chopped segment, then every old link remapped to the pieces it touches (from: the last piece of a forward handle,
+ * the first of a backward one; to: the other way round), all with an empty alignment; links == 0: no links.  *out is a
+ * new heap handle that owns copies of what it keeps of `gfa` (header, seq_data, name_data), so it outlives `gfa`.
+ * The counts, scans and expansion run on the GPU (the device `gfa` is resident on, else device 0); `gfa` is not
+ * made resident, and a resident one is only read.  max_size == 0 (where the reference loops forever):
+ * FLATGFA_ERR_ARG; a span, step or link naming something out of range: FLATGFA_ERR_BOUNDS; 2^31 or more new
+ * segments, or more than 2^32 - 1 new steps or links: FLATGFA_ERR_TOO_LARGE, found before any output is allocated. */
+int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out);
 /* The bytes `fgfa depth -b FILE.bed` prints (window_depth.rs:203-211, cli/cmds.rs:246-255); the BED
  * text is parsed as flatbed.rs:125-158 does. */
 int flatgfa_bed_depth_table(flatgfa_t gfa, const uint8_t *bed, size_t bed_len, char **text, size_t *len);
@@ -383,6 +395,22 @@ int flatgfa_dev_path_overlaps(flatgfa_dev_plan_t *plan, const uint32_t *query_id
  * for the device and kept with the handle.  Enqueued on `stream`; returns without waiting. */
 int flatgfa_dev_pangenotype_row(flatgfa_t gfa, const uint8_t *d_text, size_t len, uint64_t *d_row, uint64_t *d_first_bad,
                                 void *stream);
+/* chop (flatgfa_chop, without links) of a graph image in device memory, in two stream-ordered calls.
+ * flatgfa_dev_chop_count checks the image (g->seg_len is required: FLATGFA_ERR_ARG when NULL), scans the piece
+ * counts, waits for `stream` once to read the totals -- *n_segs_out new segments, *n_steps_out new steps -- and, when
+ * they fit 32-bit ids, enqueues seg_first u32[n_segs + 1] (device memory: old segment s became the new segments
+ * [seg_first[s], seg_first[s + 1])) and returns a job in *job; errors as flatgfa_chop's, with no job.
+ * flatgfa_dev_chop_fill enqueues on `stream` the chopped image into caller memory: steps u32[*n_steps_out],
+ * path_begin / path_end u32[n_paths] and seg_len u32[*n_segs_out] -- together a flatgfa_dev_graph_t of n_paths
+ * paths and *n_segs_out segments that flatgfa_dev_plan_create takes.  Path spans may be any spans (overlapping ones
+ * too); the new steps are the paths' expansions in path order.  g's arrays and seg_first must stay as they are until
+ * the fill is done.  flatgfa_dev_chop_free waits for the job's stream and releases its scratch. */
+typedef struct flatgfa_dev_chop flatgfa_dev_chop_t;
+int flatgfa_dev_chop_count(const flatgfa_dev_graph_t *g, uint64_t max_size, uint32_t *seg_first, void *stream, flatgfa_dev_chop_t **job,
+                           uint64_t *n_segs_out, uint64_t *n_steps_out);
+int flatgfa_dev_chop_fill(flatgfa_dev_chop_t *job, uint32_t *steps, uint32_t *path_begin, uint32_t *path_end, uint32_t *seg_len,
+                          void *stream);
+void flatgfa_dev_chop_free(flatgfa_dev_chop_t *job);
 /* Synchronizes `stream`, then returns FLATGFA_OK, or FLATGFA_ERR_BOUNDS if any kernel since the
  * last call saw a segment id >= n_segs or a path id >= n_paths.  Plans size their scratch for the
  * graph when they are created; should a node-depth call nevertheless have run out of scratch room

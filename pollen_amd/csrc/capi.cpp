@@ -26,6 +26,7 @@
 #include "temp_arena.hpp"
 #include "flatgfa_core.hpp"
 #include "gaf_device.hpp"
+#include "chop_device.hpp"
 
 using fgfa_dev::set_error;
 
@@ -1184,6 +1185,185 @@ int flatgfa_dev_pangenotype_row(flatgfa_t gfa, const uint8_t *d_text, size_t len
     }
     CAPI_HIP(fgfa_dev::gaf_scan(d_text, len, gfa->gaf_names, d_row, d_first_bad, 0, gfa->d_gaf_scratch, stream));
     CAPI_HIP(hipEventRecord(gfa->gaf_ev, stream));
+    return FLATGFA_OK;
+}
+
+// ---- chop (ops/chop.rs) ----
+
+// Device -> host copy of a large region through the process's pinned staging: the copy engine fills 8 MB chunks of the
+// pinned buffers while host threads move the chunks before them out to `dst` (a pageable hipMemcpy stages through one
+// buffer of the runtime's on one thread).  Waits for `stream`, on which the copies queue behind whatever wrote `src`.
+static hipError_t download(void *dst, const void *src, size_t bytes, hipStream_t stream) {
+    if (bytes < 4 * kChunk) {
+        const hipError_t e = bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
+        return e != hipSuccess ? e : hipStreamSynchronize(stream);
+    }
+    constexpr int kWorkers = 4, kBufs = 2 * kWorkers;
+    int device = 0;
+    hipError_t rc = hipGetDevice(&device);
+    if (rc != hipSuccess) return rc;
+    StagePool &pool = *stage_pool();
+    std::lock_guard<std::mutex> lk(pool.mu);
+    rc = pool.ensure(device, kBufs);
+    if (rc != hipSuccess) return rc;
+    const int64_t n_chunks = (int64_t)((bytes + kChunk - 1) / kChunk);
+    std::atomic<int64_t> enqueued{-1};
+    std::atomic<int64_t> copied[kBufs];
+    for (auto &c : copied) c = -1;
+    std::atomic<int> failed{0};
+    std::vector<std::thread> workers;
+    for (int t = 0; t < kWorkers; ++t)
+        workers.emplace_back([&, t]() {
+            if (hipSetDevice(device) != hipSuccess) { failed = (int)hipErrorInvalidDevice; return; }
+            for (int64_t c = t; c < n_chunks; c += kWorkers) {
+                while (enqueued.load(std::memory_order_acquire) < c)
+                    if (failed) return;
+                    else std::this_thread::yield();
+                const int b = (int)(c % kBufs);
+                const hipError_t e = hipEventSynchronize(pool.ev[b]);
+                if (e != hipSuccess) { failed = (int)e; return; }
+                const size_t off = (size_t)c * kChunk;
+                memcpy((char *)dst + off, pool.stage[b], std::min(kChunk, bytes - off));
+                copied[b].store(c, std::memory_order_release);
+            }
+        });
+    for (int64_t c = 0; c < n_chunks && !failed; ++c) {
+        const int b = (int)(c % kBufs);
+        while (c >= kBufs && copied[b].load(std::memory_order_acquire) < c - kBufs && !failed) std::this_thread::yield();
+        if (failed) break;
+        const size_t off = (size_t)c * kChunk;
+        hipError_t e = hipMemcpyAsync(pool.stage[b], (const char *)src + off, std::min(kChunk, bytes - off), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipEventRecord(pool.ev[b], stream);
+        if (e != hipSuccess) { failed = (int)e; break; }
+        enqueued.store(c, std::memory_order_release);
+    }
+    for (auto &w : workers) w.join();
+    const hipError_t e = hipStreamSynchronize(stream);
+    return failed ? (hipError_t)failed.load() : e;
+}
+
+int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
+    if (out) *out = nullptr;
+    if (!gfa || !out) { set_error("flatgfa_chop: NULL argument"); return FLATGFA_ERR_ARG; }
+    if (max_size == 0) { set_error("flatgfa_chop: the maximum segment size must be at least 1"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    const fgfa::View &v = gfa->view;
+    const size_t N = v.steps.len, P = v.paths.len, S = v.segs.len, L = links ? v.links.len : 0;
+    if (N > 0xFFFFFFFFull || S > 0x80000000ull || P > 0xFFFFFFFFull || L > 0xFFFFFFFFull) {
+        set_error("flatgfa_chop: graph too large for 32-bit ids");
+        return FLATGFA_ERR_TOO_LARGE;
+    }
+    int device = 0;
+    bool resident = false;
+    {
+        std::lock_guard<std::mutex> lk(gfa->dev_mu);
+        if (gfa->on_device) device = gfa->device, resident = true;  // (beside the graph, reading its image; it is not made resident)
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_error("no HIP device is visible; chop has no CPU fallback");
+        return FLATGFA_ERR_NO_DEVICE;
+    }
+    CAPI_HIP(hipSetDevice(device));
+    struct Release {
+        int device = 0;
+        hipStream_t stream = nullptr;
+        std::vector<void *> mem;
+        fgfa_dev::ChopJob *job = nullptr;
+        ~Release() {
+            if (stream) (void)hipStreamSynchronize(stream);
+            fgfa_dev::chop_free(job);
+            for (void *p : mem) (void)hipFree(p);
+            stream_release(device, stream);
+        }
+    } rel;
+    rel.device = device;
+    CAPI_HIP(stream_acquire(device, &rel.stream));
+    hipStream_t st = rel.stream;
+    auto dmalloc = [&](size_t bytes, void **p) -> hipError_t {
+        *p = nullptr;
+        if (!bytes) return hipSuccess;
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e == hipSuccess) rel.mem.push_back(*p);
+        return e;
+    };
+    // what chop reads: the steps, spans and lengths (the resident image's, when there is one), the seq starts, the links
+    const size_t Pa = (P + 63) & ~(size_t)63, Sa = (S + 63) & ~(size_t)63;
+    std::vector<uint32_t> host((resident ? 0 : 2 * Pa + Sa) + Sa + 1);
+    uint32_t *h_start = host.data();
+    for (size_t i = 0; i < S; ++i) h_start[i] = v.segs[i].seq.start;
+    fgfa_dev::ChopIn in;
+    in.n_steps = N;
+    in.n_paths = (uint32_t)P;
+    in.n_segs = (uint32_t)S;
+    in.n_links = L;
+    uint32_t *d_small = nullptr;
+    CAPI_HIP(dmalloc(host.size() * 4 + (S + 1) * 4, (void **)&d_small));
+    uint32_t *d_seg_first = d_small + host.size();
+    in.seq_start = d_small;
+    if (resident) {
+        in.steps = gfa->d_steps;
+        in.path_begin = gfa->d_path_begin;
+        in.path_end = gfa->d_path_end;
+        in.seg_len = gfa->d_seg_len;
+    } else {
+        uint32_t *h_pb = host.data() + Sa, *h_pe = h_pb + Pa, *h_len = h_pe + Pa;
+        for (size_t i = 0; i < P; ++i) {
+            h_pb[i] = v.paths[i].steps.start;
+            h_pe[i] = v.paths[i].steps.end;
+        }
+        for (size_t i = 0; i < S; ++i) h_len[i] = v.segs[i].seq.len();
+        in.path_begin = d_small + Sa;
+        in.path_end = in.path_begin + Pa;
+        in.seg_len = in.path_end + Pa;
+        uint32_t *d_steps = nullptr;
+        CAPI_HIP(dmalloc(N * 4, (void **)&d_steps));
+        if (N) CAPI_HIP(upload(d_steps, v.steps.data, N * 4, st));
+        in.steps = d_steps;
+    }
+    CAPI_HIP(fgfa_dev::plan_memcpy(d_small, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    if (L) {
+        uint32_t *d_links = nullptr;
+        CAPI_HIP(dmalloc(L * 16, (void **)&d_links));
+        CAPI_HIP(fgfa_dev::plan_memcpy(d_links, v.links.data, L * 16, hipMemcpyHostToDevice));
+        in.links = d_links;
+    }
+    rel.job = fgfa_dev::chop_new();
+    uint64_t S2 = 0, N2 = 0, L2 = 0;
+    int rc = fgfa_dev::chop_count(rel.job, in, max_size, links != 0, d_seg_first, st, &S2, &N2, &L2);
+    if (rc) return rc;
+    // the outputs, now that their sizes are known to fit
+    fgfa_dev::ChopOut o;
+    CAPI_HIP(dmalloc(N2 * 4, (void **)&o.steps));
+    CAPI_HIP(dmalloc(2 * Pa * 4, (void **)&o.path_begin));
+    o.path_end = o.path_begin ? o.path_begin + Pa : nullptr;
+    CAPI_HIP(dmalloc(S2 * 24, (void **)&o.seg_recs));
+    CAPI_HIP(dmalloc(L2 * 16, (void **)&o.links));
+    rc = fgfa_dev::chop_fill(rel.job, o, st);
+    if (rc) return rc;
+    auto cs = std::make_unique<CStore>();
+    fgfa::Store &h = cs->heap;
+    // (the host pools are allocated beside the kernels; the largest, the steps, on a thread of its own)
+    std::thread alloc([&] { h.steps.resize(N2); });
+    struct Joiner {
+        std::thread &t;
+        ~Joiner() { if (t.joinable()) t.join(); }
+    } joiner{alloc};
+    h.header.assign(v.header.begin(), v.header.end());
+    h.seq_data.assign(v.seq_data.begin(), v.seq_data.end());
+    h.name_data.assign(v.name_data.begin(), v.name_data.end());
+    h.segs.resize(S2);
+    h.links.resize(L2);
+    std::vector<uint32_t> spans(2 * Pa);
+    CAPI_HIP(download(h.segs.data(), o.seg_recs, S2 * 24, st));
+    CAPI_HIP(download(h.links.data(), o.links, L2 * 16, st));
+    CAPI_HIP(download(spans.data(), o.path_begin, 2 * Pa * 4, st));
+    alloc.join();
+    CAPI_HIP(download(h.steps.data(), o.steps, N2 * 4, st));
+    h.paths.resize(P);
+    for (size_t i = 0; i < P; ++i) h.paths[i] = fgfa::Path{v.paths[i].name, fgfa::Span{spans[i], spans[Pa + i]}, fgfa::Span{0, 0}};  // chop.rs:104
+    cs->view = h.view();
+    *out = cs.release();
     return FLATGFA_OK;
 }
 

@@ -3,11 +3,12 @@
 //
 //   fgfa [-i FILE.flatgfa | -I FILE.gfa] [-o OUT.flatgfa] [-O OUT.gfa] [COMMAND]
 //   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [-s PATHS]
-//            | window-depth PATH SIZE | overlap --paths FILE | matrix GAF
+//            | window-depth PATH SIZE | overlap --paths FILE | matrix GAF | chop -c N [-l]
 //
 // With no -i/-I the GFA text is read from stdin; with no COMMAND the graph is written out
 // (-o binary, -O text, otherwise text on stdout).  `depth` output is byte-identical to the
-// reference's and is computed on the GPU, as is `matrix` (cmds.rs:453-475).  Everything else in the reference CLI is out of scope.
+// reference's and is computed on the GPU, as are `matrix` (cmds.rs:453-475) and `chop` (cli/main.rs:139-159), whose graph is
+// written out as the input graph would be.  Everything else in the reference CLI is out of scope.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -106,7 +107,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "overlap" || cmd == "matrix";
+    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "overlap" || cmd == "matrix" || cmd == "chop";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -136,7 +137,7 @@ int main(int argc, char **argv) {
         return die("cannot load graph");
     }
 #ifdef MADV_POPULATE_READ
-    if (wants_device && in_flat && cmd != "matrix") {  // (a freshly mapped file: one call instead of a fault per page inside the upload's copies)
+    if (wants_device && in_flat && cmd != "matrix") {  // (chop uploads the steps too)  // (a freshly mapped file: one call instead of a fault per page inside the upload's copies)
         const void *steps = nullptr;
         uint64_t n = 0, es = 0;
         if (flatgfa_pool(g, 4, &steps, &n, &es) == 0 && n) {
@@ -147,23 +148,51 @@ int main(int argc, char **argv) {
 #endif
     if (warm.joinable()) warm.join();
 
+    // dump (cli/main.rs:192-212): -o FILE as .flatgfa, else -O FILE as GFA text, else GFA text on stdout
+    auto dump = [&](flatgfa_t gr) -> int {
+        if (out_flat) return flatgfa_write_flatgfa(gr, out_flat) ? die("write") : 0;
+        char *text = nullptr;
+        size_t n = 0;
+        int r = 0;
+        if (flatgfa_print_gfa(gr, &text, &n)) {
+            r = die("print");
+        } else if (out_gfa) {
+            FILE *f = fopen(out_gfa, "wb");
+            if (!f || fwrite(text, 1, n, f) != n || fclose(f)) { fprintf(stderr, "fgfa: cannot write %s\n", out_gfa); r = 1; }
+        } else {
+            write_all(text, n);
+        }
+        flatgfa_free_text(text);
+        return r;
+    };
+
     int rc = 0;
     if (cmd.empty()) {
-        if (out_flat) {
-            if (flatgfa_write_flatgfa(g, out_flat)) rc = die("write");
-        } else {
-            char *text = nullptr;
-            size_t n = 0;
-            if (flatgfa_print_gfa(g, &text, &n)) {
-                rc = die("print");
-            } else if (out_gfa) {
-                FILE *f = fopen(out_gfa, "wb");
-                if (!f || fwrite(text, 1, n, f) != n || fclose(f)) { fprintf(stderr, "fgfa: cannot write %s\n", out_gfa); rc = 1; }
+        rc = dump(g);
+    } else if (cmd == "chop") {
+        // cli/cmds.rs:286-307: fgfa chop -c N [-l]
+        uint64_t count = 0;
+        bool links = false, bad = false;
+        for (; i < argc; ++i) {
+            std::string a = argv[i];
+            if ((a == "-c" || a == "--count") && i + 1 < argc) {
+                char *end = nullptr;
+                count = strtoull(argv[++i], &end, 10);
+                bad = bad || !*argv[i] || *end;
+            } else if (a == "-l" || a == "--links") {
+                links = true;
             } else {
-                write_all(text, n);
+                bad = true;
             }
-            flatgfa_free_text(text);
         }
+        if (bad || count == 0) {
+            fprintf(stderr, "usage: fgfa chop -c N [-l]   (N >= 1: the maximum segment size)\n");
+            flatgfa_free(g);
+            return 2;
+        }
+        flatgfa_t chopped = nullptr;
+        if (flatgfa_chop(g, count, links ? 1 : 0, &chopped)) rc = die("chop");
+        else rc = dump(chopped);
     } else if (cmd == "toc") {
         bool bytes = i < argc && !strcmp(argv[i], "-b");
         static const char *names[11] = {"header", "segs", "paths", "links", "steps", "seq_data",

@@ -50,6 +50,25 @@ class DeviceGraph:
             self.seg_len = None if seg_len is None else _as_i32(seg_len).to(self.device)
             torch.cuda.synchronize(self.device)
 
+    @classmethod
+    def from_tensors(cls, steps, path_begin, path_end, n_segs: int, seg_len=None,
+                     h_path_begin: Optional[np.ndarray] = None, h_path_end: Optional[np.ndarray] = None) -> "DeviceGraph":
+        """A DeviceGraph over int32 CUDA tensors that are already on the device (kept, not copied).  The host copies of the
+        spans (what a DepthPlan hands the C ABI) are copied back from the device when not given."""
+        torch = _torch()
+        for t in (steps, path_begin, path_end) + (() if seg_len is None else (seg_len,)):
+            assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.device == steps.device
+        assert path_begin.numel() == path_end.numel() and (seg_len is None or seg_len.numel() == n_segs)
+        g = cls.__new__(cls)
+        g.device = steps.device
+        g.n_steps, g.n_paths, g.n_segs = int(steps.numel()), int(path_begin.numel()), int(n_segs)
+        g.steps, g.path_begin, g.path_end, g.seg_len = steps, path_begin, path_end, seg_len
+        g.h_path_begin = (np.ascontiguousarray(h_path_begin, dtype=np.uint32) if h_path_begin is not None
+                          else path_begin.cpu().numpy().view(np.uint32).copy())
+        g.h_path_end = (np.ascontiguousarray(h_path_end, dtype=np.uint32) if h_path_end is not None
+                        else path_end.cpu().numpy().view(np.uint32).copy())
+        return g
+
     def c_struct(self) -> _lib.flatgfa_dev_graph_t:
         return _lib.flatgfa_dev_graph_t(
             self.steps.data_ptr() if self.n_steps else None, self.n_steps,
@@ -297,6 +316,38 @@ def pangenotype_row(gfa, text, row, first_bad, stream=None) -> None:
         n = int(text.numel())
         _check(_lib.lib().flatgfa_dev_pangenotype_row(gfa._h, text.data_ptr() if n else None, n, row.data_ptr() if row.numel() else None,
                                                       first_bad.data_ptr(), ctypes.c_void_p(st.cuda_stream)), "dev_pangenotype_row")
+
+
+def chop(graph: DeviceGraph, max_size: int, stream=None) -> Tuple[DeviceGraph, object]:
+    """chop (flatgfa/src/ops/chop.rs, without links) of a resident graph image, on the device: returns the chopped image
+    as a new DeviceGraph (int32 tensors on the same device; a valid input to DepthPlan) and seg_first (int32[n_segs + 1]:
+    old segment s became the new segments [seg_first[s], seg_first[s + 1])).  Needs graph.seg_len.  Waits for the stream
+    once, to learn the sizes (flatgfa_dev_chop_count); the rest is enqueued on it (torch's current stream by default)."""
+    torch = _torch()
+    if graph.seg_len is None:
+        raise FlatGFAError("chop: the graph has no seg_len", -1)
+    with torch.cuda.device(graph.device):
+        st = stream if stream is not None else torch.cuda.current_stream(graph.device)
+        g = graph.c_struct()
+        seg_first = torch.empty(graph.n_segs + 1, dtype=torch.int32, device=graph.device)
+        job = ctypes.c_void_p()
+        n_segs, n_steps = ctypes.c_uint64(), ctypes.c_uint64()
+        L = _lib.lib()
+        _check(L.flatgfa_dev_chop_count(ctypes.byref(g), int(max_size), seg_first.data_ptr(), ctypes.c_void_p(st.cuda_stream),
+                                        ctypes.byref(job), ctypes.byref(n_segs), ctypes.byref(n_steps)), "dev_chop_count")
+        try:
+            steps = torch.empty(n_steps.value, dtype=torch.int32, device=graph.device)
+            pb = torch.empty(graph.n_paths, dtype=torch.int32, device=graph.device)
+            pe = torch.empty(graph.n_paths, dtype=torch.int32, device=graph.device)
+            seg_len = torch.empty(n_segs.value, dtype=torch.int32, device=graph.device)
+
+            def ptr(t):
+                return t.data_ptr() if t.numel() else None
+            _check(L.flatgfa_dev_chop_fill(job, ptr(steps), ptr(pb), ptr(pe), ptr(seg_len), ctypes.c_void_p(st.cuda_stream)),
+                   "dev_chop_fill")
+        finally:
+            L.flatgfa_dev_chop_free(job)  # (waits for the fill)
+        return DeviceGraph.from_tensors(steps, pb, pe, n_segs.value, seg_len), seg_first
 
 
 def profile_enable(on: bool) -> None:

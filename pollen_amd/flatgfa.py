@@ -361,6 +361,14 @@ class FlatGFA:
             _lib.lib().flatgfa_pangenotype_table(self._h, ptrs, lens, k, ctypes.byref(p), ctypes.byref(n)), "pangenotype_table"))
         return _take_text(p, n)
 
+    # ---- chop (ops/chop.rs) ----
+    def chop(self, max_size: int, links: bool = False) -> "FlatGFA":
+        """`fgfa chop -c max_size [-l]`: a new graph whose segments are at most max_size long (flatgfa/src/ops/chop.rs),
+        computed on the GPU.  The result owns its pools and outlives this graph."""
+        h = ctypes.c_void_p()
+        _check(_lib.lib().flatgfa_chop(self._h, int(max_size), 1 if links else 0, ctypes.byref(h)), "chop")
+        return FlatGFA(h.value)
+
 
 SHARD_WHOLE_PATHS = 1  # FLATGFA_SHARD_WHOLE_PATHS
 SHARD_NO_RCCL = 2      # FLATGFA_SHARD_NO_RCCL
