@@ -416,9 +416,11 @@ __global__ __launch_bounds__(kThreads) void k_expand_paths(const uint32_t *__res
             pbase[threadIdx.x] = base;
             const uint32_t m = (uint32_t)min<uint64_t>(kTile, e - cb);
             __syncthreads();
-            for (uint32_t ob = 0; ob < tot; ob += kOutTile) {
-                const uint32_t j = ob + threadIdx.x * kItems;
-                if (j < tot) {
+            // 64-bit: tot reaches 2^32 - 1, and a u32 ob would wrap from 2^32 - kOutTile to 0 and never end
+            for (uint64_t ob = 0; ob < tot; ob += kOutTile) {
+                const uint64_t j64 = ob + threadIdx.x * kItems;
+                if (j64 < tot) {
+                    const uint32_t j = (uint32_t)j64;
                     uint32_t lo = 0, hi = m;
                     while (hi - lo > 1) {
                         const uint32_t mid = (lo + hi) >> 1;
@@ -426,7 +428,7 @@ __global__ __launch_bounds__(kThreads) void k_expand_paths(const uint32_t *__res
                         else hi = mid;
                     }
                     uint32_t e2 = lo;
-                    for (uint32_t q = 0; q < kItems && j + q < tot; ++q) {
+                    for (uint32_t q = 0; q < kItems && j64 + q < tot; ++q) {
                         const uint32_t jj = j + q;
                         while (e2 + 1 < m && off[e2 + 1] <= jj) ++e2;
                         const uint32_t next = e2 + 1 < m ? off[e2 + 1] : tot;
