@@ -24,6 +24,7 @@
 #include "../../include/flatgfa.h"
 #include "device_common.hpp"
 #include "temp_arena.hpp"
+#include "host_copy.hpp"
 #include "flatgfa_core.hpp"
 #include "gaf_device.hpp"
 #include "chop_device.hpp"
@@ -362,126 +363,6 @@ int flatgfa_format_float(double x, int digits, char *out, int cap) {
 
 // ---- device residency ----
 
-// The pinned staging buffers are the process's own, made on first use and kept: allocating and
-// freeing eight of them per upload cost 2.9 + 3.8 ms of the 17 ms a cfg-L graph took to become
-// resident (FLATGFA_TIMING).  One upload at a time uses them.
-namespace {
-constexpr size_t kChunk = 8u << 20;
-constexpr int kMaxUploadThreads = 16;
-struct StagePool {
-    std::mutex mu;  // held for the whole of an upload
-    char *stage[2 * kMaxUploadThreads] = {};
-    hipEvent_t ev[2 * kMaxUploadThreads] = {};
-    int device = -1;
-    void release() {
-        for (int i = 0; i < 2 * kMaxUploadThreads; ++i) {
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-            if (stage[i]) (void)hipHostFree(stage[i]);
-            ev[i] = nullptr;
-            stage[i] = nullptr;
-        }
-        device = -1;
-    }
-    hipError_t ensure(int dev, int n) {
-        if (device != dev) release();  // (events belong to a device)
-        device = dev;
-        for (int i = 0; i < n; ++i) {
-            if (!stage[i]) {
-                const hipError_t rc = hipHostMalloc((void **)&stage[i], kChunk, hipHostMallocDefault);
-                if (rc != hipSuccess) { stage[i] = nullptr; return rc; }
-            }
-            if (!ev[i]) {
-                const hipError_t rc = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
-                if (rc != hipSuccess) { ev[i] = nullptr; return rc; }
-            }
-        }
-        return hipSuccess;
-    }
-};
-StagePool *stage_pool() {
-    static StagePool *p = new StagePool();  // never destroyed: the HIP runtime may be gone by the time static destructors run
-    return p;
-}
-}  // namespace
-
-// Host -> device copy of a large pageable (or file-mapped) region.  A plain hipMemcpy stages it
-// through the runtime's own pinned buffer on one thread (10-24 GB/s here, less when the source
-// is a mapped file that still has to be faulted in); a few threads copying 8 MB chunks into
-// pinned buffers and queueing async copies reach the PCIe rate (~49 GB/s measured with four,
-// tools/h2d_test.hip; a freshly mapped file adds ~17 ms of first-touch page faults per 400 MB,
-// which pread() into the pinned buffers does not beat).  Small regions take the plain route.
-static hipError_t upload(void *dst, const void *src, size_t bytes, hipStream_t stream) {
-    static const int kThreads = [] {
-        const char *e = getenv("FLATGFA_UPLOAD_THREADS");
-        const int n = e ? atoi(e) : 4;
-        return n < 1 ? 1 : n > kMaxUploadThreads ? kMaxUploadThreads : n;
-    }();
-    const bool timing = getenv("FLATGFA_TIMING") != nullptr;
-    auto tick = [t = std::chrono::steady_clock::now(), timing](const char *what) mutable {
-        if (!timing) return;
-        const auto n = std::chrono::steady_clock::now();
-        fprintf(stderr, "upload: %-31s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count());
-        t = n;
-    };
-    if (bytes < 4 * kChunk) return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
-    int device = 0;
-    hipError_t rc = hipGetDevice(&device);
-    if (rc != hipSuccess) return rc;
-    StagePool &pool = *stage_pool();
-    std::lock_guard<std::mutex> lk(pool.mu);
-    rc = pool.ensure(device, 2 * kThreads);
-    char **stage = pool.stage;
-    hipEvent_t *ev = pool.ev;
-    std::atomic<int> failed{(int)rc};
-    tick("pinned buffers + events");
-    if (rc == hipSuccess) {
-        const size_t n_chunks = (bytes + kChunk - 1) / kChunk;
-        std::vector<std::thread> workers;
-        for (int t = 0; t < kThreads; ++t)
-            workers.emplace_back([&, t]() {
-                const auto w0 = std::chrono::steady_clock::now();
-                const auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count(); };
-                if (hipSetDevice(device) != hipSuccess) { failed = (int)hipErrorInvalidDevice; return; }
-                const double t_dev = since();
-                const auto populate = [&](size_t off, size_t len) {
-#ifdef MADV_POPULATE_READ
-                    // a freshly mapped file: let the kernel map the chunk's pages in one go instead of taking a fault per
-                    // page inside the memcpy (on anonymous memory it only maps what the copy would touch anyway)
-                    static const uintptr_t page = (uintptr_t)sysconf(_SC_PAGESIZE);
-                    const uintptr_t a0 = ((uintptr_t)src + off) & ~(page - 1);
-                    (void)madvise((void *)a0, ((uintptr_t)src + off + len) - a0, MADV_POPULATE_READ);
-#else
-                    (void)off, (void)len;
-#endif
-                };
-                int round = 0;
-                for (size_t c = (size_t)t; c < n_chunks && !failed; c += kThreads, ++round) {
-                    const int b = 2 * t + (round & 1);
-                    const double t_w = since();
-                    hipError_t e = round >= 2 ? hipEventSynchronize(ev[b]) : hipSuccess;  // the buffer's previous copy is done
-                    const size_t off = c * kChunk, len = std::min(kChunk, bytes - off);
-                    const double t_a = since();
-                    if (e == hipSuccess) {
-                        populate(off, len);
-                        memcpy(stage[b], (const char *)src + off, len);
-                        const double t_b = since();
-                        e = hipMemcpyAsync((char *)dst + off, stage[b], len, hipMemcpyHostToDevice, stream);
-                        if (timing && t == 0 && round < 3)
-                            fprintf(stderr, "upload: worker 0 chunk %2d at %6.2f ms (set device %.2f): waited %.2f, fault + stage %.2f, queue %.2f ms\n", round, t_w, t_dev, t_a - t_w, t_b - t_a, since() - t_b);
-                    }
-                    if (e == hipSuccess) e = hipEventRecord(ev[b], stream);
-                    if (e != hipSuccess) failed = (int)e;
-                }
-            });
-        for (auto &w : workers) w.join();
-        tick("workers: fault in, stage, queue");
-        const hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess && !failed) failed = (int)e;
-        tick("copies drained");
-    }
-    return (hipError_t)failed.load();
-}
-
 int flatgfa_keep_host_memory(int on) {
 #ifdef __GLIBC__
     // (never map: large blocks come from the heap and go back to its free lists; never trim: the heap's top stays)
@@ -501,21 +382,15 @@ int flatgfa_warm_device(int device) {
     }
     if (device < 0 || device >= ndev) { set_error("device index out of range"); return FLATGFA_ERR_ARG; }
     CAPI_HIP(hipSetDevice(device));
-    {   // the staging buffers an upload will want (kept by the process)
-        static const int kThreads = [] {
-            const char *e = getenv("FLATGFA_UPLOAD_THREADS");
-            const int n = e ? atoi(e) : 4;
-            return n < 1 ? 1 : n > kMaxUploadThreads ? kMaxUploadThreads : n;
-        }();
-        StagePool &pool = *stage_pool();
-        std::lock_guard<std::mutex> lk(pool.mu);
-        CAPI_HIP(pool.ensure(device, 2 * kThreads));
-        // the process's first asynchronous copy and first launch (queues, the library's code object)
+    CAPI_HIP(fgfa_dev::warm_staging(device));  // (the staging buffers and this device's events, kept by the process)
+    {   // the process's first asynchronous copy and first launch (queues, the library's code object)
+        char *pinned = nullptr;
+        const auto lk = fgfa_dev::borrow_staging(&pinned);
         uint32_t *d = nullptr;
         hipStream_t s = nullptr;
         CAPI_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         hipError_t e = hipMalloc(&d, 4096);
-        if (e == hipSuccess) e = hipMemcpyAsync(d, pool.stage[0], 4096, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d, pinned, 4096, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) {
             fgfa_dev::warm_launch(s);  // (loads the library's code object)
             e = hipStreamSynchronize(s);
@@ -606,14 +481,14 @@ static int ensure_device(CStore *cs, int device) {
     if (N) {
         CAPI_HIP(hipMalloc(&im.steps, N * 4));
         tick("steps: hipMalloc");
-        CAPI_HIP(upload(im.steps, v.steps.data, N * 4, im.stream));
+        CAPI_HIP(fgfa_dev::staged_copy(im.steps, v.steps.data, N * 4, hipMemcpyHostToDevice, im.stream));
     }
     tick("steps: upload");
     soa.join();
     tick("span arrays on the host (beside the upload)");
     if (P || S) {
         CAPI_HIP(hipMalloc(&im.small, (2 * Pa + 3 * Sa + 4 * Pa) * 4));  // (the last 4 * Pa words: two u64 sums per path)
-        CAPI_HIP(fgfa_dev::plan_memcpy(im.small, host.data(), host.size() * 4, hipMemcpyHostToDevice));  // (through pinned staging, like the steps: pages the runtime pins for a copy cost the next dispatch when the host drops them, NOTES R6.6c)
+        CAPI_HIP(fgfa_dev::staged_copy(im.small, host.data(), host.size() * 4, hipMemcpyHostToDevice, nullptr));
         im.pb = im.small;
         im.pe = im.small + Pa;
         im.seg_len = im.small + 2 * Pa;
@@ -695,16 +570,15 @@ extern "C++" {
 template <class F>
 static int with_both_u32(CStore *gfa, F use) {
     const size_t S = gfa->view.segs.len, gap = (size_t)(gfa->d_uniq - gfa->d_depth);
-    if ((gap + S) * 4 <= kChunk) {
-        StagePool &pool = *stage_pool();
-        std::lock_guard<std::mutex> lk(pool.mu);
-        if (pool.ensure(gfa->device, 1) == hipSuccess) {
-            CAPI_HIP(hipMemcpyAsync(pool.stage[0], gfa->d_depth, (gap + S) * 4, hipMemcpyDeviceToHost, gfa->stream));
+    if ((gap + S) * 4 <= fgfa_dev::kStagingBytes) {
+        char *pinned = nullptr;
+        const auto lk = fgfa_dev::borrow_staging(&pinned);
+        if (pinned) {
+            CAPI_HIP(hipMemcpyAsync(pinned, gfa->d_depth, (gap + S) * 4, hipMemcpyDeviceToHost, gfa->stream));
             CAPI_HIP(hipStreamSynchronize(gfa->stream));
-            const uint32_t *src = reinterpret_cast<const uint32_t *>(pool.stage[0]);
+            const uint32_t *src = reinterpret_cast<const uint32_t *>(pinned);
             return use(src, src + gap);
         }
-        (void)hipGetLastError();
     }
     std::unique_ptr<uint32_t[]> tmp(new uint32_t[gap + S]);
     CAPI_HIP(hipMemcpy(tmp.get(), gfa->d_depth, (gap + S) * 4, hipMemcpyDeviceToHost));
@@ -1022,13 +896,6 @@ static int gaf_bad_line(uint32_t file, uint64_t offset) {
     return FLATGFA_ERR_BOUNDS;
 }
 
-// A copy of host bytes to the device, synchronous: large ones as the step pool's upload does (threads staging into the pinned
-// buffers), the rest through plan_memcpy (pinned staging from 4 MB up).
-static hipError_t gaf_copy(void *dst, const void *src, size_t bytes, hipStream_t stream) {
-    if (bytes >= 4 * kChunk) return upload(dst, src, bytes, stream);
-    return fgfa_dev::plan_memcpy(dst, src, bytes, hipMemcpyHostToDevice);
-}
-
 int flatgfa_pangenotype_matrix(flatgfa_t gfa, const uint8_t *const *gaf, const size_t *gaf_len, uint32_t n_files,
                                uint64_t *bits_out) {
     if (!gfa || (n_files && (!gaf || !gaf_len || !bits_out))) { set_error("flatgfa_pangenotype_matrix: NULL argument"); return FLATGFA_ERR_ARG; }
@@ -1116,7 +983,7 @@ int flatgfa_pangenotype_matrix(flatgfa_t gfa, const uint8_t *const *gaf, const s
             const int b = (int)(k & 1);
             if (used[b]) CAPI_HIP(hipEventSynchronize(done[b]));  // the scan that read this buffer is over
             const size_t len = pieces[k].end - pieces[k].begin;
-            CAPI_HIP(gaf_copy(d_text[b], gaf[f] + pieces[k].begin, len, cs));  // (beside the scan of the piece before, on ks)
+            CAPI_HIP(fgfa_dev::staged_copy(d_text[b], gaf[f] + pieces[k].begin, len, hipMemcpyHostToDevice, cs));  // (beside the scan of the piece before, on ks)
             CAPI_HIP(fgfa_dev::gaf_scan(d_text[b], len, gfa->gaf_names, d_row, d_bad, pieces[k].begin, d_scratch[b], ks));
             CAPI_HIP(hipEventRecord(done[b], ks));
             used[b] = true;
@@ -1189,58 +1056,6 @@ int flatgfa_dev_pangenotype_row(flatgfa_t gfa, const uint8_t *d_text, size_t len
 }
 
 // ---- chop (ops/chop.rs) ----
-
-// Device -> host copy of a large region through the process's pinned staging: the copy engine fills 8 MB chunks of the
-// pinned buffers while host threads move the chunks before them out to `dst` (a pageable hipMemcpy stages through one
-// buffer of the runtime's on one thread).  Waits for `stream`, on which the copies queue behind whatever wrote `src`.
-static hipError_t download(void *dst, const void *src, size_t bytes, hipStream_t stream) {
-    if (bytes < 4 * kChunk) {
-        const hipError_t e = bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
-        return e != hipSuccess ? e : hipStreamSynchronize(stream);
-    }
-    constexpr int kWorkers = 4, kBufs = 2 * kWorkers;
-    int device = 0;
-    hipError_t rc = hipGetDevice(&device);
-    if (rc != hipSuccess) return rc;
-    StagePool &pool = *stage_pool();
-    std::lock_guard<std::mutex> lk(pool.mu);
-    rc = pool.ensure(device, kBufs);
-    if (rc != hipSuccess) return rc;
-    const int64_t n_chunks = (int64_t)((bytes + kChunk - 1) / kChunk);
-    std::atomic<int64_t> enqueued{-1};
-    std::atomic<int64_t> copied[kBufs];
-    for (auto &c : copied) c = -1;
-    std::atomic<int> failed{0};
-    std::vector<std::thread> workers;
-    for (int t = 0; t < kWorkers; ++t)
-        workers.emplace_back([&, t]() {
-            if (hipSetDevice(device) != hipSuccess) { failed = (int)hipErrorInvalidDevice; return; }
-            for (int64_t c = t; c < n_chunks; c += kWorkers) {
-                while (enqueued.load(std::memory_order_acquire) < c)
-                    if (failed) return;
-                    else std::this_thread::yield();
-                const int b = (int)(c % kBufs);
-                const hipError_t e = hipEventSynchronize(pool.ev[b]);
-                if (e != hipSuccess) { failed = (int)e; return; }
-                const size_t off = (size_t)c * kChunk;
-                memcpy((char *)dst + off, pool.stage[b], std::min(kChunk, bytes - off));
-                copied[b].store(c, std::memory_order_release);
-            }
-        });
-    for (int64_t c = 0; c < n_chunks && !failed; ++c) {
-        const int b = (int)(c % kBufs);
-        while (c >= kBufs && copied[b].load(std::memory_order_acquire) < c - kBufs && !failed) std::this_thread::yield();
-        if (failed) break;
-        const size_t off = (size_t)c * kChunk;
-        hipError_t e = hipMemcpyAsync(pool.stage[b], (const char *)src + off, std::min(kChunk, bytes - off), hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipEventRecord(pool.ev[b], stream);
-        if (e != hipSuccess) { failed = (int)e; break; }
-        enqueued.store(c, std::memory_order_release);
-    }
-    for (auto &w : workers) w.join();
-    const hipError_t e = hipStreamSynchronize(stream);
-    return failed ? (hipError_t)failed.load() : e;
-}
 
 int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
     if (out) *out = nullptr;
@@ -1318,14 +1133,14 @@ int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
         in.seg_len = in.path_end + Pa;
         uint32_t *d_steps = nullptr;
         CAPI_HIP(dmalloc(N * 4, (void **)&d_steps));
-        if (N) CAPI_HIP(upload(d_steps, v.steps.data, N * 4, st));
+        CAPI_HIP(fgfa_dev::staged_copy(d_steps, v.steps.data, N * 4, hipMemcpyHostToDevice, st));
         in.steps = d_steps;
     }
-    CAPI_HIP(fgfa_dev::plan_memcpy(d_small, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    CAPI_HIP(fgfa_dev::staged_copy(d_small, host.data(), host.size() * 4, hipMemcpyHostToDevice, nullptr));
     if (L) {
         uint32_t *d_links = nullptr;
         CAPI_HIP(dmalloc(L * 16, (void **)&d_links));
-        CAPI_HIP(fgfa_dev::plan_memcpy(d_links, v.links.data, L * 16, hipMemcpyHostToDevice));
+        CAPI_HIP(fgfa_dev::staged_copy(d_links, v.links.data, L * 16, hipMemcpyHostToDevice, nullptr));
         in.links = d_links;
     }
     rel.job = fgfa_dev::chop_new();
@@ -1355,11 +1170,11 @@ int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
     h.segs.resize(S2);
     h.links.resize(L2);
     std::vector<uint32_t> spans(2 * Pa);
-    CAPI_HIP(download(h.segs.data(), o.seg_recs, S2 * 24, st));
-    CAPI_HIP(download(h.links.data(), o.links, L2 * 16, st));
-    CAPI_HIP(download(spans.data(), o.path_begin, 2 * Pa * 4, st));
+    CAPI_HIP(fgfa_dev::staged_copy(h.segs.data(), o.seg_recs, S2 * 24, hipMemcpyDeviceToHost, st));
+    CAPI_HIP(fgfa_dev::staged_copy(h.links.data(), o.links, L2 * 16, hipMemcpyDeviceToHost, st));
+    CAPI_HIP(fgfa_dev::staged_copy(spans.data(), o.path_begin, 2 * Pa * 4, hipMemcpyDeviceToHost, st));
     alloc.join();
-    CAPI_HIP(download(h.steps.data(), o.steps, N2 * 4, st));
+    CAPI_HIP(fgfa_dev::staged_copy(h.steps.data(), o.steps, N2 * 4, hipMemcpyDeviceToHost, st));
     h.paths.resize(P);
     for (size_t i = 0; i < P; ++i) h.paths[i] = fgfa::Path{v.paths[i].name, fgfa::Span{spans[i], spans[Pa + i]}, fgfa::Span{0, 0}};  // chop.rs:104
     cs->view = h.view();

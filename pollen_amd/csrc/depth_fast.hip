@@ -54,6 +54,7 @@
 
 #include "depth_fast_kernels.hpp"
 #include "temp_arena.hpp"
+#include "host_copy.hpp"
 #include "prof.hpp"
 
 namespace fgfa_dev {
@@ -547,7 +548,7 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
         Vec<uint32_t> spans(2 * np);
         std::copy(hb, hb + np, spans.begin());
         std::copy(he, he + np, spans.begin() + (ptrdiff_t)np);
-        hipError_t e = plan_memcpy(d_runs + n_out * np, spans.data(), np * 8, hipMemcpyHostToDevice);
+        hipError_t e = staged_copy(d_runs + n_out * np, spans.data(), np * 8, hipMemcpyHostToDevice, nullptr);
         if (e != hipSuccess) {
             (void)hipFree(d_runs);
             FAST_TRY(e);
@@ -567,7 +568,7 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
                            d_runs + n_out * np, d_runs + (n_out + 1) * np, g.n_paths, g.n_steps, d_runs, d_runs + np, d_runs + 2 * np,
                            want_ext ? d_runs + 3 * np : nullptr);
         Vec<uint32_t> out(n_out * np);
-        e = plan_memcpy(out.data(), d_runs, n_out * np * 4, hipMemcpyDeviceToHost);
+        e = staged_copy(out.data(), d_runs, n_out * np * 4, hipMemcpyDeviceToHost, nullptr);
         (void)hipFree(d_runs);
         FAST_TRY(e);
         runs.assign(out.begin(), out.begin() + (ptrdiff_t)np);
@@ -633,11 +634,11 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
         for (size_t i = 0; i < whole.size(); ++i) at[i] = whole[i].x;
         uint32_t *d_at = nullptr;
         FAST_TRY(hipMalloc(&d_at, whole.size() * 8));
-        hipError_t e = plan_memcpy(d_at, at.data(), whole.size() * 4, hipMemcpyHostToDevice);
+        hipError_t e = staged_copy(d_at, at.data(), whole.size() * 4, hipMemcpyHostToDevice, nullptr);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_first_ids, dim3((uint32_t)((whole.size() + 255) / 256)), dim3(256), 0, nullptr, g.steps, d_at, (uint32_t)whole.size(),
                                d_at + whole.size());
-            e = plan_memcpy(first.data(), d_at + whole.size(), whole.size() * 4, hipMemcpyDeviceToHost);
+            e = staged_copy(first.data(), d_at + whole.size(), whole.size() * 4, hipMemcpyDeviceToHost, nullptr);
         }
         (void)hipFree(d_at);
         FAST_TRY(e);
@@ -656,7 +657,7 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
         FAST_TRY(hipMemset(fp->rev_steps, 0, (size_t)fp->n_rev_steps * 4));
         uint4 *d_list = nullptr;
         FAST_TRY(hipMalloc(&d_list, rev_list.size() * sizeof(uint4)));
-        hipError_t e = plan_memcpy(d_list, rev_list.data(), rev_list.size() * sizeof(uint4), hipMemcpyHostToDevice);
+        hipError_t e = staged_copy(d_list, rev_list.data(), rev_list.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_reverse_copy, dim3(std::min<uint32_t>((uint32_t)rev_list.size(), fp->n_cus * 8u)), dim3(256), 0, nullptr,
                                g.steps, d_list, (uint32_t)rev_list.size(), fp->rev_steps);
@@ -929,7 +930,7 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
         std::copy(elist.begin(), elist.end(), slab.begin() + (ptrdiff_t)o_elist);
         std::copy(wave_off.begin(), wave_off.end(), slab.begin() + (ptrdiff_t)o_wave_off);
         FAST_TRY(hipMalloc(&fp->lists_slab, total_words * 4));
-        FAST_TRY(plan_memcpy(fp->lists_slab, slab.data(), total_words * 4, hipMemcpyHostToDevice));
+        FAST_TRY(staged_copy(fp->lists_slab, slab.data(), total_words * 4, hipMemcpyHostToDevice, nullptr));
         fp->fat_off = fp->lists_slab + o_fat_off;
         fp->fat_woff = fp->lists_slab + o_fat_woff;
         fp->perm = fp->lists_slab + o_perm;
@@ -1016,7 +1017,7 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
         }
     }
     if (!items.empty()) {
-        FAST_TRY(plan_memcpy(fp->items, items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        FAST_TRY(staged_copy(fp->items, items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr));
         if (!measure_switch("FLATGFA_NO_ITEM_DIRS")) {  // (measurement builds: every item taken as running upwards)
             unsigned long long *d_runs64 = nullptr, runs64 = 0, item_steps = 0, counted[2] = {0, 0};
             // (FLATGFA_NO_CLAIM=0: every item claims, monotone or not -- tests and measurements)
@@ -1034,7 +1035,7 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
             if (fp->n_shared && no_claim) FAST_TRY(hipMalloc(&d_mono, (size_t)fp->n_items * sizeof(uint4)));
             hipLaunchKernelGGL(k_item_dirs, dim3(std::min<uint32_t>(fp->n_items, fp->n_cus * 8u)), dim3(256), 0, nullptr, g.steps,
                                reinterpret_cast<uint4 *>(fp->items), fp->n_items, d_runs64, d_mono);
-            hipError_t e = plan_memcpy(counted, d_runs64, 16, hipMemcpyDeviceToHost);
+            hipError_t e = staged_copy(counted, d_runs64, 16, hipMemcpyDeviceToHost, nullptr);
             runs64 = counted[0];
             (void)hipFree(d_runs64);
             // The pieces of a split path: the path never meets a segment twice when every piece runs strictly one way,
@@ -1042,14 +1043,14 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
             Vec<uint4> dev_items;
             if (e == hipSuccess && (d_mono || !no_claim)) {
                 dev_items.resize(items.size());
-                e = plan_memcpy(dev_items.data(), fp->items, items.size() * sizeof(uint4), hipMemcpyDeviceToHost);
+                e = staged_copy(dev_items.data(), fp->items, items.size() * sizeof(uint4), hipMemcpyDeviceToHost, nullptr);
             }
             if (e == hipSuccess && !no_claim) {
                 for (uint4 &it : dev_items) it.z &= ~kItemNoClaim;
-                e = plan_memcpy(fp->items, dev_items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice);
+                e = staged_copy(fp->items, dev_items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr);
             } else if (e == hipSuccess && d_mono) {
                 Vec<uint4> mono(items.size());
-                e = plan_memcpy(mono.data(), d_mono, items.size() * sizeof(uint4), hipMemcpyDeviceToHost);
+                e = staged_copy(mono.data(), d_mono, items.size() * sizeof(uint4), hipMemcpyDeviceToHost, nullptr);
                 if (e == hipSuccess) {
                     Vec<Vec<uint32_t>> pieces(fp->n_shared);
                     for (uint32_t j = 0; j < fp->n_items; ++j) {
@@ -1072,7 +1073,7 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
                             any = true;
                         }
                     }
-                    if (any) e = plan_memcpy(fp->items, dev_items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice);
+                    if (any) e = staged_copy(fp->items, dev_items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr);
                 }
             }
             if (d_mono) (void)hipFree(d_mono);
@@ -1080,7 +1081,7 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
             if (no_claim) {  // how many there are (flatgfa_dev_plan_describe: no_claim_items)
                 if (dev_items.empty()) {
                     dev_items.resize(items.size());
-                    FAST_TRY(plan_memcpy(dev_items.data(), fp->items, items.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+                    FAST_TRY(staged_copy(dev_items.data(), fp->items, items.size() * sizeof(uint4), hipMemcpyDeviceToHost, nullptr));
                 }
                 for (const uint4 &it : dev_items) fp->n_noclaim += it.z >> 31;
             }
@@ -1120,15 +1121,15 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
     }
     if (!short_items.empty()) {
         FAST_TRY(hipMalloc(&fp->short_items, short_items.size() * sizeof(uint4)));
-        FAST_TRY(plan_memcpy(fp->short_items, short_items.data(), short_items.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        FAST_TRY(staged_copy(fp->short_items, short_items.data(), short_items.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr));
     }
     if (!medium_items.empty()) {
         FAST_TRY(hipMalloc(&fp->medium_items, medium_items.size() * sizeof(uint4)));
-        FAST_TRY(plan_memcpy(fp->medium_items, medium_items.data(), medium_items.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        FAST_TRY(staged_copy(fp->medium_items, medium_items.data(), medium_items.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr));
     }
     if (!tiny_items.empty()) {
         FAST_TRY(hipMalloc(&fp->tiny_items, tiny_items.size() * sizeof(uint4)));
-        FAST_TRY(plan_memcpy(fp->tiny_items, tiny_items.data(), tiny_items.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        FAST_TRY(staged_copy(fp->tiny_items, tiny_items.data(), tiny_items.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr));
     }
     {
         Vec<uint32_t> other;
@@ -1138,7 +1139,7 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
         fp->n_other = (uint32_t)other.size();
         if (!other.empty()) {
             FAST_TRY(hipMalloc(&fp->other_ids, other.size() * 4));
-            FAST_TRY(plan_memcpy(fp->other_ids, other.data(), other.size() * 4, hipMemcpyHostToDevice));
+            FAST_TRY(staged_copy(fp->other_ids, other.data(), other.size() * 4, hipMemcpyHostToDevice, nullptr));
         }
     }
     // (the attribute belongs to the kernel, not to the plan: set once per device by the translation unit that holds it)
@@ -1207,10 +1208,10 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
         const int rc = run_range(*fp, g, nullptr, nullptr, d_status, nullptr, nullptr, true);
         Vec<uint32_t> cnt(slots);
         hipError_t e = rc == FLATGFA_OK ? hipDeviceSynchronize() : hipErrorUnknown;
-        if (e == hipSuccess) e = plan_memcpy(cnt.data(), fp->counts, slots * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = staged_copy(cnt.data(), fp->counts, slots * 4, hipMemcpyDeviceToHost, nullptr);
         if (e == hipSuccess) e = hipMemset(fp->counts, 0, slots * 4);
         uint32_t st = 0;
-        if (e == hipSuccess) e = plan_memcpy(&st, d_status, 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = staged_copy(&st, d_status, 4, hipMemcpyDeviceToHost, nullptr);
         (void)hipFree(d_status);
         fp->eligible = false;
         FAST_TRY(e);
@@ -1264,10 +1265,10 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
             fp->bucket_records = (slots + fp->n_slots) * (uint64_t)fp->cap;
         } else {
             FAST_TRY(hipMalloc(&fp->buckets, std::max<uint64_t>(total, 64) * 4));
-            FAST_TRY(plan_memcpy(fp->pk_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-            FAST_TRY(plan_memcpy(fp->pk_base, base.data(), base.size() * 8, hipMemcpyHostToDevice));
+            FAST_TRY(staged_copy(fp->pk_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, nullptr));
+            FAST_TRY(staged_copy(fp->pk_base, base.data(), base.size() * 8, hipMemcpyHostToDevice, nullptr));
             FAST_TRY(hipMalloc(&fp->pk, slots * sizeof(uint2)));
-            FAST_TRY(plan_memcpy(fp->pk, pk.data(), slots * sizeof(uint2), hipMemcpyHostToDevice));
+            FAST_TRY(staged_copy(fp->pk, pk.data(), slots * sizeof(uint2), hipMemcpyHostToDevice, nullptr));
             fp->cap = (uint32_t)std::max<uint64_t>(deepest, 4);  // (what describe() reports: the deepest sub-bucket)
             fp->bucket_records = total;
         }
@@ -1571,7 +1572,7 @@ void fast_marks_finish(FastPlan *fp, MarksJob *job) {
     if (!job->active) return;
     unsigned long long cnt[4] = {0, 0, 0, 0};
     hipError_t e = hipEventSynchronize(job->done);
-    if (e == hipSuccess) e = plan_memcpy(cnt, job->cnt, 32, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = staged_copy(cnt, job->cnt, 32, hipMemcpyDeviceToHost, nullptr);
     const unsigned long long flagged = cnt[2];
     // (worth it from half of the chunks: pass 2's build with the no-claim test costs the claiming records 4 %, k_scan's with the
     // marks 1-10 % (short items most), and the claims are two fifths of pass 2 -- contigs of ten blocks with a third of
@@ -1713,7 +1714,7 @@ bool fast_plan_grow(FastPlan *fp, bool ahead_of_need) {
     const auto wants = [&](FastPlan *q) {
         if (!ahead_of_need || !q->taken) return true;
         uint32_t v = 0;
-        if (plan_memcpy(&v, q->taken + q->n_slots, 4, hipMemcpyDeviceToHost) != hipSuccess) return true;
+        if (staged_copy(&v, q->taken + q->n_slots, 4, hipMemcpyDeviceToHost, nullptr) != hipSuccess) return true;
         if (v) (void)hipMemset(q->taken + q->n_slots, 0, 4);
         return v > (q->cap >> 1);
     };
@@ -1894,7 +1895,7 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
         constexpr size_t kRow = kTprofRow;
         std::vector<unsigned long long> raw(kRow * (size_t)fp.n_slots);
         (void)hipStreamSynchronize(stream);
-        (void)plan_memcpy(raw.data(), sa.tprof, raw.size() * 8, hipMemcpyDeviceToHost);
+        (void)staged_copy(raw.data(), sa.tprof, raw.size() * 8, hipMemcpyDeviceToHost, nullptr);
         (void)hipFree(sa.tprof);
         unsigned long long t0 = ~0ull;
         for (uint32_t i = 0; i < grid; ++i) t0 = std::min(t0, raw[kRow * i]);
@@ -1929,7 +1930,7 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
     if (aa.tprof) {  // diagnostic: where the waves of pass 2 spend their time
         std::vector<uint32_t> raw(tprof_words);
         (void)hipStreamSynchronize(stream);
-        (void)plan_memcpy(raw.data(), aa.tprof, tprof_words * 4, hipMemcpyDeviceToHost);
+        (void)staged_copy(raw.data(), aa.tprof, tprof_words * 4, hipMemcpyDeviceToHost, nullptr);
         (void)hipFree(aa.tprof);
         const size_t waves = tprof_words / 16;
         double sum[16] = {}, mx[16] = {};
@@ -1946,7 +1947,7 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
     if (fp.dbg & kDbgTime) {  // diagnostic: where the waves of k_scan spend their cycles
         unsigned long long acc[8] = {};
         (void)hipStreamSynchronize(stream);
-        (void)plan_memcpy(acc, status + 8, sizeof acc, hipMemcpyDeviceToHost);
+        (void)staged_copy(acc, status + 8, sizeof acc, hipMemcpyDeviceToHost, nullptr);
         (void)hipMemset(status + 8, 0, sizeof acc);
         const double waves = (double)grid * kWaves;
         fprintf(stderr, "k_scan cycles per wave: wait_block %.0f  epoch_wait %.0f  passA+B %.0f  drain %.0f  other %.0f  item switch %.0f\n",

@@ -41,6 +41,7 @@
 #include "../../include/flatgfa.h"
 #include "device_common.hpp"
 #include "flatgfa_core.hpp"
+#include "host_copy.hpp"
 
 using fgfa_dev::set_error;
 
@@ -542,10 +543,10 @@ flatgfa_sharded_t *flatgfa_sharded_create(flatgfa_t gfa, const int *devices, int
         for (size_t i = 0; i < S; ++i) host[2 * Pa + i] = v.segs[i].seq.len();
         if (n_loc) {
             CR_HIP(hipMalloc(&s.d_steps, n_loc * 4));
-            CR_HIP(hipMemcpy(s.d_steps, (const char *)v.steps.data + s.step_lo * 4, n_loc * 4, hipMemcpyHostToDevice));  // (byte copy: the pool may be unaligned)
+            CR_HIP(fgfa_dev::staged_copy(s.d_steps, (const char *)v.steps.data + s.step_lo * 4, n_loc * 4, hipMemcpyHostToDevice, s.stream));  // (byte copy: the pool may be unaligned)
         }
         CR_HIP(hipMalloc(&s.d_small, std::max<size_t>(host.size(), 1) * 4));
-        CR_HIP(hipMemcpy(s.d_small, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+        CR_HIP(fgfa_dev::staged_copy(s.d_small, host.data(), host.size() * 4, hipMemcpyHostToDevice, s.stream));
         s.d_pb = s.d_small;
         s.d_pe = s.d_small + Pa;
         s.d_seg_len = s.d_small + 2 * Pa;

@@ -87,10 +87,6 @@ struct TempAlloc {
 template <class T>
 using Vec = std::vector<T, TempAlloc<T>>;
 
-
-// A copy between the host's pageable memory and the device, synchronous like hipMemcpy -- through the process's own pinned
-// staging buffers from four megabytes up: the runtime would otherwise pin the caller's pages for the transfer, and pages registered with
-// the GPU that the kernel then moves or unmaps cost the process's queues the same eviction (depth_device.hip: plan_memcpy).
-hipError_t plan_memcpy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind);
+// (their copies to and from the device go through the process's pinned staging for the same reason: host_copy.hpp)
 
 }  // namespace fgfa_dev

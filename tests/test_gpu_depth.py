@@ -6,9 +6,13 @@ because both sides divide the same two integers.  Run with `-m gpu` on an MI355X
 import os
 import subprocess
 
+import sys
+
 import numpy as np
 import pytest
 
+import chop_model
+import chop_shapes
 import pollen_amd as pa
 from conftest import GOLDEN, ROOT, fixture_id, golden_gfas
 from oracle import flatgfa_oracle as fo
@@ -181,6 +185,51 @@ def test_residency_timing_and_repeated_uploads(tmp_path):
         d, u = g.seg_depth_with_uniq()
         assert (d == want_d).all() and (u == want_u).all()
         g.close()
+
+
+MiB = 1 << 20
+
+
+def staged_graph(path, n_steps, seed):
+    """A graph with a step pool of 4 n_steps bytes (five paths over 4096 segments of 1-8 bp), written to `path`."""
+    rng = np.random.default_rng(seed)
+    S = 4096
+    cuts = np.linspace(0, n_steps, 6).astype(np.int64)
+    p = chop_shapes.make_pools(rng.integers(1, 9, S), rng.integers(0, 2 * S, n_steps, dtype=np.uint32),
+                               np.stack([cuts[:-1], cuts[1:]], 1))
+    with open(path, "wb") as f:
+        f.write(fo.dump_flatgfa(p))
+    return p
+
+
+def check_staged_copies(path, p):
+    """chop of the graph before it is resident (its steps go up, the new pools come down) and to_device + node depth,
+    each against its model.  c = 8 is the longest segment, so the pools come back at the sizes they went up at."""
+    g = pa.load(path)
+    assert chop_model.same_pools(chop_model.pools_of(g.chop(8)), chop_model.chop_fast(p, 8))
+    g.to_device(0)
+    want_d, want_u = fo.seg_depth_with_uniq(p)
+    d, u = g.seg_depth_with_uniq()
+    assert (d == want_d).all() and (u == want_u).all()
+    g.close()
+
+
+@pytest.mark.parametrize("nbytes", [4 * MiB - 4, 4 * MiB, 4 * MiB + 4, 8 * MiB + 4, 32 * MiB - 4, 32 * MiB, 32 * MiB + 4, 68 * MiB + 4])
+def test_staged_copy_route_and_chunk_boundaries(tmp_path, nbytes):
+    """Step pools on either side of the staged route's edges (4 MB: plain or staged; 32 MB: one thread or several) and of
+    its chunks, in both directions."""
+    path = str(tmp_path / "g.flatgfa")
+    check_staged_copies(path, staged_graph(path, nbytes // 4, nbytes))
+
+
+@pytest.mark.parametrize("threads", ["1", "16"])
+def test_staged_copy_thread_counts(tmp_path, threads):
+    """A 40 MB step pool up and down with FLATGFA_UPLOAD_THREADS at its ends (read once per process: a process each)."""
+    code = ("import sys; sys.path[:0] = sys.argv[1:3]; import test_gpu_depth as t; "
+            "t.check_staged_copies(sys.argv[3], t.staged_graph(sys.argv[3], 10 * 2**20 + 1, 7))")
+    r = subprocess.run([sys.executable, "-c", code, ROOT, os.path.join(ROOT, "tests"), str(tmp_path / "g.flatgfa")],
+                       capture_output=True, text=True, env=dict(os.environ, FLATGFA_UPLOAD_THREADS=threads), timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
 
 
 def test_cli_depth_is_byte_identical():
