@@ -76,7 +76,7 @@ enum {
     FLATGFA_ERR_NO_DEVICE = -3, /* no usable HIP device; there is no CPU fallback */
     FLATGFA_ERR_HIP = -4,       /* a HIP runtime call failed; see flatgfa_last_error() */
     FLATGFA_ERR_IO = -5,
-    FLATGFA_ERR_TOO_LARGE = -6, /* more than 2^32-1 steps */
+    FLATGFA_ERR_TOO_LARGE = -6, /* more than 2^32-1 steps, or a size past an operation's own limit (path overlaps: 2^28 segments) */
     FLATGFA_ERR_PARSE = -7,     /* GFA text the reference's parser panics on (flatgfa_translate_prealloc; the parse calls that return a handle return NULL) */
     FLATGFA_ERR_STALE_PLAN = -8 /* FLATGFA_CHECK_NO_CLAIM=1 only: the step values changed behind a device plan (flatgfa_dev_plan_steps_changed) */
 };
@@ -384,7 +384,8 @@ int flatgfa_dev_path_depth_all(flatgfa_dev_plan_t *plan, uint32_t *depth_out, ui
  * query_ids u32[n_q] and touch_out u8[n_q * n_paths] are device memory.  A coarse bitmap per path
  * (one bit per 2048 handles) is built on the first call and kept with the plan; exact handle
  * bitsets are built for the query paths only, per call -- memory follows the queries, not the
- * number of paths. */
+ * number of paths.  A graph of more than 2^28 segments (n_segs > 268435456) is refused with
+ * FLATGFA_ERR_TOO_LARGE before anything is written; one of 0 segments gives all zeros. */
 int flatgfa_dev_path_overlaps(flatgfa_dev_plan_t *plan, const uint32_t *query_ids, uint32_t n_q, uint8_t *touch_out,
                               void *stream);
 /* One pangenotype row on device (as flatgfa_pangenotype_matrix, for one piece of text): d_text[0, len) is

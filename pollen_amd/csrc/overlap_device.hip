@@ -205,17 +205,18 @@ extern "C" int flatgfa_dev_path_overlaps_impl(const flatgfa_dev_graph_t *g, int 
                                               uint32_t **qbits_cache, size_t *qbits_bytes, bool *qbits_all, const uint32_t *query_ids, uint32_t n_q, uint8_t *touch_out,
                                               uint32_t *status, hipStream_t stream) {
     if (n_q == 0 || g->n_paths == 0) return FLATGFA_OK;
-    const uint32_t words = (((g->n_segs + 31u) / 32u) + 3u) & ~3u;
-    if (words == 0) {
+    if (g->n_segs == 0) {
         if (hipMemsetAsync(touch_out, 0, (size_t)n_q * g->n_paths, stream) != hipSuccess) return FLATGFA_ERR_HIP;
         return FLATGFA_OK;
     }
+    // (sizes in 64 bits, the refusal before anything narrows them: (n_segs + 31) / 32 in 32 bits is 0 from 2^32 - 31 on)
     const uint64_t n_blocks = (2ull * g->n_segs + (1u << kBlockBits) - 1) >> kBlockBits;
     const uint32_t cwords = (uint32_t)((n_blocks + 31) / 32);
-    if (cwords > kCoarseMaxWords) {
+    if ((n_blocks + 31) / 32 > kCoarseMaxWords) {
         set_error("path overlaps: more than 2^28 segments");
         return FLATGFA_ERR_TOO_LARGE;
     }
+    const uint32_t words = (uint32_t)((((uint64_t)g->n_segs + 31u) / 32u + 3u) & ~(uint64_t)3u);
     if (!*coarse_cache) {
         if (hipMalloc(coarse_cache, (size_t)g->n_paths * cwords * 4u) != hipSuccess) {
             set_error("path overlaps: cannot allocate the per-path coarse bitmaps");
