@@ -206,6 +206,43 @@ int flatgfa_pangenotype_matrix(flatgfa_t gfa, const uint8_t *const *gaf, const s
  * '1' per segment id.  *text is malloc'd; release with flatgfa_free_text. */
 int flatgfa_pangenotype_table(flatgfa_t gfa, const uint8_t *const *gaf, const size_t *gaf_len, uint32_t n_files,
                               char **text, size_t *len);
+/* The GAF lookup (flatgfa/src/ops/gaf.rs; `fgfa gaf GAF [-s] [-b]`, cli/cmds.rs:311-376; flatgfa-py's all_reads and
+ * print_gaf_lookup): every line of gaf[0, len) -- the bytes before a '\n', none skipped; what follows the last '\n' is not
+ * a line -- is a read.  Field 0 is its name, field 5 its path, fields 7 and 8 its start and end along that path (digits,
+ * read wrapping).  The path's tokens (`>N` forward, `<N` backward, up to the first byte that continues neither) are looked
+ * up in the graph's NameMap and give one event each: the stretch of the segment that [start, end) covers
+ * (gaf.rs:200-243) -- none of it, all of it, or Partial(a, b).  The text goes to the device in chunks cut after a '\n'
+ * through the process's pinned staging and the answers come back the same way; the name table and the sequence pool are
+ * uploaded on first use and kept with the handle.  The graph need not be resident, and this does not make it so.
+ * Where the reference panics: a line without nine tabs or without digits, each run followed by a tab, in fields 7 and 8
+ * gives FLATGFA_ERR_PARSE; a name the graph does not have gives FLATGFA_ERR_BOUNDS; and so does, where bases are asked
+ * for (flatgfa_gaf_seqs), a Partial(a, b) that cannot be sliced (an end below the start).  flatgfa_last_error() names the
+ * byte offset of the first such line, and the line at the lowest offset decides the code.  Nothing is returned then. */
+/* `fgfa gaf GAF -b`: the number of events (and of lines, when `lines` is not NULL); every name is still looked up. */
+int flatgfa_gaf_count(flatgfa_t gfa, const uint8_t *gaf, size_t len, uint64_t *events, uint64_t *lines);
+/* The bytes `fgfa gaf GAF -s` prints (cmds.rs:349-357): per read its name, a tab, the bases its events cover as the graph
+ * spells them (a backward handle reversed and complemented: ACGTacgt to TGCAtgca, every other byte itself), a newline.
+ * *text is malloc'd; release with flatgfa_free_text. */
+int flatgfa_gaf_seqs(flatgfa_t gfa, const uint8_t *gaf, size_t len, char **text, size_t *text_len);
+/* The bytes `fgfa gaf GAF` prints (cmds.rs:367-374, gaf.rs:167-197): per read its name and a newline, then per event
+ * "{index}: {segment name}{+|-}, {a}-{b}bp", "{index}: {segment name}{+|-}, {length}bp" or "{index}: (skipped)" with nothing
+ * between or behind them.  Formatted on the host from flatgfa_gaf_events. */
+int flatgfa_gaf_table(flatgfa_t gfa, const uint8_t *gaf, size_t len, char **text, size_t *text_len);
+/* The events themselves, in host memory (one block: release with flatgfa_gaf_events_free).  Line l's events are
+ * [line_first[l], line_first[l + 1]); its name is gaf[name_off[l], name_off[l] + name_len[l]). */
+typedef struct flatgfa_gaf_events_t {
+    uint64_t n_lines;
+    uint64_t n_events;
+    uint64_t *line_first; /* [n_lines + 1] */
+    uint64_t *name_off;   /* [n_lines] */
+    uint64_t *name_len;   /* [n_lines] */
+    uint32_t *handle;     /* [n_events]: (segment id << 1) | backward */
+    uint8_t *kind;        /* [n_events]: 0 none, 1 all, 2 partial */
+    uint64_t *a;          /* [n_events]: Partial(a, b); 0 and the segment's length for all; 0, 0 for none */
+    uint64_t *b;
+} flatgfa_gaf_events_t;
+int flatgfa_gaf_events(flatgfa_t gfa, const uint8_t *gaf, size_t len, flatgfa_gaf_events_t **out);
+void flatgfa_gaf_events_free(flatgfa_gaf_events_t *ev);
 /* chop (flatgfa/src/ops/chop.rs; `fgfa chop -c max_size [-l]`, cli/main.rs:139-159): every segment longer
  * than max_size becomes ceil(len / max_size) segments -- max_size bases each, the remainder last -- numbered in
  * segment order and named id + 1; a step becomes the steps of its pieces (reversed, all backward, for a backward
@@ -396,6 +433,24 @@ int flatgfa_dev_path_overlaps(flatgfa_dev_plan_t *plan, const uint32_t *query_id
  * for the device and kept with the handle.  Enqueued on `stream`; returns without waiting. */
 int flatgfa_dev_pangenotype_row(flatgfa_t gfa, const uint8_t *d_text, size_t len, uint64_t *d_row, uint64_t *d_first_bad,
                                 void *stream);
+/* The GAF lookup on device text (as flatgfa_gaf_events and flatgfa_gaf_seqs, for one piece of text), in two calls.
+ * flatgfa_dev_gaf_count: d_text[0, len) is GAF text in device memory of the current device, at any alignment, made of
+ * whole lines (what follows its last '\n' is ignored).  It indexes the lines, parses them, forms every event and, with
+ * seqs != 0, lays out the `-s` text; it waits for `stream` to read the totals -- *n_lines, *n_events and *seq_bytes (the
+ * length of the `-s` text; 0 without seqs) -- and checks them: errors as flatgfa_gaf_events' (and, with seqs,
+ * flatgfa_gaf_seqs'), offsets counted in d_text.  *job must be NULL, or a job of an earlier call whose scratch is then
+ * used again.  flatgfa_dev_gaf_fill enqueues on `stream` the copies into caller memory (device; any pointer may be NULL):
+ * line_first u64[n_lines + 1], line_end u64[n_lines] (the offset of each line's '\n': a line, and its name, start behind
+ * the one before), name_len u64[n_lines], handle u32 / kind u8 / a, b u64 [n_events], and the gather of the `-s` text
+ * into seq_text u8[seq_bytes].  d_text must stay as it is until the fill is done.  The graph's name table and sequence
+ * pool are made on the first call for the device and kept with the handle.  flatgfa_dev_gaf_free waits for the job's
+ * stream and releases its scratch. */
+typedef struct flatgfa_dev_gaf flatgfa_dev_gaf_t;
+int flatgfa_dev_gaf_count(flatgfa_t gfa, const uint8_t *d_text, size_t len, int seqs, void *stream, flatgfa_dev_gaf_t **job,
+                          uint64_t *n_lines, uint64_t *n_events, uint64_t *seq_bytes);
+int flatgfa_dev_gaf_fill(flatgfa_dev_gaf_t *job, uint64_t *line_first, uint64_t *line_end, uint64_t *name_len, uint32_t *handle,
+                         uint8_t *kind, uint64_t *a, uint64_t *b, uint8_t *seq_text, void *stream);
+void flatgfa_dev_gaf_free(flatgfa_dev_gaf_t *job);
 /* chop (flatgfa_chop, without links) of a graph image in device memory, in two stream-ordered calls.
  * flatgfa_dev_chop_count checks the image (g->seg_len is required: FLATGFA_ERR_ARG when NULL), scans the piece
  * counts, waits for `stream` once to read the totals -- *n_segs_out new segments, *n_steps_out new steps -- and, when

@@ -69,6 +69,11 @@ SIGNATURES = {
     "flatgfa_bed_depth_table": (c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_pangenotype_matrix": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "flatgfa_pangenotype_table": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_gaf_count": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_uint64), POINTER(c_uint64)]),
+    "flatgfa_gaf_seqs": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_gaf_table": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_gaf_events": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "flatgfa_gaf_events_free": (None, [c_void_p]),
     "flatgfa_chop": (c_int, [c_void_p, c_uint64, c_int, POINTER(c_void_p)]),
     "flatgfa_sharded_create": (c_void_p, [c_void_p, c_void_p, c_int, ctypes.c_uint]),
     "flatgfa_sharded_free": (None, [c_void_p]),
@@ -101,6 +106,10 @@ SIGNATURES = {
     "flatgfa_dev_seg_depth": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "flatgfa_dev_path_sums": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "flatgfa_dev_pangenotype_row": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "flatgfa_dev_gaf_count": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, POINTER(c_void_p), POINTER(c_uint64),
+                                      POINTER(c_uint64), POINTER(c_uint64)]),
+    "flatgfa_dev_gaf_fill": (c_int, [c_void_p] * 10),
+    "flatgfa_dev_gaf_free": (None, [c_void_p]),
     "flatgfa_dev_chop_count": (c_int, [POINTER(flatgfa_dev_graph_t), c_uint64, c_void_p, c_void_p, POINTER(c_void_p),
                                        POINTER(c_uint64), POINTER(c_uint64)]),
     "flatgfa_dev_chop_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -28,6 +28,7 @@
 #include "flatgfa_core.hpp"
 #include "gaf_device.hpp"
 #include "chop_device.hpp"
+#include "gaf_lookup_device.hpp"
 
 using fgfa_dev::set_error;
 
@@ -100,6 +101,11 @@ struct CStore {
     uint64_t *d_gaf_scratch = nullptr;
     size_t gaf_scratch_words = 0;
     hipEvent_t gaf_ev = nullptr;
+    // GAF lookup: the sequence pool on one device (made on first use: Segment.seq.start and Segment::len() per segment,
+    // then seq_data), freed with the handle as the name table is
+    int gaf_seq_device = -1;
+    uint32_t *d_gaf_seg_seq = nullptr;
+    uint8_t *d_gaf_seq_data = nullptr;
 
     ~CStore() {
         if (plan) flatgfa_dev_plan_destroy(plan);
@@ -111,6 +117,7 @@ struct CStore {
         for (uint64_t *p : {d_gaf_names, d_gaf_scratch})
             if (p) (void)hipFree(p);
         if (gaf_ev) (void)hipEventDestroy(gaf_ev);
+        if (d_gaf_seg_seq) (void)hipFree(d_gaf_seg_seq);
         stream_release(device, stream);
     }
 };
@@ -1054,6 +1061,372 @@ int flatgfa_dev_pangenotype_row(flatgfa_t gfa, const uint8_t *d_text, size_t len
     CAPI_HIP(hipEventRecord(gfa->gaf_ev, stream));
     return FLATGFA_OK;
 }
+
+// ---- GAF lookup (ops/gaf.rs) ----
+
+// The handle's sequence pool on `device` (the current device), made once.  A span that leaves seq_data, where the reference
+// panics on the slice, is refused here: the gather reads what the spans say.
+static int ensure_gaf_seqs(CStore *cs, int device) {
+    if (cs->gaf_seq_device == device) return FLATGFA_OK;
+    const fgfa::View &v = cs->view;
+    const size_t S = v.segs.len, n_seq = v.seq_data.len;
+    std::vector<uint32_t> seg_seq(2 * S + 2, 0);
+    for (size_t i = 0; i < S; ++i) {
+        const fgfa::Span sp = v.segs[i].seq;
+        if (sp.start > sp.end || sp.end > n_seq) {
+            set_error("gaf: segment " + std::to_string(i) + " has a sequence span outside seq_data");
+            return FLATGFA_ERR_BOUNDS;
+        }
+        seg_seq[2 * i] = sp.start;
+        seg_seq[2 * i + 1] = sp.end - sp.start;
+    }
+    const size_t head = (seg_seq.size() * 4 + 255) & ~(size_t)255;
+    uint8_t *d = nullptr;
+    CAPI_HIP(hipMalloc(&d, head + n_seq + 16));
+    hipError_t e = fgfa_dev::staged_copy(d, seg_seq.data(), seg_seq.size() * 4, hipMemcpyHostToDevice, nullptr);
+    if (e == hipSuccess && n_seq) e = fgfa_dev::staged_copy(d + head, v.seq_data.data, n_seq, hipMemcpyHostToDevice, nullptr);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        set_error(std::string("gaf: copying the sequence pool to the device failed: ") + hipGetErrorString(e));
+        return FLATGFA_ERR_HIP;
+    }
+    if (cs->d_gaf_seg_seq) (void)hipFree(cs->d_gaf_seg_seq);  // (the handle moved to another device; hipFree waits for the memory's users)
+    cs->d_gaf_seg_seq = reinterpret_cast<uint32_t *>(d);
+    cs->d_gaf_seq_data = d + head;
+    cs->gaf_seq_device = device;
+    return FLATGFA_OK;
+}
+
+static int ensure_gaf_graph(CStore *cs, int device, fgfa_dev::GafGraph *g) {
+    int rc = ensure_gaf_names(cs, device);
+    if (!rc) rc = ensure_gaf_seqs(cs, device);
+    if (rc) return rc;
+    g->names = cs->gaf_names;
+    g->seg_seq = cs->d_gaf_seg_seq;
+    g->seq_data = cs->d_gaf_seq_data;
+    return FLATGFA_OK;
+}
+
+// Which of a piece's bad lines decides (the one at the lowest offset), as a FLATGFA_* code with its message; 0 when none is bad.
+static int gaf_lookup_verdict(const fgfa_dev::GafTotals &t, bool seqs) {
+    const uint64_t bounds = std::min<uint64_t>(t.bad_name, seqs ? t.bad_slice : ~0ull);
+    if (t.bad_parse == ~0ull && bounds == ~0ull) return FLATGFA_OK;
+    if (t.bad_parse < bounds) {
+        set_error("gaf: the line at byte offset " + std::to_string(t.bad_parse) +
+                  " is not a GAF record (nine tabs, digits in fields 7 and 8)");
+        return FLATGFA_ERR_PARSE;
+    }
+    set_error("gaf: the line at byte offset " + std::to_string(bounds) +
+              (t.bad_name <= bounds ? " names a segment that is not in the graph" : " ends before it starts: its range cannot be sliced"));
+    return FLATGFA_ERR_BOUNDS;
+}
+
+namespace {
+enum GafMode { kGafCount, kGafSeqs, kGafEvents };
+struct GafResult {
+    uint64_t n_lines = 0, n_events = 0;
+    char *text = nullptr;  // kGafSeqs: malloc'd
+    uint64_t text_len = 0, text_cap = 0;
+    std::vector<uint64_t> line_first, name_off, name_len, a, b;  // kGafEvents
+    std::vector<uint32_t> handle;
+    std::vector<uint8_t> kind;
+    ~GafResult() { free(text); }
+};
+}  // namespace
+
+// One lookup over host text: chunks cut after a '\n' go to the device through the pinned staging, each is counted, checked and
+// -- when nothing in it is bad -- its answer comes back through the same staging, the `-s` text in pieces of a bounded size.
+static int gaf_lookup_host(flatgfa_t gfa, const uint8_t *gaf, size_t len, GafMode mode, GafResult *res) {
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    int device = 0;
+    {
+        std::lock_guard<std::mutex> lk(gfa->dev_mu);
+        if (gfa->on_device) device = gfa->device;  // (beside the graph, when it is resident; it is not made so)
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_error("no HIP device is visible; the GAF lookup has no CPU fallback");
+        return FLATGFA_ERR_NO_DEVICE;
+    }
+    CAPI_HIP(hipSetDevice(device));
+    fgfa_dev::GafGraph graph;
+    int rc = ensure_gaf_graph(gfa, device, &graph);
+    if (rc) return rc;
+    if (mode == kGafEvents) res->line_first.push_back(0);
+
+    size_t target = (size_t)64 << 20, out_bound = (size_t)64 << 20;
+    if (const char *h = test_hook("FLATGFA_GAF_CHUNK_BYTES")) target = std::max<size_t>(1, strtoull(h, nullptr, 10));   // tests
+    if (const char *h = test_hook("FLATGFA_GAF_OUT_BYTES")) out_bound = std::max<size_t>(1, strtoull(h, nullptr, 10));  // tests
+    const void *last_nl = len ? memrchr(gaf, '\n', len) : nullptr;
+    const size_t end = last_nl ? (size_t)((const uint8_t *)last_nl - gaf) + 1 : 0;  // (what follows the last '\n' is not a line)
+
+    // The chunks: cut after a '\n', at most `target` bytes unless one line is longer.
+    std::vector<std::pair<size_t, size_t>> pieces;
+    size_t text_cap = 16;
+    for (size_t b = 0; b < end;) {
+        size_t e = end;
+        if (end - b > target) {
+            const void *q = memrchr(gaf + b, '\n', target);
+            if (!q) q = memchr(gaf + b + target, '\n', end - b - target);  // a line longer than a chunk grows it
+            e = (size_t)((const uint8_t *)q - gaf) + 1;
+        }
+        pieces.emplace_back(b, e);
+        text_cap = std::max(text_cap, e - b);
+        b = e;
+    }
+    if (pieces.empty()) return FLATGFA_OK;
+    text_cap = (text_cap + 255) & ~(size_t)255;
+
+    // Two text buffers: the chunk behind the one being looked up travels to the device meanwhile, on a thread and a stream of
+    // its own (a staged copy returns when the bytes have arrived).
+    hipError_t up_err = hipSuccess;  // (declared before the thread that writes it is: it outlives the join)
+    struct Release {
+        int device = 0;
+        hipStream_t st = nullptr, cs = nullptr;
+        uint8_t *d_text = nullptr, *d_out = nullptr;
+        fgfa_dev::GafLookupJob *job = nullptr;
+        std::thread up;
+        ~Release() {
+            if (up.joinable()) up.join();
+            fgfa_dev::gaf_lookup_free(job);
+            if (d_text) (void)hipFree(d_text);
+            if (d_out) (void)hipFree(d_out);
+            stream_release(device, st);
+            stream_release(device, cs);
+        }
+    } r;
+    r.device = device;
+    CAPI_HIP(stream_acquire(device, &r.st));
+    CAPI_HIP(stream_acquire(device, &r.cs));
+    r.job = fgfa_dev::gaf_lookup_new();
+    CAPI_HIP(hipMalloc(&r.d_text, (pieces.size() > 1 ? 2 : 1) * text_cap));
+    size_t out_cap = 0;
+    up_err = fgfa_dev::staged_copy(r.d_text, gaf + pieces[0].first, pieces[0].second - pieces[0].first, hipMemcpyHostToDevice, r.cs);
+    for (size_t k = 0; k < pieces.size(); ++k) {
+        if (r.up.joinable()) r.up.join();
+        CAPI_HIP(up_err);
+        const size_t b = pieces[k].first, n = pieces[k].second - b;
+        uint8_t *d_text = r.d_text + (k & 1) * text_cap;
+        if (k + 1 < pieces.size()) {  // (its buffer was read by chunk k - 1, which is done: every count and copy-back waited)
+            uint8_t *d_next = r.d_text + ((k + 1) & 1) * text_cap;
+            const uint8_t *src = gaf + pieces[k + 1].first;
+            const size_t bytes = pieces[k + 1].second - pieces[k + 1].first;
+            hipStream_t cs = r.cs;
+            r.up = std::thread([=, &up_err] {
+                up_err = hipSetDevice(device);
+                if (up_err == hipSuccess) up_err = fgfa_dev::staged_copy(d_next, src, bytes, hipMemcpyHostToDevice, cs);
+            });
+        }
+        fgfa_dev::GafTotals t;
+        rc = fgfa_dev::gaf_lookup_count(r.job, d_text, n, graph, mode == kGafSeqs, b, r.st, &t);
+        if (!rc) rc = gaf_lookup_verdict(t, mode == kGafSeqs);  // (chunks go in text order: the first bad chunk holds the lowest offset)
+        if (rc) return rc;
+        const fgfa_dev::GafArrays &ar = fgfa_dev::gaf_lookup_arrays(r.job);
+        const uint64_t L = t.n_lines, E = t.n_events;
+        if (mode == kGafSeqs) {
+            if (res->text_len + t.seq_bytes + 1 > res->text_cap) {
+                const uint64_t cap = std::max<uint64_t>(res->text_len + t.seq_bytes + 1, res->text_cap + res->text_cap / 2);
+                char *p = (char *)realloc(res->text, cap);
+                if (!p) { set_error("out of memory"); return FLATGFA_ERR_IO; }
+                res->text = p;
+                res->text_cap = cap;
+            }
+            for (uint64_t o = 0; o < t.seq_bytes;) {  // the chunk's text, a bounded piece at a time
+                const uint64_t m = std::min<uint64_t>(out_bound, t.seq_bytes - o);
+                if (m > out_cap) {  // (at most a few times a call: it grows to twice what was needed, up to the bound)
+                    if (r.d_out) CAPI_HIP(hipFree(r.d_out));
+                    r.d_out = nullptr;
+                    out_cap = std::min<uint64_t>(out_bound, 2 * std::max<uint64_t>(m, t.seq_bytes));
+                    CAPI_HIP(hipMalloc(&r.d_out, out_cap + 16));
+                }
+                rc = fgfa_dev::gaf_lookup_gather(r.job, o, o + m, r.d_out, r.st);
+                if (rc) return rc;
+                CAPI_HIP(fgfa_dev::staged_copy(res->text + res->text_len, r.d_out, m, hipMemcpyDeviceToHost, r.st));
+                res->text_len += m;
+                o += m;
+            }
+        } else if (mode == kGafEvents && L) {
+            const uint64_t L0 = res->n_lines, E0 = res->n_events;
+            res->line_first.resize(L0 + L + 1);
+            res->name_off.resize(L0 + L);
+            res->name_len.resize(L0 + L);
+            // (line_first[L0] of this chunk is 0 on the device and E0 here: copied from the chunk's second entry on)
+            CAPI_HIP(fgfa_dev::staged_copy(&res->line_first[L0 + 1], ar.line_first + 1, L * 8, hipMemcpyDeviceToHost, r.st));
+            CAPI_HIP(fgfa_dev::staged_copy(&res->name_off[L0], ar.line_end, L * 8, hipMemcpyDeviceToHost, r.st));
+            CAPI_HIP(fgfa_dev::staged_copy(&res->name_len[L0], ar.name_len, L * 8, hipMemcpyDeviceToHost, r.st));
+            for (uint64_t l = L; l-- > 0;) {  // a line starts behind the '\n' of the one before
+                res->name_off[L0 + l] = b + (l ? res->name_off[L0 + l - 1] + 1 : 0);
+                res->line_first[L0 + l + 1] += E0;
+            }
+            res->handle.resize(E0 + E);
+            res->kind.resize(E0 + E);
+            res->a.resize(E0 + E);
+            res->b.resize(E0 + E);
+            if (E) {
+                CAPI_HIP(fgfa_dev::staged_copy(&res->handle[E0], ar.handle, E * 4, hipMemcpyDeviceToHost, r.st));
+                CAPI_HIP(fgfa_dev::staged_copy(&res->kind[E0], ar.kind, E, hipMemcpyDeviceToHost, r.st));
+                CAPI_HIP(fgfa_dev::staged_copy(&res->a[E0], ar.a, E * 8, hipMemcpyDeviceToHost, r.st));
+                CAPI_HIP(fgfa_dev::staged_copy(&res->b[E0], ar.b, E * 8, hipMemcpyDeviceToHost, r.st));
+            }
+        }
+        res->n_lines += L;
+        res->n_events += E;
+    }
+    return FLATGFA_OK;
+}
+
+static int gaf_args(const char *what, flatgfa_t gfa, const uint8_t *gaf, size_t len, const void *out) {
+    if (!gfa || !out || (len && !gaf)) { set_error(std::string(what) + ": NULL argument"); return FLATGFA_ERR_ARG; }
+    return FLATGFA_OK;
+}
+
+int flatgfa_gaf_count(flatgfa_t gfa, const uint8_t *gaf, size_t len, uint64_t *events, uint64_t *lines) {
+    if (int rc = gaf_args("flatgfa_gaf_count", gfa, gaf, len, events)) return rc;
+    GafResult res;
+    if (int rc = gaf_lookup_host(gfa, gaf, len, kGafCount, &res)) return rc;
+    *events = res.n_events;
+    if (lines) *lines = res.n_lines;
+    return FLATGFA_OK;
+}
+
+int flatgfa_gaf_seqs(flatgfa_t gfa, const uint8_t *gaf, size_t len, char **text, size_t *text_len) {
+    if (int rc = gaf_args("flatgfa_gaf_seqs", gfa, gaf, len, text)) return rc;
+    *text = nullptr;
+    GafResult res;
+    if (int rc = gaf_lookup_host(gfa, gaf, len, kGafSeqs, &res)) return rc;
+    if (!res.text && !(res.text = (char *)malloc(1))) { set_error("out of memory"); return FLATGFA_ERR_IO; }
+    res.text[res.text_len] = 0;
+    *text = res.text;
+    res.text = nullptr;
+    if (text_len) *text_len = (size_t)res.text_len;
+    return FLATGFA_OK;
+}
+
+int flatgfa_gaf_events(flatgfa_t gfa, const uint8_t *gaf, size_t len, flatgfa_gaf_events_t **out) {
+    if (int rc = gaf_args("flatgfa_gaf_events", gfa, gaf, len, out)) return rc;
+    *out = nullptr;
+    GafResult res;
+    if (int rc = gaf_lookup_host(gfa, gaf, len, kGafEvents, &res)) return rc;
+    const uint64_t L = res.n_lines, E = res.n_events;
+    // one block: the struct, then the u64 arrays, the u32 array, the bytes
+    const size_t bytes = sizeof(flatgfa_gaf_events_t) + ((L + 1) + 2 * L + 2 * E) * 8 + E * 4 + E + 8;
+    char *blk = (char *)malloc(bytes);
+    if (!blk) { set_error("out of memory"); return FLATGFA_ERR_IO; }
+    flatgfa_gaf_events_t *ev = reinterpret_cast<flatgfa_gaf_events_t *>(blk);
+    uint64_t *w = reinterpret_cast<uint64_t *>(blk + sizeof(flatgfa_gaf_events_t));
+    ev->n_lines = L;
+    ev->n_events = E;
+    ev->line_first = w;
+    ev->name_off = w + L + 1;
+    ev->name_len = ev->name_off + L;
+    ev->a = ev->name_len + L;
+    ev->b = ev->a + E;
+    ev->handle = reinterpret_cast<uint32_t *>(ev->b + E);
+    ev->kind = reinterpret_cast<uint8_t *>(ev->handle + E);
+    memcpy(ev->line_first, res.line_first.data(), (L + 1) * 8);
+    if (L) {
+        memcpy(ev->name_off, res.name_off.data(), L * 8);
+        memcpy(ev->name_len, res.name_len.data(), L * 8);
+    }
+    if (E) {
+        memcpy(ev->a, res.a.data(), E * 8);
+        memcpy(ev->b, res.b.data(), E * 8);
+        memcpy(ev->handle, res.handle.data(), E * 4);
+        memcpy(ev->kind, res.kind.data(), E);
+    }
+    *out = ev;
+    return FLATGFA_OK;
+}
+
+void flatgfa_gaf_events_free(flatgfa_gaf_events_t *ev) { free(ev); }
+
+int flatgfa_gaf_table(flatgfa_t gfa, const uint8_t *gaf, size_t len, char **text, size_t *text_len) {
+    if (int rc = gaf_args("flatgfa_gaf_table", gfa, gaf, len, text)) return rc;
+    *text = nullptr;
+    flatgfa_gaf_events_t *ev = nullptr;
+    if (int rc = flatgfa_gaf_events(gfa, gaf, len, &ev)) return rc;
+    // cmds.rs:367-374, gaf.rs:167-197: the name and a newline, then the events with nothing between or behind them
+    const fgfa::View &v = gfa->view;
+    std::string s;
+    for (uint64_t l = 0; l < ev->n_lines; ++l) {
+        s.append(reinterpret_cast<const char *>(gaf) + ev->name_off[l], ev->name_len[l]);
+        s.push_back('\n');
+        for (uint64_t k = ev->line_first[l]; k < ev->line_first[l + 1]; ++k) {
+            s += std::to_string(k - ev->line_first[l]);
+            if (ev->kind[k] == 0) {
+                s += ": (skipped)";
+                continue;
+            }
+            const fgfa::Segment seg = v.segs[ev->handle[k] >> 1];
+            s += ": " + std::to_string(seg.name) + ((ev->handle[k] & 1u) ? "-, " : "+, ");
+            if (ev->kind[k] == 1) s += std::to_string(seg.seq.len()) + "bp";
+            else s += std::to_string(ev->a[k]) + "-" + std::to_string(ev->b[k]) + "bp";
+        }
+    }
+    flatgfa_gaf_events_free(ev);
+    char *p = (char *)malloc(s.size() + 1);
+    if (!p) { set_error("out of memory"); return FLATGFA_ERR_IO; }
+    memcpy(p, s.data(), s.size());
+    p[s.size()] = 0;
+    *text = p;
+    if (text_len) *text_len = s.size();
+    return FLATGFA_OK;
+}
+
+struct flatgfa_dev_gaf {
+    fgfa_dev::GafLookupJob *job = nullptr;
+    fgfa_dev::GafTotals totals;
+    ~flatgfa_dev_gaf() { fgfa_dev::gaf_lookup_free(job); }
+};
+
+int flatgfa_dev_gaf_count(flatgfa_t gfa, const uint8_t *d_text, size_t len, int seqs, void *stream, flatgfa_dev_gaf_t **job,
+                          uint64_t *n_lines, uint64_t *n_events, uint64_t *seq_bytes) {
+    if (!gfa || !job || !n_lines || !n_events || (len && !d_text)) { set_error("flatgfa_dev_gaf_count: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    int device = 0;
+    CAPI_HIP(hipGetDevice(&device));
+    fgfa_dev::GafGraph graph;
+    int rc = ensure_gaf_graph(gfa, device, &graph);
+    if (rc) return rc;
+    flatgfa_dev_gaf_t *h = *job ? *job : new flatgfa_dev_gaf();  // (a job given is used again: its scratch stays)
+    if (!h->job) h->job = fgfa_dev::gaf_lookup_new();
+    rc = fgfa_dev::gaf_lookup_count(h->job, d_text, len, graph, seqs != 0, 0, (hipStream_t)stream, &h->totals);
+    if (!rc) rc = gaf_lookup_verdict(h->totals, seqs != 0);
+    if (rc) {
+        if (!*job) delete h;
+        return rc;
+    }
+    *job = h;
+    *n_lines = h->totals.n_lines;
+    *n_events = h->totals.n_events;
+    if (seq_bytes) *seq_bytes = h->totals.seq_bytes;
+    return FLATGFA_OK;
+}
+
+int flatgfa_dev_gaf_fill(flatgfa_dev_gaf_t *job, uint64_t *line_first, uint64_t *line_end, uint64_t *name_len, uint32_t *handle,
+                         uint8_t *kind, uint64_t *a, uint64_t *b, uint8_t *seq_text, void *stream_) {
+    if (!job || !job->job) { set_error("flatgfa_dev_gaf_fill: NULL job"); return FLATGFA_ERR_ARG; }
+    hipStream_t stream = (hipStream_t)stream_;
+    const fgfa_dev::GafArrays &ar = fgfa_dev::gaf_lookup_arrays(job->job);
+    const uint64_t L = job->totals.n_lines, E = job->totals.n_events;
+    if (L) {
+        if (line_first) CAPI_HIP(hipMemcpyAsync(line_first, ar.line_first, (L + 1) * 8, hipMemcpyDeviceToDevice, stream));
+        if (line_end) CAPI_HIP(hipMemcpyAsync(line_end, ar.line_end, L * 8, hipMemcpyDeviceToDevice, stream));
+        if (name_len) CAPI_HIP(hipMemcpyAsync(name_len, ar.name_len, L * 8, hipMemcpyDeviceToDevice, stream));
+    }
+    if (E) {
+        if (handle) CAPI_HIP(hipMemcpyAsync(handle, ar.handle, E * 4, hipMemcpyDeviceToDevice, stream));
+        if (kind) CAPI_HIP(hipMemcpyAsync(kind, ar.kind, E, hipMemcpyDeviceToDevice, stream));
+        if (a) CAPI_HIP(hipMemcpyAsync(a, ar.a, E * 8, hipMemcpyDeviceToDevice, stream));
+        if (b) CAPI_HIP(hipMemcpyAsync(b, ar.b, E * 8, hipMemcpyDeviceToDevice, stream));
+    }
+    int rc = FLATGFA_OK;
+    if (seq_text && job->totals.seq_bytes) rc = fgfa_dev::gaf_lookup_gather(job->job, 0, job->totals.seq_bytes, seq_text, stream);
+    if (!rc) rc = fgfa_dev::gaf_lookup_used_on(job->job, stream);  // (the next count, or the free, waits for these copies)
+    return rc;
+}
+
+void flatgfa_dev_gaf_free(flatgfa_dev_gaf_t *job) { delete job; }
 
 // ---- chop (ops/chop.rs) ----
 

@@ -3,7 +3,7 @@
 //
 //   fgfa [-i FILE.flatgfa | -I FILE.gfa] [-o OUT.flatgfa] [-O OUT.gfa] [COMMAND]
 //   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [-s PATHS]
-//            | window-depth PATH SIZE | overlap --paths FILE | matrix GAF | chop -c N [-l]
+//            | window-depth PATH SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l]
 //
 // With no -i/-I the GFA text is read from stdin; with no COMMAND the graph is written out
 // (-o binary, -O text, otherwise text on stdout).  `depth` output is byte-identical to the
@@ -107,7 +107,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "overlap" || cmd == "matrix" || cmd == "chop";
+    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -137,7 +137,7 @@ int main(int argc, char **argv) {
         return die("cannot load graph");
     }
 #ifdef MADV_POPULATE_READ
-    if (wants_device && in_flat && cmd != "matrix") {  // (chop uploads the steps too)  // (a freshly mapped file: one call instead of a fault per page inside the upload's copies)
+    if (wants_device && in_flat && cmd != "matrix" && cmd != "gaf") {  // (chop uploads the steps too)  // (a freshly mapped file: one call instead of a fault per page inside the upload's copies)
         const void *steps = nullptr;
         uint64_t n = 0, es = 0;
         if (flatgfa_pool(g, 4, &steps, &n, &es) == 0 && n) {
@@ -334,6 +334,48 @@ int main(int argc, char **argv) {
         if (flatgfa_pangenotype_table(g, &text_in, &n, 1, &text, &len)) rc = die("matrix");
         else write_all(text, len);
         flatgfa_free_text(text);
+    } else if (cmd == "gaf") {
+        // cli/cmds.rs:311-376: fgfa gaf GAF [-s] [-b] [-p] -- one GAF file; -p without -b is unimplemented!() in the reference
+        const char *gaf = nullptr;
+        bool seqs = false, bench = false, parallel = false, bad = false;
+        for (; i < argc; ++i) {
+            const std::string a = argv[i];
+            if (a == "-s") seqs = true;
+            else if (a == "-b") bench = true;
+            else if (a == "-p") parallel = true;
+            else if (a[0] != '-' && !gaf) gaf = argv[i];
+            else bad = true;
+        }
+        if (bad || !gaf || (parallel && !bench)) {
+            fprintf(stderr, "usage: fgfa gaf GAF [-s] [-b [-p]]\n");
+            flatgfa_free(g);
+            return 2;
+        }
+        const int fd = open(gaf, O_RDONLY);
+        struct stat sb;
+        if (fd < 0 || fstat(fd, &sb) != 0) {
+            fprintf(stderr, "fgfa: cannot open %s\n", gaf);
+            if (fd >= 0) close(fd);
+            flatgfa_free(g);
+            return 1;
+        }
+        const size_t n = (size_t)sb.st_size;
+        void *m = n ? mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0) : nullptr;
+        close(fd);
+        if (m == MAP_FAILED) { fprintf(stderr, "fgfa: cannot map %s\n", gaf); flatgfa_free(g); return 1; }
+        if (m) (void)madvise(m, n, MADV_SEQUENTIAL);
+        const uint8_t *text_in = (const uint8_t *)m;
+        if (bench) {  // cmds.rs:325-347: the events are counted, nothing else is printed
+            uint64_t events = 0;
+            if (flatgfa_gaf_count(g, text_in, n, &events, nullptr)) rc = die("gaf");
+            else printf("%llu\n", (unsigned long long)events);
+        } else {
+            char *text = nullptr;
+            size_t len = 0;
+            if (seqs ? flatgfa_gaf_seqs(g, text_in, n, &text, &len) : flatgfa_gaf_table(g, text_in, n, &text, &len)) rc = die("gaf");
+            else write_all(text, len);
+            flatgfa_free_text(text);
+        }
     } else {
         fprintf(stderr, "fgfa: command '%s' is outside the depth path this build covers\n", cmd.c_str());
         rc = 2;

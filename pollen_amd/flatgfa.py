@@ -361,6 +361,53 @@ class FlatGFA:
             _lib.lib().flatgfa_pangenotype_table(self._h, ptrs, lens, k, ctypes.byref(p), ctypes.byref(n)), "pangenotype_table"))
         return _take_text(p, n)
 
+    # ---- GAF lookup (ops/gaf.rs) ----
+    def _gaf_text(self, gaf, call):
+        """`call(pointer, length, array)` over one GAF text: a file name (mapped) or bytes."""
+        box = []
+        self._gaf_call([gaf], lambda ptrs, lens, n: box.append(call(ptrs[0], lens[0])))
+        return box[0]
+
+    def gaf_count(self, gaf) -> int:
+        """`fgfa gaf GAF -b`: the number of events of all reads (flatgfa/src/cli/cmds.rs:325-347)."""
+        ev = ctypes.c_uint64()
+        self._gaf_text(gaf, lambda p, n: _check(_lib.lib().flatgfa_gaf_count(self._h, p, n, ctypes.byref(ev), None), "gaf_count"))
+        return int(ev.value)
+
+    def gaf_seqs(self, gaf) -> bytes:
+        """The bytes `fgfa gaf GAF -s` prints: per read its name, a tab, its bases as the graph spells them."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._gaf_text(gaf, lambda t, k: _check(_lib.lib().flatgfa_gaf_seqs(self._h, t, k, ctypes.byref(p), ctypes.byref(n)), "gaf_seqs"))
+        return _take_text(p, n)
+
+    def gaf_table(self, gaf) -> bytes:
+        """The bytes `fgfa gaf GAF` prints: per read its name, then which stretch of each segment it covers."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._gaf_text(gaf, lambda t, k: _check(_lib.lib().flatgfa_gaf_table(self._h, t, k, ctypes.byref(p), ctypes.byref(n)), "gaf_table"))
+        return _take_text(p, n)
+
+    def all_reads(self, gaf):
+        """flatgfa-py's FlatGFA.all_reads (flatgfa.pyi:87): the reads of a GAF file (a name, or bytes) as GAFLines, each an
+        iterable of ChunkEvents -- views over the arrays of one device lookup."""
+        from . import gaf as _gaf
+        _v, pools = self._views()
+
+        def call(ptr, n):
+            text = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), shape=(n,)) if n else np.zeros(0, np.uint8)
+            return _gaf.all_reads(self, pools, self._h, text)
+        return self._gaf_text(gaf, call)
+
+    def print_gaf_lookup(self, gaf) -> None:
+        """flatgfa-py's FlatGFA.print_gaf_lookup (flatgfa.pyi:88): the `-s` text, to stdout."""
+        import sys
+        out = self.gaf_seqs(gaf)
+        sys.stdout.flush()
+        if hasattr(sys.stdout, "buffer"):
+            sys.stdout.buffer.write(out)
+        else:  # (a text-only stand-in for stdout)
+            sys.stdout.write(out.decode(errors="replace"))
+        sys.stdout.flush()
+
     # ---- chop (ops/chop.rs) ----
     def chop(self, max_size: int, links: bool = False) -> "FlatGFA":
         """`fgfa chop -c max_size [-l]`: a new graph whose segments are at most max_size long (flatgfa/src/ops/chop.rs),
