@@ -318,7 +318,8 @@ int flatgfa_sharded_ranks_seen(flatgfa_sharded_t *sh);
  * otherwise.  This is flatgfa_sharded_create's rule for a graph whose paths' step spans lie in path order in the steps pool
  * (every path's steps behind those of the path before it: what the parser emits, flatgfa/src/parse.rs:149-159); where they do
  * not -- the types allow arbitrary spans -- flatgfa_sharded_create cuts at path boundaries only, as with
- * FLATGFA_SHARD_WHOLE_PATHS. */
+ * FLATGFA_SHARD_WHOLE_PATHS.  The rule is computed exactly for any lengths whose total is below 2^64; lengths that add up
+ * to 2^64 or more have no u64 cut points and are refused with FLATGFA_ERR_TOO_LARGE. */
 int flatgfa_shard_cuts(const uint64_t *path_steps, uint32_t n_paths, int n_shards, unsigned flags, uint64_t *cuts_out);
 
 /* ------------------------------------------------------------------------ */

@@ -260,7 +260,7 @@ void shard_cuts(const std::vector<uint64_t> &cum, int n_shards, bool may_split, 
         const uint64_t lo = cum[p], hi = cum[std::min(p + 1, P)];
         const uint64_t near = target - lo <= hi - target ? lo : hi;
         const uint64_t off = near > target ? near - target : target - near;
-        const uint64_t c = (!may_split || off * 8 * n_shards <= T) ? near : target;
+        const uint64_t c = (!may_split || (__uint128_t)off * 8 * n_shards <= T) ? near : target;  // (in 64 bits the product wraps from T = 2^56 on)
         cut[(size_t)r] = std::max(c, cut[(size_t)r - 1]);
     }
 }
@@ -602,7 +602,10 @@ int flatgfa_sharded_layout(flatgfa_sharded_t *h, int shard, int *device, uint64_
 int flatgfa_shard_cuts(const uint64_t *path_steps, uint32_t n_paths, int n_shards, unsigned flags, uint64_t *cuts_out) {
     if ((n_paths && !path_steps) || n_shards < 1 || n_shards > 64 || !cuts_out) { set_error("flatgfa_shard_cuts: bad argument"); return FLATGFA_ERR_ARG; }
     std::vector<uint64_t> cum((size_t)n_paths + 1, 0), cut;
-    for (uint32_t p = 0; p < n_paths; ++p) cum[p + 1] = cum[p] + path_steps[p];
+    for (uint32_t p = 0; p < n_paths; ++p) {
+        if (path_steps[p] > ~cum[p]) { set_error("flatgfa_shard_cuts: the path lengths add up to 2^64 or more"); return FLATGFA_ERR_TOO_LARGE; }
+        cum[p + 1] = cum[p] + path_steps[p];
+    }
     shard_cuts(cum, n_shards, !(flags & FLATGFA_SHARD_WHOLE_PATHS), &cut);
     for (int r = 0; r <= n_shards; ++r) cuts_out[r] = cut[(size_t)r];
     return FLATGFA_OK;
