@@ -159,7 +159,10 @@ int flatgfa_residency_ms(flatgfa_t gfa, double *h2d_ms, double *plan_ms);
 /* seg_depth_with_uniq (ops/depth.rs:15-39) when uniq_out != NULL, seg_depth (depth.rs:45-56)
  * when it is NULL.  Outputs are indexed by segment id, one uint64_t (Rust usize) each. */
 int flatgfa_seg_depth(flatgfa_t gfa, uint64_t *depth_out, uint64_t *uniq_out);
-/* path_depth + measure_path (ops/depth.rs:88-131) for the given path ids, in order. */
+/* path_depth + measure_path (ops/depth.rs:88-131) for the given path ids, in order.  Every path's two
+ * sums -- its length and sum of depth * segment length -- must stay below 2^64 (the reference's usize:
+ * beyond it a release build wraps and a debug build panics); the mean is (weighted as f64) / (length
+ * as f64), each total rounded to nearest-even once, and NaN for a path of no bases. */
 int flatgfa_path_depth(flatgfa_t gfa, const uint32_t *path_ids, uint32_t n_ids, uint64_t *length_out,
                        double *mean_depth_out);
 /* The bytes `fgfa depth -d` prints: SegDepth::emit (ops/depth.rs:67-82; cli/cmds.rs:237-245). */
@@ -414,7 +417,9 @@ int flatgfa_dev_path_sums(flatgfa_dev_plan_t *plan, const uint32_t *path_ids, ui
  * the two integer sums of measure_path into length_out / weighted_out u64[n_paths] (device
  * memory), indexed by path.  The sums of the paths the step-scan kernel walks are formed in the
  * same pass that accumulates node depth -- a run of segments contributes two differences of
- * window-local prefix sums -- so the steps are read once. */
+ * window-local prefix sums -- so the steps are read once.  As with flatgfa_path_depth, every path's
+ * sums must stay below 2^64; the 64-bit intermediate values (a window's prefix sums over all paths
+ * among them) wrap and their differences stay exact. */
 int flatgfa_dev_path_depth_all(flatgfa_dev_plan_t *plan, uint32_t *depth_out, uint64_t *length_out,
                                uint64_t *weighted_out, void *stream);
 /* Path-pair overlap on device (slow_odgi/slow_odgi/overlap.py:6-14): touch_out[k * n_paths + j] = 1

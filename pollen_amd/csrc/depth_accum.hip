@@ -962,7 +962,8 @@ __device__ __forceinline__ unsigned long long wave_total_u64(unsigned long long 
     FGFA_DPP_ADD64(0x142 /* row_bcast:15 */, 0xa, true);
     FGFA_DPP_ADD64(0x143 /* row_bcast:31 */, 0xc, true);
 #undef FGFA_DPP_ADD64
-    return ((unsigned long long)__builtin_amdgcn_readlane((uint32_t)(x >> 32), 63) << 32) | __builtin_amdgcn_readlane((uint32_t)x, 63);
+    // (readlane returns int: without the cast a low word with bit 31 set is sign-extended over the high word)
+    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(x >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((uint32_t)x, 63);
 }
 
 // Eight such sums at once: x[k] holds this lane's share of sum k; every lane returns the wave's
