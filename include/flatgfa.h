@@ -258,6 +258,30 @@ void flatgfa_gaf_events_free(flatgfa_gaf_events_t *ev);
  * FLATGFA_ERR_ARG; a span, step or link naming something out of range: FLATGFA_ERR_BOUNDS; 2^31 or more new
  * segments, or more than 2^32 - 1 new steps or links: FLATGFA_ERR_TOO_LARGE, found before any output is allocated. */
 int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out);
+/* extract (flatgfa/src/ops/extract.rs; `fgfa extract -n NAME -c DIST [-d N] [-e N]`, cli/cmds.rs:174-215): the subgraph
+ * around one segment.  flatgfa_find_seg is FlatGFA::find_seg (flatgfa.rs:380-384): the id of the first segment with that
+ * name, or -1.  The new graph holds the old header; the origin as segment 0 and every segment within link_distance links
+ * of it, numbered in the order the reference's walk meets them (each level pops its frontier from the back and reads all
+ * links in link order); the segments of every gap between two visits of a path to the subgraph that re-enters at a base
+ * position of at most max_distance_subpaths, swept over all paths num_iterations times (the reference CLI's defaults:
+ * 300000 and 6); every link between two kept segments with its alignment; and per path one new path
+ * "{name}:{start}-{end}" for each maximal run of steps on kept segments, without overlaps.  line_order is empty, so the
+ * graph prints in normalized order.  *out is a new heap handle that owns all its pools and outlives `gfa`.  The walk
+ * over the links, the positions, the subpaths, the link filter and the gathers run on the GPU (the device `gfa` is
+ * resident on, else device 0); a resident graph's steps are read in place, and `gfa` is not made resident (its sequence
+ * pool is kept on the device with the handle, as for the GAF lookup).  An origin, step, link or span naming something out
+ * of range: FLATGFA_ERR_BOUNDS; totals past 32-bit ids or spans: FLATGFA_ERR_TOO_LARGE, before any output is allocated. */
+int64_t flatgfa_find_seg(flatgfa_t gfa, uint64_t name);
+int flatgfa_extract(flatgfa_t gfa, uint32_t origin_seg, uint64_t link_distance, uint64_t max_distance_subpaths,
+                    uint64_t num_iterations, flatgfa_t *out);
+/* position (flatgfa/src/ops/position.rs; `fgfa position -p path,offset,+`, cli/cmds.rs:105-152): the step of a path that
+ * holds base `offset` -- the first whose end position is past it -- as *handle_out (segment << 1 | backward) and the
+ * offset into that step, with *found = 1; *found = 0 when the path is no longer than `offset`.  A segmented scan of the
+ * path's segment lengths and a search on the GPU.  flatgfa_position_table takes the CLI's argument and returns the bytes
+ * the reference prints (nothing when not found; free with flatgfa_free_text); a malformed triple, an unknown path or the
+ * orientation "-" give FLATGFA_ERR_ARG with the reference's own message in flatgfa_last_error(). */
+int flatgfa_position(flatgfa_t gfa, uint32_t path, uint64_t offset, uint32_t *handle_out, uint64_t *seg_offset_out, int *found);
+int flatgfa_position_table(flatgfa_t gfa, const uint8_t *triple, size_t len, char **text, size_t *n);
 /* The bytes `fgfa depth -b FILE.bed` prints (window_depth.rs:203-211, cli/cmds.rs:246-255); the BED
  * text is parsed as flatbed.rs:125-158 does. */
 int flatgfa_bed_depth_table(flatgfa_t gfa, const uint8_t *bed, size_t bed_len, char **text, size_t *len);

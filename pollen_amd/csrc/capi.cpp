@@ -29,6 +29,7 @@
 #include "gaf_device.hpp"
 #include "chop_device.hpp"
 #include "gaf_lookup_device.hpp"
+#include "extract_device.hpp"
 
 using fgfa_dev::set_error;
 
@@ -1552,6 +1553,305 @@ int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
     for (size_t i = 0; i < P; ++i) h.paths[i] = fgfa::Path{v.paths[i].name, fgfa::Span{spans[i], spans[Pa + i]}, fgfa::Span{0, 0}};  // chop.rs:104
     cs->view = h.view();
     *out = cs.release();
+    return FLATGFA_OK;
+}
+
+// ---- extract (ops/extract.rs) and position (ops/position.rs) ----
+
+int64_t flatgfa_find_seg(flatgfa_t gfa, uint64_t name) {
+    if (!gfa) { set_error("flatgfa_find_seg: NULL handle"); return -1; }
+    const fgfa::View &v = gfa->view;
+    for (size_t i = 0; i < v.segs.len; ++i)  // flatgfa.rs:380-384: the first one
+        if (v.segs[i].name == name) return (int64_t)i;
+    return -1;
+}
+
+extern "C++" {
+namespace {
+// What one extract or position call holds on the device, given back on every way out.
+struct DevScope {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::vector<void *> mem;
+    fgfa_dev::ExtractJob *job = nullptr;
+    ~DevScope() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        fgfa_dev::extract_free(job);
+        for (void *p : mem) (void)hipFree(p);
+        stream_release(device, stream);
+    }
+    template <class T>
+    hipError_t alloc(T **p, size_t count) {
+        *p = nullptr;
+        const hipError_t e = hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) mem.push_back(*p);
+        return e;
+    }
+    // a device copy of host memory
+    template <class T>
+    hipError_t upload(T **p, const void *src, size_t count) {
+        hipError_t e = alloc(p, count);
+        if (e == hipSuccess && count) e = fgfa_dev::staged_copy(*p, src, count * sizeof(T), hipMemcpyHostToDevice, stream);
+        return e;
+    }
+};
+
+// The device a call on `gfa` runs on (the one it is resident on, else 0), made current, with a stream.
+int open_scope(flatgfa_t gfa, DevScope *sc, bool *resident, const char *what) {
+    *resident = false;
+    {
+        std::lock_guard<std::mutex> lk(gfa->dev_mu);
+        if (gfa->on_device) sc->device = gfa->device, *resident = true;  // (beside the graph; it is not made resident)
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_error(std::string("no HIP device is visible; ") + what + " has no CPU fallback");
+        return FLATGFA_ERR_NO_DEVICE;
+    }
+    CAPI_HIP(hipSetDevice(sc->device));
+    CAPI_HIP(stream_acquire(sc->device, &sc->stream));
+    return FLATGFA_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int flatgfa_extract(flatgfa_t gfa, uint32_t origin_seg, uint64_t link_distance, uint64_t max_distance_subpaths, uint64_t num_iterations,
+                    flatgfa_t *out) {
+    if (out) *out = nullptr;
+    if (!gfa || !out) { set_error("flatgfa_extract: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    const fgfa::View &v = gfa->view;
+    const size_t N = v.steps.len, P = v.paths.len, S = v.segs.len, L = v.links.len, A = v.alignment.len;
+    if (N > 0xFFFFFFFFull || S > 0x80000000ull || P > 0xFFFFFFFEull || L > 0xFFFFFFFFull || A > 0xFFFFFFFFull) {
+        set_error("flatgfa_extract: graph too large for 32-bit ids");
+        return FLATGFA_ERR_TOO_LARGE;
+    }
+    if (origin_seg >= S) { set_error("flatgfa_extract: the origin segment is out of range"); return FLATGFA_ERR_BOUNDS; }
+    // the paths' steps one behind another: as they lie in the pool when the spans tile it in path order (what the parser makes)
+    std::vector<uint32_t> pstart(P + 1, 0), pbegin(P);
+    bool tiling = true;
+    uint64_t n_lin = 0;
+    for (size_t p = 0; p < P; ++p) {
+        const fgfa::Span sp = v.paths[p].steps;
+        if (sp.start > sp.end || sp.end > N) { set_error("flatgfa_extract: a path has a step span outside the steps pool"); return FLATGFA_ERR_BOUNDS; }
+        tiling = tiling && sp.start == n_lin;
+        pbegin[p] = sp.start;
+        n_lin += sp.len();
+        if (n_lin > 0xFFFFFFFFull) { set_error("flatgfa_extract: the paths hold more than 2^32 - 1 steps"); return FLATGFA_ERR_TOO_LARGE; }
+        pstart[p + 1] = (uint32_t)n_lin;
+    }
+    for (size_t i = 0; i < S; ++i) {
+        const fgfa::Span o = v.segs[i].optional;
+        if (o.start > o.end || o.end > v.optional_data.len) {
+            set_error("flatgfa_extract: segment " + std::to_string(i) + " has an optional-data span outside optional_data");
+            return FLATGFA_ERR_BOUNDS;
+        }
+    }
+    DevScope sc;
+    bool resident = false;
+    if (int rc = open_scope(gfa, &sc, &resident, "extract")) return rc;
+    hipStream_t st = sc.stream;
+    if (int rc = ensure_gaf_seqs(gfa, sc.device)) return rc;  // (lengths and sequences, kept with the handle)
+
+    fgfa_dev::ExtractGraph g;
+    g.n_steps = n_lin;
+    g.n_paths = (uint32_t)P;
+    g.n_segs = (uint32_t)S;
+    g.seg_seq = gfa->d_gaf_seg_seq;
+    g.n_links = L;
+    g.n_align = A;
+    uint32_t *d_pstart = nullptr, *d_links = nullptr, *d_steps = nullptr;
+    CAPI_HIP(sc.upload(&d_pstart, pstart.data(), P + 1));
+    CAPI_HIP(sc.upload(&d_links, v.links.data, L * 4));
+    g.pstart = d_pstart;
+    g.links = d_links;
+    if (resident) d_steps = gfa->d_steps;  // (used in place)
+    else CAPI_HIP(sc.upload(&d_steps, v.steps.data, N));
+    if (!tiling) {
+        uint32_t *d_pb = nullptr, *d_lin = nullptr;
+        CAPI_HIP(sc.upload(&d_pb, pbegin.data(), P));
+        CAPI_HIP(sc.alloc(&d_lin, n_lin));
+        if (int rc = fgfa_dev::gather_u32(d_steps, N, d_pb, d_pstart, P, n_lin, d_lin, st)) return rc;
+        d_steps = d_lin;
+    }
+    g.steps = d_steps;
+
+    sc.job = fgfa_dev::extract_new();
+    fgfa_dev::ExtractJob *job = sc.job;
+    int rc = fgfa_dev::extract_begin(job, g, st);
+    if (rc) return rc;
+    std::vector<uint32_t> order;  // old ids in new-id order (seg_map, extract.rs:9, inverted)
+    if ((rc = fgfa_dev::extract_bfs(job, origin_seg, link_distance, &order))) return rc;
+    if ((rc = fgfa_dev::extract_positions(job))) return rc;
+
+    // merge_subpaths (extract.rs:65-98, 181-185), on the host over each path's prefix of steps that start at or before
+    // max_distance_subpaths: a fill happens only on re-entry at such a step, and the paths and sweeps depend on one another in order
+    if (num_iterations && P) {
+        std::vector<uint32_t> plen(P);
+        if ((rc = fgfa_dev::extract_prefix_lens(job, max_distance_subpaths, plen.data()))) return rc;
+        const size_t n_bfs = order.size();
+        fgfa_dev::extract_merge_host(reinterpret_cast<const uint32_t *>(v.steps.data), pbegin.data(), plen.data(), P, S, num_iterations, &order);
+        if ((rc = fgfa_dev::extract_add(job, order.data() + n_bfs, order.size() - n_bfs, n_bfs))) return rc;
+    }
+
+    fgfa_dev::ExtractTotals tot;
+    if ((rc = fgfa_dev::extract_count(job, &tot))) return rc;
+    // the new segments, and where their sequences and optional data go
+    const size_t S2 = order.size();
+    std::vector<uint32_t> lay(4 * S2);  // seq src, seq dst, optional src, optional dst
+    uint32_t *seq_src = lay.data(), *seq_dst = seq_src + S2, *opt_src = seq_dst + S2, *opt_dst = opt_src + S2;
+    uint64_t n_seq = 0, n_opt = 0;
+    for (size_t k = 0; k < S2; ++k) {
+        const fgfa::Segment sg = v.segs[order[k]];
+        seq_src[k] = sg.seq.start, seq_dst[k] = (uint32_t)n_seq, opt_src[k] = sg.optional.start, opt_dst[k] = (uint32_t)n_opt;
+        n_seq += sg.seq.len();
+        n_opt += sg.optional.len();
+        if (n_seq > 0xFFFFFFFFull || n_opt > 0xFFFFFFFFull) {
+            set_error("flatgfa_extract: the subgraph's sequences or optional data pass 2^32 - 1 bytes");
+            return FLATGFA_ERR_TOO_LARGE;
+        }
+    }
+    uint32_t *d_lay = nullptr;
+    uint8_t *d_seq2 = nullptr, *d_opt = nullptr, *d_opt2 = nullptr;
+    fgfa_dev::ExtractOut o;
+    uint32_t *d_align = nullptr;
+    CAPI_HIP(sc.upload(&d_lay, lay.data(), lay.size()));
+    CAPI_HIP(sc.alloc(&d_seq2, n_seq));
+    CAPI_HIP(sc.alloc(&o.steps, tot.steps));
+    CAPI_HIP(sc.alloc(&o.recs, tot.paths));
+    CAPI_HIP(sc.alloc(&o.links, tot.links * 4));
+    CAPI_HIP(sc.alloc(&o.align, tot.ops));
+    if (tot.ops) CAPI_HIP(sc.upload(&d_align, v.alignment.data, A));
+    o.align_src = d_align;
+    if ((rc = fgfa_dev::extract_fill(job, o))) return rc;
+    if ((rc = fgfa_dev::gather_bytes(gfa->d_gaf_seq_data, v.seq_data.len, d_lay, d_lay + S2, S2, n_seq, d_seq2, st))) return rc;
+    if (n_opt) {
+        CAPI_HIP(sc.upload(&d_opt, v.optional_data.data, v.optional_data.len));
+        CAPI_HIP(sc.alloc(&d_opt2, n_opt));
+        if ((rc = fgfa_dev::gather_bytes(d_opt, v.optional_data.len, d_lay + 2 * S2, d_lay + 3 * S2, S2, n_opt, d_opt2, st))) return rc;
+    }
+
+    auto cs = std::make_unique<CStore>();
+    fgfa::Store &h = cs->heap;
+    std::vector<fgfa_dev::SubpathRec> recs(tot.paths);
+    CAPI_HIP(fgfa_dev::staged_copy(recs.data(), o.recs, tot.paths * sizeof(fgfa_dev::SubpathRec), hipMemcpyDeviceToHost, st));
+    // include_subpath (extract.rs:56-61): "{name}:{start}-{end}"
+    uint64_t n_name = 0;
+    for (const auto &r : recs) {
+        if (r.path >= P) { set_error("flatgfa_extract: internal: a subpath names no path"); return FLATGFA_ERR_HIP; }
+        n_name += v.paths[r.path].name.len() + 2 + std::to_string(r.start).size() + std::to_string(r.end).size();
+    }
+    if (n_name > 0xFFFFFFFFull) {
+        set_error("flatgfa_extract: the subpaths' names would take " + std::to_string(n_name) + " bytes: more than 32-bit spans hold");
+        return FLATGFA_ERR_TOO_LARGE;
+    }
+    h.header.assign(v.header.begin(), v.header.end());
+    h.segs.resize(S2);
+    for (size_t k = 0; k < S2; ++k) {
+        const fgfa::Segment sg = v.segs[order[k]];
+        h.segs[k] = fgfa::Segment{sg.name, fgfa::Span{seq_dst[k], seq_dst[k] + sg.seq.len()}, fgfa::Span{opt_dst[k], opt_dst[k] + sg.optional.len()}};
+    }
+    h.name_data.reserve(n_name);
+    h.paths.resize(tot.paths);
+    for (size_t k = 0; k < recs.size(); ++k) {
+        const fgfa_dev::SubpathRec &r = recs[k];
+        const fgfa::Span nm = v.paths[r.path].name;
+        const uint32_t b = (uint32_t)h.name_data.size();
+        h.name_data.insert(h.name_data.end(), v.name_data.data + nm.start, v.name_data.data + nm.end);
+        const std::string tail = ":" + std::to_string(r.start) + "-" + std::to_string(r.end);
+        h.name_data.insert(h.name_data.end(), tail.begin(), tail.end());
+        h.paths[k] = fgfa::Path{fgfa::Span{b, (uint32_t)h.name_data.size()}, fgfa::Span{(uint32_t)r.step_begin, (uint32_t)r.step_end}, fgfa::Span{0, 0}};
+    }
+    h.steps.resize(tot.steps);
+    h.links.resize(tot.links);
+    h.alignment.resize(tot.ops);
+    h.seq_data.resize(n_seq);
+    h.optional_data.resize(n_opt);
+    CAPI_HIP(fgfa_dev::staged_copy(h.steps.data(), o.steps, tot.steps * 4, hipMemcpyDeviceToHost, st));
+    CAPI_HIP(fgfa_dev::staged_copy(h.links.data(), o.links, tot.links * 16, hipMemcpyDeviceToHost, st));
+    CAPI_HIP(fgfa_dev::staged_copy(h.alignment.data(), o.align, tot.ops * 4, hipMemcpyDeviceToHost, st));
+    CAPI_HIP(fgfa_dev::staged_copy(h.seq_data.data(), d_seq2, n_seq, hipMemcpyDeviceToHost, st));
+    if (n_opt) CAPI_HIP(fgfa_dev::staged_copy(h.optional_data.data(), d_opt2, n_opt, hipMemcpyDeviceToHost, st));
+    cs->view = h.view();
+    *out = cs.release();
+    return FLATGFA_OK;
+}
+
+int flatgfa_position(flatgfa_t gfa, uint32_t path, uint64_t offset, uint32_t *handle_out, uint64_t *seg_offset_out, int *found) {
+    if (found) *found = 0;
+    if (!gfa || !handle_out || !seg_offset_out || !found) { set_error("flatgfa_position: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    const fgfa::View &v = gfa->view;
+    if (path >= v.paths.len) { set_error("flatgfa_position: the path index is out of range"); return FLATGFA_ERR_BOUNDS; }
+    const fgfa::Span sp = v.paths[path].steps;
+    if (sp.start > sp.end || sp.end > v.steps.len) { set_error("flatgfa_position: the path has a step span outside the steps pool"); return FLATGFA_ERR_BOUNDS; }
+    if (v.segs.len > 0x80000000ull) { set_error("flatgfa_position: graph too large for 32-bit ids"); return FLATGFA_ERR_TOO_LARGE; }
+    DevScope sc;
+    bool resident = false;
+    if (int rc = open_scope(gfa, &sc, &resident, "position")) return rc;
+    if (int rc = ensure_gaf_seqs(gfa, sc.device)) return rc;
+    const uint32_t *d_steps = nullptr;
+    if (resident) {
+        d_steps = gfa->d_steps + sp.start;
+    } else {
+        uint32_t *d = nullptr;
+        CAPI_HIP(sc.upload(&d, v.steps.data + sp.start, sp.len()));
+        d_steps = d;
+    }
+    uint64_t index = 0, start = 0;
+    if (int rc = fgfa_dev::position_find(d_steps, sp.len(), gfa->d_gaf_seg_seq, (uint32_t)v.segs.len, offset, sc.stream, &index, &start)) return rc;
+    if (index < sp.len()) {
+        *handle_out = v.steps[sp.start + index].bits;
+        *seg_offset_out = offset - start;
+        *found = 1;
+    }
+    return FLATGFA_OK;
+}
+
+int flatgfa_position_table(flatgfa_t gfa, const uint8_t *triple, size_t len, char **text, size_t *n) {
+    if (text) *text = nullptr;
+    if (n) *n = 0;
+    if (!gfa || !text || !n || (len && !triple)) { set_error("flatgfa_position_table: NULL argument"); return FLATGFA_ERR_ARG; }
+    // cmds.rs:114-132, with its messages
+    const std::string arg((const char *)triple, len);
+    std::vector<std::string> parts(1);
+    for (char c : arg) {
+        if (c == ',') parts.emplace_back();
+        else parts.back().push_back(c);
+    }
+    if (parts.size() != 3) { set_error("position must be path_name,offset,orientation"); return FLATGFA_ERR_ARG; }
+    uint64_t offset = 0;
+    {   // usize::from_str: an optional '+', then digits only, within 64 bits
+        const std::string &t = parts[1];
+        size_t k = !t.empty() && t[0] == '+' ? 1 : 0;
+        bool ok = k < t.size();
+        for (; ok && k < t.size(); ++k) {
+            if (t[k] < '0' || t[k] > '9') { ok = false; break; }
+            const uint64_t d = (uint64_t)(t[k] - '0');
+            if (offset > (UINT64_MAX - d) / 10) { ok = false; break; }
+            offset = offset * 10 + d;
+        }
+        if (!ok) { set_error("offset must be a number"); return FLATGFA_ERR_ARG; }
+    }
+    if (parts[2] != "+" && parts[2] != "-") { set_error("orientation must be + or -"); return FLATGFA_ERR_ARG; }
+    const int64_t path = gfa->view.find_path((const uint8_t *)parts[0].data(), parts[0].size());
+    if (path < 0) { set_error("path not found"); return FLATGFA_ERR_ARG; }
+    if (parts[2] != "+") { set_error("only + is implemented so far"); return FLATGFA_ERR_ARG; }
+    uint32_t handle = 0;
+    uint64_t seg_off = 0;
+    int found = 0;
+    if (int rc = flatgfa_position(gfa, (uint32_t)path, offset, &handle, &seg_off, &found)) return rc;
+    std::string out;
+    if (found) {  // cmds.rs:136-149
+        out = "#source.path.pos\ttarget.graph.pos\n" + parts[0] + "," + std::to_string(offset) + ",+\t" +
+              std::to_string(gfa->view.segs[handle >> 1].name) + "," + std::to_string(seg_off) + "," + ((handle & 1u) ? "-" : "+") + "\n";
+    }
+    char *buf = (char *)malloc(out.size() + 1);
+    if (!buf) { set_error("flatgfa_position_table: out of memory"); return FLATGFA_ERR_ARG; }
+    memcpy(buf, out.data(), out.size());
+    buf[out.size()] = 0;
+    *text = buf;
+    *n = out.size();
     return FLATGFA_OK;
 }
 

@@ -4,11 +4,12 @@
 //   fgfa [-i FILE.flatgfa | -I FILE.gfa] [-o OUT.flatgfa] [-O OUT.gfa] [COMMAND]
 //   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [-s PATHS]
 //            | window-depth PATH SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l]
+//            | extract -n NAME -c DIST [-d N] [-e N] | position -p PATH,OFFSET,+
 //
 // With no -i/-I the GFA text is read from stdin; with no COMMAND the graph is written out
 // (-o binary, -O text, otherwise text on stdout).  `depth` output is byte-identical to the
-// reference's and is computed on the GPU, as are `matrix` (cmds.rs:453-475) and `chop` (cli/main.rs:139-159), whose graph is
-// written out as the input graph would be.  Everything else in the reference CLI is out of scope.
+// reference's and is computed on the GPU, as are `matrix` (cmds.rs:453-475), `position` (cmds.rs:105-152), and `chop`
+// (cli/main.rs:139-159) and `extract` (cmds.rs:174-215), whose graph is written out as the input graph would be.  Everything else in the reference CLI is out of scope.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -107,7 +108,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop";
+    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "extract" || cmd == "position";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -193,6 +194,47 @@ int main(int argc, char **argv) {
         flatgfa_t chopped = nullptr;
         if (flatgfa_chop(g, count, links ? 1 : 0, &chopped)) rc = die("chop");
         else rc = dump(chopped);
+    } else if (cmd == "extract") {
+        // cli/cmds.rs:174-215: fgfa extract -n NAME -c DIST [-d N] [-e N]
+        uint64_t name = 0, dist = 0, max_dist = 300000, iters = 6;
+        bool have_n = false, have_c = false, bad = false;
+        for (; i < argc; ++i) {
+            const std::string a = argv[i];
+            uint64_t *dst = nullptr;
+            if (a == "-n" || a == "--seg-name") dst = &name, have_n = true;
+            else if (a == "-c" || a == "--link-distance") dst = &dist, have_c = true;
+            else if (a == "-d" || a == "--max-distance-subpaths") dst = &max_dist;
+            else if (a == "-e" || a == "--max-merging-iterations") dst = &iters;
+            if (!dst || i + 1 >= argc) { bad = true; break; }
+            char *end = nullptr;
+            const char *val = argv[++i];
+            *dst = strtoull(val, &end, 10);
+            bad = bad || *val < '0' || *val > '9' || *end;
+        }
+        if (bad || !have_n || !have_c) {
+            fprintf(stderr, "usage: fgfa extract -n NAME -c DIST [-d MAX_DISTANCE_SUBPATHS] [-e MAX_MERGING_ITERATIONS]\n");
+            flatgfa_free(g);
+            return 2;
+        }
+        const int64_t origin = flatgfa_find_seg(g, name);
+        flatgfa_t sub = nullptr;
+        if (origin < 0) { fprintf(stderr, "Error: \"segment not found\"\n"); rc = 1; }  // (main's Err, cli/main.rs:132-133)
+        else if (flatgfa_extract(g, (uint32_t)origin, dist, max_dist, iters, &sub)) rc = die("extract");
+        else rc = dump(sub);
+    } else if (cmd == "position") {
+        // cli/cmds.rs:105-152: fgfa position -p PATH,OFFSET,+
+        if (i + 2 != argc || (strcmp(argv[i], "-p") && strcmp(argv[i], "--path-pos"))) {
+            fprintf(stderr, "usage: fgfa position -p PATH,OFFSET,+\n");
+            flatgfa_free(g);
+            return 2;
+        }
+        char *text = nullptr;
+        size_t n = 0;
+        const int prc = flatgfa_position_table(g, (const uint8_t *)argv[i + 1], strlen(argv[i + 1]), &text, &n);
+        if (prc == FLATGFA_ERR_ARG) { fprintf(stderr, "Error: \"%s\"\n", flatgfa_last_error()); rc = 1; }  // (the reference's Err)
+        else if (prc) rc = die("position");
+        else write_all(text, n);
+        flatgfa_free_text(text);
     } else if (cmd == "toc") {
         bool bytes = i < argc && !strcmp(argv[i], "-b");
         static const char *names[11] = {"header", "segs", "paths", "links", "steps", "seq_data",

@@ -416,6 +416,42 @@ class FlatGFA:
         _check(_lib.lib().flatgfa_chop(self._h, int(max_size), 1 if links else 0, ctypes.byref(h)), "chop")
         return FlatGFA(h.value)
 
+    # ---- extract (ops/extract.rs) and position (ops/position.rs) ----
+    def find_seg(self, name: int) -> Optional[int]:
+        """The id of the first segment called `name` (FlatGFA::find_seg), or None."""
+        i = _lib.lib().flatgfa_find_seg(self._h, int(name))
+        return None if i < 0 else int(i)
+
+    def extract(self, seg_name: int, link_distance: int, max_distance_subpaths: int = 300000, num_iterations: int = 6) -> "FlatGFA":
+        """`fgfa extract -n seg_name -c link_distance [-d max_distance_subpaths] [-e num_iterations]`: the subgraph within
+        link_distance links of the segment, with the subpaths through it (flatgfa/src/ops/extract.rs), computed on the GPU.
+        KeyError when no segment has that name.  The result owns its pools and outlives this graph."""
+        origin = self.find_seg(seg_name)
+        if origin is None:
+            raise KeyError("segment not found")
+        h = ctypes.c_void_p()
+        _check(_lib.lib().flatgfa_extract(self._h, origin, int(link_distance), int(max_distance_subpaths), int(num_iterations),
+                                          ctypes.byref(h)), "extract")
+        return FlatGFA(h.value)
+
+    def position(self, path_name: bytes, offset: int) -> Optional[Tuple[int, int, bool]]:
+        """`fgfa position -p path_name,offset,+`: (segment name, offset into the step, forward?) of the step of the path that
+        holds base `offset`, or None past the path's end (flatgfa/src/ops/position.rs).  KeyError for an unknown path."""
+        p = self.find_path(path_name)
+        if p is None:
+            raise KeyError("path not found")
+        hd, off, found = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_int()
+        _check(_lib.lib().flatgfa_position(self._h, p, int(offset), ctypes.byref(hd), ctypes.byref(off), ctypes.byref(found)), "position")
+        if not found.value:
+            return None
+        return int(self.pool("segs")["name"][hd.value >> 1]), int(off.value), (hd.value & 1) == 0
+
+    def position_table(self, triple: bytes) -> bytes:
+        """The bytes `fgfa position -p triple` prints."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(_lib.lib().flatgfa_position_table(self._h, triple, len(triple), ctypes.byref(p), ctypes.byref(n)), "position")
+        return _take_text(p, n)
+
 
 SHARD_WHOLE_PATHS = 1  # FLATGFA_SHARD_WHOLE_PATHS
 SHARD_NO_RCCL = 2      # FLATGFA_SHARD_NO_RCCL
