@@ -282,6 +282,29 @@ int flatgfa_extract(flatgfa_t gfa, uint32_t origin_seg, uint64_t link_distance, 
  * orientation "-" give FLATGFA_ERR_ARG with the reference's own message in flatgfa_last_error(). */
 int flatgfa_position(flatgfa_t gfa, uint32_t path, uint64_t offset, uint32_t *handle_out, uint64_t *seg_offset_out, int *found);
 int flatgfa_position_table(flatgfa_t gfa, const uint8_t *triple, size_t len, char **text, size_t *n);
+/* validate (slow_odgi/slow_odgi/validate.py:5-25; `fgfa validate`): do the links support the paths?  Every path is walked
+ * in path order and every pair of consecutive steps (a, b) of one path in step order -- a path of fewer than two steps has
+ * none (validate.py:11-12), and a path's last step forms none with the next path's first.  The pair is supported when a link
+ * has (from, to) == (a, b) or == (flip(b), flip(a)) (validate.py:16-19 over the `outs` lists of mygfa/preprocess.py:23-43).
+ * One record per unsupported pair, in that order: the path's index, the index of `a` within the path, and the two handles
+ * (segment << 1 | backward).  *out is malloc'd (release with flatgfa_missing_links_free) and may be NULL when *n == 0;
+ * out == NULL with n != NULL returns the count only.  flatgfa_validate_table returns the bytes the reference prints, one
+ * line per record (validate.py:20-24; nothing for a valid graph; free with flatgfa_free_text), formatted on the host.
+ * The links become an index on the GPU -- built on the first validate or degree call, kept with the handle and freed by
+ * flatgfa_free -- and one pass over the steps looks every pair up in it (the device `gfa` is resident on, else device 0;
+ * a resident graph's steps are read in place, and `gfa` is not made resident).  A link or a step naming a segment out of
+ * range, or a path whose span leaves the steps pool: FLATGFA_ERR_BOUNDS; NULL arguments: FLATGFA_ERR_ARG. */
+typedef struct { uint32_t path, step, from, to; } flatgfa_missing_link_t;
+int flatgfa_validate(flatgfa_t gfa, flatgfa_missing_link_t **out, uint64_t *n);
+void flatgfa_missing_links_free(flatgfa_missing_link_t *p);
+int flatgfa_validate_table(flatgfa_t gfa, char **text, size_t *len);
+/* degree (slow_odgi/slow_odgi/degree.py:5-18; `fgfa degree`): degree_out[s] = the number of link ends on segment s -- the
+ * links whose `from` names it plus those whose `to` does, whatever the orientations (degree.py:11-16: the four lists of
+ * preprocess.py:31-41), so a self-loop counts 2 and a duplicate link counts again.  Counted on the GPU in the pass that
+ * builds the link index.  flatgfa_degree_table: "#node.id\tnode.degree\n", then "{name}\t{degree}\n" per segment in pool
+ * order (degree.py:7, 17; free with flatgfa_free_text). */
+int flatgfa_degree(flatgfa_t gfa, uint64_t *degree_out /* [segment_count] */);
+int flatgfa_degree_table(flatgfa_t gfa, char **text, size_t *len);
 /* The bytes `fgfa depth -b FILE.bed` prints (window_depth.rs:203-211, cli/cmds.rs:246-255); the BED
  * text is parsed as flatbed.rs:125-158 does. */
 int flatgfa_bed_depth_table(flatgfa_t gfa, const uint8_t *bed, size_t bed_len, char **text, size_t *len);

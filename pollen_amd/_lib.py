@@ -79,6 +79,11 @@ SIGNATURES = {
     "flatgfa_extract": (c_int, [c_void_p, c_uint32, c_uint64, c_uint64, c_uint64, POINTER(c_void_p)]),
     "flatgfa_position": (c_int, [c_void_p, c_uint32, c_uint64, POINTER(c_uint32), POINTER(c_uint64), POINTER(c_int)]),
     "flatgfa_position_table": (c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_validate": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_uint64)]),
+    "flatgfa_missing_links_free": (None, [c_void_p]),
+    "flatgfa_validate_table": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_degree": (c_int, [c_void_p, c_void_p]),
+    "flatgfa_degree_table": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_sharded_create": (c_void_p, [c_void_p, c_void_p, c_int, ctypes.c_uint]),
     "flatgfa_sharded_free": (None, [c_void_p]),
     "flatgfa_sharded_layout": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint32),

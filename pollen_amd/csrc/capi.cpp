@@ -30,6 +30,7 @@
 #include "chop_device.hpp"
 #include "gaf_lookup_device.hpp"
 #include "extract_device.hpp"
+#include "topology_device.hpp"
 
 using fgfa_dev::set_error;
 
@@ -107,6 +108,9 @@ struct CStore {
     int gaf_seq_device = -1;
     uint32_t *d_gaf_seg_seq = nullptr;
     uint8_t *d_gaf_seq_data = nullptr;
+    // validate, degree: the link index on one device (made on the first validate or degree call, never for a graph that is not asked)
+    int topo_device = -1;
+    fgfa_dev::TopoIndex topo;
 
     ~CStore() {
         if (plan) flatgfa_dev_plan_destroy(plan);
@@ -119,6 +123,7 @@ struct CStore {
             if (p) (void)hipFree(p);
         if (gaf_ev) (void)hipEventDestroy(gaf_ev);
         if (d_gaf_seg_seq) (void)hipFree(d_gaf_seg_seq);
+        fgfa_dev::topo_index_free(&topo);
         stream_release(device, stream);
     }
 };
@@ -1853,6 +1858,124 @@ int flatgfa_position_table(flatgfa_t gfa, const uint8_t *triple, size_t len, cha
     *text = buf;
     *n = out.size();
     return FLATGFA_OK;
+}
+
+// ---- validate (slow_odgi/validate.py) and degree (slow_odgi/degree.py) ----
+
+extern "C++" {
+namespace {
+// The handle's link index on `device` (the current device), made once: the links are uploaded for the build only.
+int ensure_topo(CStore *cs, DevScope *sc) {
+    if (cs->topo_device == sc->device) return FLATGFA_OK;
+    const fgfa::View &v = cs->view;
+    if (v.links.len > 0xFFFFFFFFull || v.segs.len > 0x7FFFFFFFull) {
+        set_error("topology: graph too large for 32-bit ids");
+        return FLATGFA_ERR_TOO_LARGE;
+    }
+    uint32_t *d_links = nullptr;
+    CAPI_HIP(hipMalloc((void **)&d_links, std::max<size_t>(v.links.len, 1) * 16));
+    hipError_t e = hipSuccess;
+    if (v.links.len) e = fgfa_dev::staged_copy(d_links, v.links.data, v.links.len * 16, hipMemcpyHostToDevice, sc->stream);
+    fgfa_dev::TopoIndex ix;
+    int rc = FLATGFA_OK;
+    if (e == hipSuccess) rc = fgfa_dev::topo_index_build(d_links, v.links.len, (uint32_t)v.segs.len, sc->stream, &ix);
+    (void)hipStreamSynchronize(sc->stream);
+    (void)hipFree(d_links);
+    CAPI_HIP(e);
+    if (rc) return rc;
+    fgfa_dev::topo_index_free(&cs->topo);  // (the handle moved to another device)
+    cs->topo = ix;
+    cs->topo_device = sc->device;
+    return FLATGFA_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int flatgfa_validate(flatgfa_t gfa, flatgfa_missing_link_t **out, uint64_t *n) {
+    if (out) *out = nullptr;
+    if (n) *n = 0;
+    if (!gfa || !n) { set_error("flatgfa_validate: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    const fgfa::View &v = gfa->view;
+    const size_t N = v.steps.len, P = v.paths.len;
+    if (N > 0xFFFFFFFFull || P > 0xFFFFFFFEull) { set_error("flatgfa_validate: graph too large for 32-bit ids"); return FLATGFA_ERR_TOO_LARGE; }
+    // the paths' steps numbered one behind another, whatever their spans do in the pool (they may overlap or leave gaps)
+    std::vector<uint32_t> pstart(P + 1, 0), pbegin(P + 1, 0);
+    uint64_t n_lin = 0;
+    for (size_t p = 0; p < P; ++p) {
+        const fgfa::Span sp = v.paths[p].steps;
+        if (sp.start > sp.end || sp.end > N) { set_error("flatgfa_validate: a path has a step span outside the steps pool"); return FLATGFA_ERR_BOUNDS; }
+        pbegin[p] = sp.start;
+        n_lin += sp.len();
+        if (n_lin > 0xFFFFFFFFull) { set_error("flatgfa_validate: the paths hold more than 2^32 - 1 steps"); return FLATGFA_ERR_TOO_LARGE; }
+        pstart[p + 1] = (uint32_t)n_lin;
+    }
+    DevScope sc;
+    bool resident = false;
+    if (int rc = open_scope(gfa, &sc, &resident, "validate")) return rc;
+    if (int rc = ensure_topo(gfa, &sc)) return rc;
+    fgfa_dev::TopoSteps ts;
+    uint32_t *d_pstart = nullptr, *d_pbegin = nullptr, *d_steps = nullptr;
+    CAPI_HIP(sc.upload(&d_pstart, pstart.data(), P + 1));
+    CAPI_HIP(sc.upload(&d_pbegin, pbegin.data(), P + 1));
+    if (resident) d_steps = gfa->d_steps;  // (read in place)
+    else CAPI_HIP(sc.upload(&d_steps, v.steps.data, N));
+    ts.steps = d_steps, ts.pstart = d_pstart, ts.pbegin = d_pbegin, ts.n_paths = (uint32_t)P, ts.n_lin = n_lin;
+    struct JobGuard {
+        fgfa_dev::ValidateJob *j;
+        ~JobGuard() { fgfa_dev::validate_free(j); }
+    } job{fgfa_dev::validate_new()};  // (declared after the scope: freed before its stream goes back)
+    uint64_t count = 0;
+    if (int rc = fgfa_dev::validate_count(job.j, gfa->topo, ts, sc.stream, &count)) return rc;
+    *n = count;
+    if (!out || !count) return FLATGFA_OK;
+    flatgfa_missing_link_t *recs = (flatgfa_missing_link_t *)malloc((size_t)count * sizeof *recs);
+    if (!recs) { set_error("flatgfa_validate: out of memory"); return FLATGFA_ERR_IO; }
+    if (int rc = fgfa_dev::validate_fill(job.j, recs)) {
+        free(recs);
+        return rc;
+    }
+    *out = recs;
+    return FLATGFA_OK;
+}
+
+void flatgfa_missing_links_free(flatgfa_missing_link_t *p) { free(p); }
+
+int flatgfa_validate_table(flatgfa_t gfa, char **text, size_t *len) {
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (!gfa || !text) { set_error("flatgfa_validate_table: NULL argument"); return FLATGFA_ERR_ARG; }
+    flatgfa_missing_link_t *recs = nullptr;
+    uint64_t n = 0;
+    if (int rc = flatgfa_validate(gfa, &recs, &n)) return rc;
+    // the text is made on the host: a graph worth validating has few or no missing links
+    static_assert(sizeof(fgfa::MissingLink) == sizeof(flatgfa_missing_link_t), "one record layout");
+    std::string out;
+    const bool ok = fgfa::emit_missing_links(gfa->view, reinterpret_cast<const fgfa::MissingLink *>(recs), (size_t)n, &out);
+    flatgfa_missing_links_free(recs);
+    if (!ok) { set_error("flatgfa_validate_table: internal: a record names no path or segment"); return FLATGFA_ERR_HIP; }
+    return give_text(out, text, len);
+}
+
+int flatgfa_degree(flatgfa_t gfa, uint64_t *degree_out) {
+    if (!gfa || !degree_out) { set_error("flatgfa_degree: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    DevScope sc;
+    bool resident = false;
+    if (int rc = open_scope(gfa, &sc, &resident, "degree")) return rc;
+    if (int rc = ensure_topo(gfa, &sc)) return rc;
+    return fgfa_dev::topo_degree(gfa->topo, sc.stream, degree_out);
+}
+
+int flatgfa_degree_table(flatgfa_t gfa, char **text, size_t *len) {
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (!gfa || !text) { set_error("flatgfa_degree_table: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::vector<uint64_t> deg(gfa->view.segs.len + 1, 0);
+    if (int rc = flatgfa_degree(gfa, deg.data())) return rc;
+    std::string out;
+    fgfa::emit_degree(gfa->view, deg.data(), &out);
+    return give_text(out, text, len);
 }
 
 }  // extern "C"

@@ -4,12 +4,13 @@
 //   fgfa [-i FILE.flatgfa | -I FILE.gfa] [-o OUT.flatgfa] [-O OUT.gfa] [COMMAND]
 //   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [-s PATHS]
 //            | window-depth PATH SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l]
-//            | extract -n NAME -c DIST [-d N] [-e N] | position -p PATH,OFFSET,+
+//            | extract -n NAME -c DIST [-d N] [-e N] | position -p PATH,OFFSET,+ | validate | degree
 //
 // With no -i/-I the GFA text is read from stdin; with no COMMAND the graph is written out
 // (-o binary, -O text, otherwise text on stdout).  `depth` output is byte-identical to the
 // reference's and is computed on the GPU, as are `matrix` (cmds.rs:453-475), `position` (cmds.rs:105-152), and `chop`
-// (cli/main.rs:139-159) and `extract` (cmds.rs:174-215), whose graph is written out as the input graph would be.  Everything else in the reference CLI is out of scope.
+// (cli/main.rs:139-159) and `extract` (cmds.rs:174-215), whose graph is written out as the input graph would be; `validate` and `degree` print what slow_odgi's validate.py and
+// degree.py print.  Everything else in the reference CLI is out of scope.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -108,7 +109,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "extract" || cmd == "position";
+    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -233,6 +234,18 @@ int main(int argc, char **argv) {
         const int prc = flatgfa_position_table(g, (const uint8_t *)argv[i + 1], strlen(argv[i + 1]), &text, &n);
         if (prc == FLATGFA_ERR_ARG) { fprintf(stderr, "Error: \"%s\"\n", flatgfa_last_error()); rc = 1; }  // (the reference's Err)
         else if (prc) rc = die("position");
+        else write_all(text, n);
+        flatgfa_free_text(text);
+    } else if (cmd == "validate" || cmd == "degree") {
+        // slow_odgi validate (validate.py:5-25), slow_odgi degree (degree.py:5-18): no arguments; the exit status is 0 whatever validate finds
+        if (i != argc) {
+            fprintf(stderr, "usage: fgfa %s\n", cmd.c_str());
+            flatgfa_free(g);
+            return 2;
+        }
+        char *text = nullptr;
+        size_t n = 0;
+        if (cmd == "validate" ? flatgfa_validate_table(g, &text, &n) : flatgfa_degree_table(g, &text, &n)) rc = die(cmd.c_str());
         else write_all(text, n);
         flatgfa_free_text(text);
     } else if (cmd == "toc") {

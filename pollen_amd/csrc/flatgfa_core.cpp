@@ -1150,4 +1150,31 @@ void emit_overlap(const View &v, const uint32_t *query_ids, size_t n_q, const ui
     }
 }
 
+bool emit_missing_links(const View &v, const MissingLink *recs, size_t n, std::string *out) {  // slow_odgi/validate.py:20-24
+    for (size_t k = 0; k < n; ++k) {
+        const MissingLink r = recs[k];
+        if (r.path >= v.paths.len || (r.from >> 1) >= v.segs.len || (r.to >> 1) >= v.segs.len) return false;
+        const Span nm = v.paths[r.path].name;
+        if (nm.start > nm.end || nm.end > v.name_data.len) return false;
+        out->append("[odgi::validate] error: the path ");
+        out->append((const char *)v.name_data.data + nm.start, nm.len());
+        out->append(" does not respect the graph topology: the link ");
+        put_handle(v, r.from, out);
+        out->push_back(',');
+        put_handle(v, r.to, out);
+        out->append(" is missing.\n");
+    }
+    return true;
+}
+
+void emit_degree(const View &v, const uint64_t *degree, std::string *out) {  // slow_odgi/degree.py:7, 17
+    out->append("#node.id\tnode.degree\n");
+    for (size_t i = 0; i < v.segs.len; ++i) {
+        put_u64(out, v.segs[i].name);
+        out->push_back('\t');
+        put_u64(out, degree[i]);
+        out->push_back('\n');
+    }
+}
+
 }  // namespace fgfa

@@ -264,6 +264,14 @@ void emit_interval_depth(const Bed &bed, const double *depths, std::string *out)
 // slow_odgi/slow_odgi/overlap.py:17-32
 void emit_overlap(const View &v, const uint32_t *query_ids, size_t n_q, const uint64_t *path_len, const uint8_t *touch,
                   std::string *out);
+// slow_odgi/slow_odgi/validate.py:20-24: one line per unsupported step pair (the records of flatgfa_validate).  False, with
+// `out` left at the lines before it, for a record that names a path or a segment the graph does not have.
+struct MissingLink {
+    uint32_t path, step, from, to;
+};
+bool emit_missing_links(const View &v, const MissingLink *recs, size_t n, std::string *out);
+// slow_odgi/slow_odgi/degree.py:7, 17
+void emit_degree(const View &v, const uint64_t *degree, std::string *out);
 
 // The synthetic-graph generator of SURVEY.md 8(d) (spec: oracle/synth.py).
 // model 0 = pangenome, 1 = uniform, 2 = chromosome, 3 = haplotype (oracle/synth.py has the spec).

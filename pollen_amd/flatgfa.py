@@ -452,6 +452,47 @@ class FlatGFA:
         _check(_lib.lib().flatgfa_position_table(self._h, triple, len(triple), ctypes.byref(p), ctypes.byref(n)), "position")
         return _take_text(p, n)
 
+    # ---- validate (slow_odgi/validate.py) and degree (slow_odgi/degree.py) ----
+    def validate(self) -> np.ndarray:
+        """`fgfa validate` as records: one per pair of consecutive steps of a path that no link supports, in path order then
+        step order (slow_odgi/validate.py:9-24) -- `path`, `step` (the index of the pair's first step in its path), and the
+        two handles `src` and `dst` (segment << 1 | backward).  Empty for a graph whose paths are walks of it."""
+        out, n = ctypes.c_void_p(), ctypes.c_uint64()
+        _check(_lib.lib().flatgfa_validate(self._h, ctypes.byref(out), ctypes.byref(n)), "validate")
+        try:
+            if not n.value:
+                return np.zeros(0, MISSING_LINK_DT)
+            raw = (ctypes.c_char * (n.value * MISSING_LINK_DT.itemsize)).from_address(out.value)  # (string_at takes a C int)
+            return np.frombuffer(raw, MISSING_LINK_DT).copy()
+        finally:
+            _lib.lib().flatgfa_missing_links_free(out)
+
+    def validate_count(self) -> int:
+        """How many records validate() would return, without fetching them."""
+        n = ctypes.c_uint64()
+        _check(_lib.lib().flatgfa_validate(self._h, None, ctypes.byref(n)), "validate")
+        return int(n.value)
+
+    def validate_table(self) -> bytes:
+        """The bytes `fgfa validate` prints: nothing for a valid graph."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(_lib.lib().flatgfa_validate_table(self._h, ctypes.byref(p), ctypes.byref(n)), "validate")
+        return _take_text(p, n)
+
+    def degree(self) -> np.ndarray:
+        """slow_odgi/degree.py:9-17 -> link ends per segment, uint64, indexed by segment id."""
+        d = np.zeros(max(self.segment_count, 1), np.uint64)
+        _check(_lib.lib().flatgfa_degree(self._h, d.ctypes.data), "degree")
+        return d[:self.segment_count]
+
+    def degree_table(self) -> bytes:
+        """The bytes `fgfa degree` prints."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(_lib.lib().flatgfa_degree_table(self._h, ctypes.byref(p), ctypes.byref(n)), "degree")
+        return _take_text(p, n)
+
+
+MISSING_LINK_DT = np.dtype([("path", "<u4"), ("step", "<u4"), ("src", "<u4"), ("dst", "<u4")])  # flatgfa_missing_link_t
 
 SHARD_WHOLE_PATHS = 1  # FLATGFA_SHARD_WHOLE_PATHS
 SHARD_NO_RCCL = 2      # FLATGFA_SHARD_NO_RCCL
