@@ -28,6 +28,7 @@
 #include "../../include/flatgfa.h"
 #include "chop_device.hpp"
 #include "device_common.hpp"
+#include "device_scan.hpp"
 #include "prof.hpp"
 
 namespace fgfa_dev {
@@ -44,44 +45,6 @@ constexpr uint32_t kRMax = kOutTile / kTile + 2;  // source tiles that can cover
 constexpr uint32_t kNonTiling = 1, kBadSpan = 2, kBadStep = 4, kBadLink = 8;
 
 __device__ __forceinline__ uint64_t pieces(uint32_t len, uint64_t c) { return len <= c ? 1u : ((uint64_t)len - 1) / c + 1; }
-
-__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {
-    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int d) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v += shfl_xor_u64(v, d);
-    return v;
-}
-
-// Exclusive scan over the workgroup's 256 lanes; *total = the sum.  Contains barriers: every lane calls it.
-template <class T>
-__device__ __forceinline__ T block_excl_scan(T v, T *total) {
-    __shared__ T wsum[kThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T u = (T)shfl_up_u64((uint64_t)incl, d);
-        if (lane >= d) incl += u;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) {
-        if (w < wave) before += wsum[w];
-        all += wsum[w];
-    }
-    __syncthreads();  // (wsum is reused by the next call)
-    *total = all;
-    return before + incl - v;
-}
 
 // ---- piece counts ----
 struct SegCount {
@@ -147,7 +110,7 @@ __global__ __launch_bounds__(kThreads) void k_reduce(Src src, uint64_t n, uint64
         const uint32_t i = b + threadIdx.x;
         const uint64_t v = i < n_wg ? __hip_atomic_load(wg + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
         uint64_t tot;
-        const uint64_t ex = block_excl_scan<uint64_t>(v, &tot);
+        const uint64_t ex = block_excl_scan<uint64_t, kThreads>(v, &tot);
         if (i < n_wg) wg[i] = carry + ex;
         carry += tot;
     }
@@ -174,7 +137,7 @@ __global__ __launch_bounds__(kThreads) void k_offsets(Src src, uint64_t n, const
     const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
     const uint64_t cnt = i < n ? src(i) : 0;
     uint64_t tot;
-    const uint64_t ex = block_excl_scan<uint64_t>(cnt, &tot);
+    const uint64_t ex = block_excl_scan<uint64_t, kThreads>(cnt, &tot);
     if (i < n) wr(i, n, prefix[blockIdx.x] + ex, cnt);
 }
 struct SegFirstWriter {
@@ -277,7 +240,7 @@ __global__ __launch_bounds__(kThreads) void k_expand(Load ld, Emit em, uint64_t 
         uint32_t cnt = 0, a = 0, b = 0;
         if (i < n) ld(i, &cnt, &a, &b);
         uint32_t tot;
-        const uint32_t ex = block_excl_scan<uint32_t>(cnt, &tot);
+        const uint32_t ex = block_excl_scan<uint32_t, kThreads>(cnt, &tot);
         off[r * kTile + threadIdx.x] = (uint32_t)prefix[t0 + r] + ex;
         pa[r * kTile + threadIdx.x] = a;
         pb[r * kTile + threadIdx.x] = b;
@@ -329,12 +292,6 @@ __global__ __launch_bounds__(kThreads) void k_check_spans(const uint32_t *__rest
     if (b > e || e > n_steps) f |= kBadSpan;
     if (b != (p ? pe[p - 1] : 0u) || (p == n_paths - 1 && e != n_steps)) f |= kNonTiling;
     if (f) atomicOr(flags, f);
-}
-
-__global__ __launch_bounds__(kThreads) void k_check_links(const uint32_t *__restrict__ links, uint64_t n_links, uint32_t n_segs, uint32_t *flags) {
-    const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n_links) return;
-    if ((links[i * 4] >> 1) >= n_segs || (links[i * 4 + 1] >> 1) >= n_segs) atomicOr(flags, kBadLink);
 }
 
 // a span clamped into the pool (a bad one was reported by k_check_spans)
@@ -410,7 +367,7 @@ __global__ __launch_bounds__(kThreads) void k_expand_paths(const uint32_t *__res
             uint32_t cnt = 0, h = 0, base = 0;
             if (i < e) StepLoad{steps, seg_first, n_segs}(i, &cnt, &h, &base);
             uint32_t tot;
-            const uint32_t ex = block_excl_scan<uint32_t>(cnt, &tot);
+            const uint32_t ex = block_excl_scan<uint32_t, kThreads>(cnt, &tot);
             off[threadIdx.x] = ex;
             pa[threadIdx.x] = h;
             pbase[threadIdx.x] = base;
@@ -486,8 +443,6 @@ struct ScanBuf {
     }
 };
 
-inline uint32_t blocks(uint64_t n, uint64_t per) { return (uint32_t)((n + per - 1) / per); }
-
 template <class Src>
 void launch_reduce(const ScanBuf &sb, Src src, uint64_t *total_out, hipStream_t st, const char *name) {
     if (!sb.n) return;  // (the total stays 0 from the memset)
@@ -496,11 +451,11 @@ void launch_reduce(const ScanBuf &sb, Src src, uint64_t *total_out, hipStream_t 
 }
 void launch_prefix(const ScanBuf &sb, hipStream_t st) {
     if (!sb.n) return;  // (prefix[0] = 0 from the memset)
-    hipLaunchKernelGGL(k_prefix, dim3(blocks(sb.n_tiles, kThreads)), dim3(kThreads), 0, st, sb.tile_sum, sb.wg, sb.n_tiles, sb.n_wg, sb.prefix);
+    hipLaunchKernelGGL(k_prefix, dim3((uint32_t)blocks(sb.n_tiles, kThreads)), dim3(kThreads), 0, st, sb.tile_sum, sb.wg, sb.n_tiles, sb.n_wg, sb.prefix);
 }
 void launch_map(const ScanBuf &sb, hipStream_t st) {
     if (!sb.n_out_tiles) return;
-    hipLaunchKernelGGL(k_map, dim3(blocks(sb.n_out_tiles, kThreads)), dim3(kThreads), 0, st, sb.prefix, sb.n_tiles, sb.n_out_tiles, sb.map);
+    hipLaunchKernelGGL(k_map, dim3((uint32_t)blocks(sb.n_out_tiles, kThreads)), dim3(kThreads), 0, st, sb.prefix, sb.n_tiles, sb.n_out_tiles, sb.map);
 }
 
 }  // namespace
@@ -528,14 +483,7 @@ ChopJob *chop_new() { return new ChopJob(); }
 void chop_free(ChopJob *j) { delete j; }
 const ChopIn &chop_input(const ChopJob *j) { return j->in; }
 
-#define CHOP_HIP(expr)                                                                   \
-    do {                                                                                 \
-        hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess) {                                                          \
-            set_error(std::string("chop: ") + #expr + ": " + hipGetErrorString(_e));     \
-            return FLATGFA_ERR_HIP;                                                      \
-        }                                                                                \
-    } while (0)
+#define CHOP_HIP(expr) FGFA_HIP("chop: ", expr)
 
 int chop_count(ChopJob *j, const ChopIn &in, uint64_t c, bool links, uint32_t *seg_first, hipStream_t st, uint64_t *n_new_segs,
                uint64_t *n_new_steps, uint64_t *n_new_links) {
@@ -566,10 +514,11 @@ int chop_count(ChopJob *j, const ChopIn &in, uint64_t c, bool links, uint32_t *s
     uint32_t *flags = reinterpret_cast<uint32_t *>(j->hdr);
     if (in.n_paths == 0) CHOP_HIP(hipMemsetAsync(flags, kNonTiling, 1, st));  // (no path: the pool is not walked)
     if (in.n_paths)
-        hipLaunchKernelGGL(k_check_spans, dim3(blocks(in.n_paths, kThreads)), dim3(kThreads), 0, st, in.path_begin, in.path_end, in.n_paths,
+        hipLaunchKernelGGL(k_check_spans, dim3((uint32_t)blocks(in.n_paths, kThreads)), dim3(kThreads), 0, st, in.path_begin, in.path_end, in.n_paths,
                            in.n_steps, flags);
     if (links && in.n_links)
-        hipLaunchKernelGGL(k_check_links, dim3(blocks(in.n_links, kThreads)), dim3(kThreads), 0, st, in.links, in.n_links, in.n_segs, flags);
+        hipLaunchKernelGGL(k_check_links<kThreads>, dim3((uint32_t)blocks(in.n_links, kThreads)), dim3(kThreads), 0, st, in.links, in.n_links, in.n_segs,
+                           flags, kBadLink);
     launch_reduce(j->seg, SegCount{in.seg_len, c}, j->hdr + 1, st, "k_chop_reduce_segs");
     launch_reduce(j->step, StepCount{in.steps, in.seg_len, in.n_segs, c, flags}, j->hdr + 2, st, "k_chop_reduce_steps");
     if (in.n_paths) {
@@ -638,7 +587,7 @@ int chop_fill(ChopJob *j, const ChopOut &out, hipStream_t st) {
                                j->N2, out.steps);
         }
         if (in.n_paths)
-            hipLaunchKernelGGL(k_path_spans, dim3(blocks(in.n_paths, kThreads / 64)), dim3(kThreads), 0, st, in.steps, in.path_begin, in.path_end,
+            hipLaunchKernelGGL(k_path_spans, dim3((uint32_t)blocks(in.n_paths, kThreads / 64)), dim3(kThreads), 0, st, in.steps, in.path_begin, in.path_end,
                                in.n_paths, in.n_steps, j->seg_first, in.n_segs, j->step.prefix, out.path_begin, out.path_end);
     } else if (in.n_paths) {
         launch_prefix(j->path, st);
@@ -656,7 +605,7 @@ int chop_fill(ChopJob *j, const ChopOut &out, hipStream_t st) {
                            j->seg.prefix, j->seg.n_tiles, j->seg.map, j->S2, out.seg_len);
     }
     if (j->links && in.n_links)
-        hipLaunchKernelGGL(k_links, dim3(blocks(in.n_links, kThreads)), dim3(kThreads), 0, st, in.links, in.n_links, j->seg_first, in.n_segs,
+        hipLaunchKernelGGL(k_links, dim3((uint32_t)blocks(in.n_links, kThreads)), dim3(kThreads), 0, st, in.links, in.n_links, j->seg_first, in.n_segs,
                            out.links + (j->S2 - in.n_segs) * 4);
     CHOP_HIP(hipGetLastError());
     return FLATGFA_OK;

@@ -5,9 +5,9 @@
 //                 first offer to a segment also appends it to the level's candidate list.  The candidates come back with their
 //                 keys, are ordered by key (the order in which the reference's LIFO walk meets them) and committed with their
 //                 new ids and their ranks for the next level.
-//   k_scan        the one scan all the rest is built from: a tile of 1024 elements per workgroup, a pair of 64-bit sums and a
-//                 head flag per element (a head restarts the sums: the segmented scan), in three launches -- the tiles'
-//                 aggregates, one workgroup over the aggregates, the tiles again with their prefixes.  PosOp: base positions of
+//   k_scan        (device_scan.hpp) the one scan all the rest is built from: a tile of 1024 elements per workgroup, a pair of
+//                 64-bit sums and a head flag per element (SV; a head restarts the sums: the segmented scan), in three launches
+//                 -- the tiles' aggregates, k_spine over the aggregates, the tiles again with their prefixes.  PosOp: base positions of
 //                 the steps per path.  StepOp: member steps and run starts, writing the translated steps and one record per
 //                 subpath.  LinkOp: kept links and their alignment ops, writing the translated links.
 //   k_gather      variable-length copies by output tile (sequences, optional data, alignment ops, paths laid out one behind another):
@@ -20,6 +20,7 @@
 
 #include "../../include/flatgfa.h"
 #include "device_common.hpp"
+#include "device_scan.hpp"
 #include "extract_device.hpp"
 #include "host_copy.hpp"
 
@@ -29,6 +30,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr uint32_t kPer = 4;  // consecutive elements per lane
 constexpr uint32_t kTile = kThreads * kPer;
+constexpr uint32_t kMaxGrid = 256 * 8;  // workgroups of a grid-stride launch
 constexpr uint32_t kGatherPer = 16;
 constexpr uint32_t kGatherTile = kThreads * kGatherPer;
 constexpr uint32_t kNoRank = 0xFFFFFFFFu;
@@ -40,67 +42,20 @@ constexpr uint32_t kBadStep = 1, kBadLink = 2, kBadSpan = 4;
 struct U2 {
     uint64_t a, b;
 };
-struct SV {  // a scan value: two sums, and whether a head lies in the stretch they cover
+struct SV {  // a scan value (device_scan.hpp): two sums, and whether a head lies in the stretch they cover
+    using Carry = U2;
+    using Wide = SV;
     U2 v;
     uint32_t f;
+    __device__ __forceinline__ static SV zero() { return SV{{0, 0}, 0u}; }
+    __device__ __forceinline__ static SV comb(const SV &x, const SV &y) {
+        if (y.f) return SV{y.v, 1u};
+        return SV{{x.v.a + y.v.a, x.v.b + y.v.b}, x.f};
+    }
+    __device__ __forceinline__ U2 carry() const { return v; }
+    __device__ __forceinline__ static SV widen(const SV &x) { return x; }
+    __device__ __forceinline__ static SV after(const U2 &c) { return SV{c, 0u}; }
 };
-__device__ __forceinline__ SV zero_sv() { return SV{{0, 0}, 0u}; }
-__device__ __forceinline__ SV comb(const SV &x, const SV &y) {
-    if (y.f) return SV{y.v, 1u};
-    return SV{{x.v.a + y.v.a, x.v.b + y.v.b}, x.f};
-}
-
-// Inclusive scan of one value per lane over the workgroup, left in sh.  Contains barriers: every lane calls it.
-__device__ __forceinline__ void block_scan(SV *sh, SV mine) {
-    const uint32_t t = threadIdx.x;
-    sh[t] = mine;
-    __syncthreads();
-    for (uint32_t d = 1; d < kThreads; d <<= 1) {
-        SV x = sh[t];
-        if (t >= d) x = comb(sh[t - d], x);
-        __syncthreads();
-        sh[t] = x;
-        __syncthreads();
-    }
-}
-
-template <class Op, bool kApply>
-__global__ __launch_bounds__(kThreads) void k_scan(Op op, uint64_t n, SV *__restrict__ aggr, const U2 *__restrict__ prefix) {
-    __shared__ SV sh[kThreads];
-    const uint64_t base = (uint64_t)blockIdx.x * kTile + (uint64_t)threadIdx.x * kPer;
-    SV item[kPer];
-    SV acc = zero_sv();
-#pragma unroll
-    for (uint32_t q = 0; q < kPer; ++q) {
-        item[q] = base + q < n ? op.load(base + q) : zero_sv();
-        acc = comb(acc, item[q]);
-    }
-    block_scan(sh, acc);
-    if (!kApply) {
-        if (threadIdx.x == kThreads - 1) aggr[blockIdx.x] = sh[kThreads - 1];
-        return;
-    }
-    SV run = comb(SV{prefix[blockIdx.x], 0u}, threadIdx.x ? sh[threadIdx.x - 1] : zero_sv());
-#pragma unroll
-    for (uint32_t q = 0; q < kPer; ++q) {
-        if (base + q < n) op.store(base + q, run.v, item[q]);
-        run = comb(run, item[q]);
-    }
-}
-
-// One workgroup: the exclusive scan of the tiles' aggregates, and the total.
-__global__ __launch_bounds__(kThreads) void k_spine(const SV *__restrict__ aggr, uint64_t n_tiles, U2 *__restrict__ prefix, U2 *total) {
-    __shared__ SV sh[kThreads];
-    SV carry = zero_sv();
-    for (uint64_t b = 0; b < n_tiles; b += kThreads) {
-        const uint64_t i = b + threadIdx.x;
-        block_scan(sh, i < n_tiles ? aggr[i] : zero_sv());
-        if (i < n_tiles) prefix[i] = comb(carry, threadIdx.x ? sh[threadIdx.x - 1] : zero_sv()).v;
-        carry = comb(carry, sh[kThreads - 1]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry.v;
-}
 
 __device__ __forceinline__ bool head_at(const uint32_t *heads, uint64_t i) { return (heads[i >> 5] >> (i & 31)) & 1u; }
 
@@ -139,14 +94,8 @@ struct StepOp {
         const uint32_t h = steps[i], s = h >> 1;
         out_steps[before.a] = ((state[s] - 1) << 1) | (h & 1u);  // tr_handle, extract.rs:137-140
         if (me.v.b) {
-            uint32_t lo = 0, hi = n_paths;  // the last path that starts at or before step i: the one that holds it
-            while (hi - lo > 1) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                if (pstart[mid] <= i) lo = mid;
-                else hi = mid;
-            }
             SubpathRec &r = recs[before.b];
-            r.path = lo;
+            r.path = last_start_at_or_before(pstart, 0, n_paths - 1, i);  // (n_steps = pstart[n_paths]: where there is a step there is a path)
             r.start = pos[i];
             r.step_begin = before.a;
         }
@@ -166,7 +115,7 @@ struct LinkOp {
     uint32_t *out_links, *al_src, *al_dst;
     __device__ SV load(uint64_t i) const {
         const uint32_t *l = links + i * 4;
-        if (!state[l[0] >> 1] || !state[l[1] >> 1]) return zero_sv();
+        if (!state[l[0] >> 1] || !state[l[1] >> 1]) return SV::zero();
         if (l[2] > l[3] || l[3] > n_align) {
             atomicOr(flags, kBadSpan);
             return SV{{1, 0}, 0u};
@@ -191,12 +140,6 @@ __global__ __launch_bounds__(kThreads) void k_heads(const uint32_t *__restrict__
     if (p >= n_paths) return;
     const uint32_t b = pstart[p];
     if (b < pstart[p + 1]) atomicOr(heads + (b >> 5), 1u << (b & 31));
-}
-
-__global__ __launch_bounds__(kThreads) void k_check_links(const uint32_t *__restrict__ links, uint64_t n_links, uint32_t n_segs, uint32_t *flags) {
-    const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n_links) return;
-    if ((links[i * 4] >> 1) >= n_segs || (links[i * 4 + 1] >> 1) >= n_segs) atomicOr(flags, kBadLink);
 }
 
 // Link::incident_seg (flatgfa.rs:137-145) for every frontier segment at once.  A self-loop offers nothing.
@@ -282,69 +225,22 @@ __global__ __launch_bounds__(kThreads) void k_find_pos(const uint64_t *__restric
     }
 }
 
-inline uint32_t blocks(uint64_t n, uint64_t per) { return (uint32_t)((n + per - 1) / per); }
-inline uint32_t stride_blocks(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(blocks(n, kThreads), 1), 256 * 8); }
-
 }  // namespace
 
-#define EX_HIP(expr)                                                                    \
-    do {                                                                                \
-        hipError_t _e = (expr);                                                         \
-        if (_e != hipSuccess) {                                                         \
-            set_error(std::string("extract: ") + #expr + ": " + hipGetErrorString(_e)); \
-            return FLATGFA_ERR_HIP;                                                     \
-        }                                                                               \
-    } while (0)
-
-namespace {
-// the three launches of one scan; the spine's scratch must hold blocks(n, kTile) tiles
-struct Spine {
-    SV *aggr = nullptr;
-    U2 *prefix = nullptr, *total = nullptr;
-};
-template <class Op>
-void scan_count(const Op &op, uint64_t n, const Spine &sp, hipStream_t st) {
-    const uint32_t tiles = blocks(n, kTile);
-    if (tiles) hipLaunchKernelGGL((k_scan<Op, false>), dim3(tiles), dim3(kThreads), 0, st, op, n, sp.aggr, sp.prefix);
-    hipLaunchKernelGGL(k_spine, dim3(1), dim3(kThreads), 0, st, sp.aggr, (uint64_t)tiles, sp.prefix, sp.total);
-}
-template <class Op>
-void scan_apply(const Op &op, uint64_t n, const Spine &sp, hipStream_t st) {
-    const uint32_t tiles = blocks(n, kTile);
-    if (tiles) hipLaunchKernelGGL((k_scan<Op, true>), dim3(tiles), dim3(kThreads), 0, st, op, n, sp.aggr, sp.prefix);
-}
-}  // namespace
+#define EX_HIP(expr) FGFA_HIP("extract: ", expr)
 
 struct ExtractJob {
     ExtractGraph g;
     hipStream_t st = nullptr;
-    std::vector<void *> mem;
+    DeviceMem mem;
     uint32_t *state = nullptr, *rank = nullptr, *cand = nullptr, *list[2] = {nullptr, nullptr}, *heads = nullptr, *words = nullptr;
     unsigned long long *key = nullptr;
     U2 *pairs = nullptr;
     uint64_t *pos = nullptr;
-    Spine step_sp, link_sp;
+    Spine<SV> step_sp, link_sp;
     uint32_t *al_src = nullptr, *al_dst = nullptr;
     ExtractTotals tot;
     bool counted = false;
-    ~ExtractJob() {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *p : mem) (void)hipFree(p);
-    }
-    template <class T>
-    hipError_t alloc(T **p, uint64_t count) {
-        *p = nullptr;
-        const hipError_t e = hipMalloc((void **)p, std::max<uint64_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) mem.push_back(*p);
-        return e;
-    }
-    hipError_t alloc_spine(Spine *sp, uint64_t n) {
-        const uint64_t tiles = blocks(n, kTile);
-        hipError_t e = alloc(&sp->aggr, tiles);
-        if (e == hipSuccess) e = alloc(&sp->prefix, tiles + 1);
-        sp->total = sp->prefix ? sp->prefix + tiles : nullptr;
-        return e;
-    }
     int flags_error(uint32_t *f) {
         EX_HIP(staged_copy(f, words, 4, hipMemcpyDeviceToHost, st));
         return FLATGFA_OK;
@@ -360,27 +256,28 @@ int extract_begin(ExtractJob *j, const ExtractGraph &g, hipStream_t st) {
         return FLATGFA_ERR_TOO_LARGE;
     }
     j->g = g;
-    j->st = st;
+    j->st = j->mem.st = st;
     const uint64_t S = g.n_segs, N = g.n_steps;
-    EX_HIP(j->alloc(&j->state, S));
-    EX_HIP(j->alloc(&j->rank, S));
-    EX_HIP(j->alloc(&j->key, S));
-    EX_HIP(j->alloc(&j->cand, S));
-    EX_HIP(j->alloc(&j->list[0], S));
-    EX_HIP(j->alloc(&j->list[1], S));
-    EX_HIP(j->alloc(&j->pairs, S));
-    EX_HIP(j->alloc(&j->heads, N / 32 + 2));
-    EX_HIP(j->alloc(&j->pos, N));
-    EX_HIP(j->alloc(&j->words, 4));
-    EX_HIP(j->alloc_spine(&j->step_sp, N));
-    EX_HIP(j->alloc_spine(&j->link_sp, g.n_links));
+    EX_HIP(j->mem.alloc(&j->state, S));
+    EX_HIP(j->mem.alloc(&j->rank, S));
+    EX_HIP(j->mem.alloc(&j->key, S));
+    EX_HIP(j->mem.alloc(&j->cand, S));
+    EX_HIP(j->mem.alloc(&j->list[0], S));
+    EX_HIP(j->mem.alloc(&j->list[1], S));
+    EX_HIP(j->mem.alloc(&j->pairs, S));
+    EX_HIP(j->mem.alloc(&j->heads, N / 32 + 2));
+    EX_HIP(j->mem.alloc(&j->pos, N));
+    EX_HIP(j->mem.alloc(&j->words, 4));
+    EX_HIP(j->step_sp.alloc(&j->mem, blocks(N, kTile)));
+    EX_HIP(j->link_sp.alloc(&j->mem, blocks(g.n_links, kTile)));
     EX_HIP(hipMemsetAsync(j->state, 0, std::max<uint64_t>(S, 1) * 4, st));
     EX_HIP(hipMemsetAsync(j->rank, 0xFF, std::max<uint64_t>(S, 1) * 4, st));
     EX_HIP(hipMemsetAsync(j->key, 0xFF, std::max<uint64_t>(S, 1) * 8, st));
     EX_HIP(hipMemsetAsync(j->heads, 0, (N / 32 + 2) * 4, st));
     EX_HIP(hipMemsetAsync(j->words, 0, 16, st));
     if (g.n_links) {
-        hipLaunchKernelGGL(k_check_links, dim3(blocks(g.n_links, kThreads)), dim3(kThreads), 0, st, g.links, g.n_links, g.n_segs, j->words);
+        hipLaunchKernelGGL(k_check_links<kThreads>, dim3((uint32_t)blocks(g.n_links, kThreads)), dim3(kThreads), 0, st, g.links, g.n_links, g.n_segs,
+                           j->words, kBadLink);
         EX_HIP(hipGetLastError());
         uint32_t f = 0;
         if (int rc = j->flags_error(&f)) return rc;
@@ -395,7 +292,7 @@ int extract_add(ExtractJob *j, const uint32_t *segs, uint64_t n, uint64_t base) 
     EX_HIP(hipMalloc((void **)&d, n * 4));
     hipError_t e = staged_copy(d, segs, n * 4, hipMemcpyHostToDevice, j->st);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_commit, dim3(blocks(n, kThreads)), dim3(kThreads), 0, j->st, d, n, base, j->state, j->rank, false);
+        hipLaunchKernelGGL(k_commit, dim3((uint32_t)blocks(n, kThreads)), dim3(kThreads), 0, j->st, d, n, base, j->state, j->rank, false);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(j->st);
     }
@@ -418,14 +315,14 @@ int extract_bfs(ExtractJob *j, uint32_t origin, uint64_t dist, std::vector<uint3
     std::vector<uint32_t> next;
     for (uint64_t lvl = 0; lvl < dist && n_front && g.n_links; ++lvl) {
         EX_HIP(hipMemsetAsync(count, 0, 4, st));
-        hipLaunchKernelGGL(k_bfs_level, dim3(stride_blocks(g.n_links)), dim3(kThreads), 0, st, g.links, g.n_links, j->state, j->rank, j->key,
+        hipLaunchKernelGGL(k_bfs_level, dim3(stride_blocks(g.n_links, kThreads, kMaxGrid)), dim3(kThreads), 0, st, g.links, g.n_links, j->state, j->rank, j->key,
                            j->cand, count);
-        hipLaunchKernelGGL(k_clear_rank, dim3(blocks(n_front, kThreads)), dim3(kThreads), 0, st, j->list[cur], n_front, j->rank);
+        hipLaunchKernelGGL(k_clear_rank, dim3((uint32_t)blocks(n_front, kThreads)), dim3(kThreads), 0, st, j->list[cur], n_front, j->rank);
         EX_HIP(hipGetLastError());
         uint32_t c = 0;
         EX_HIP(staged_copy(&c, count, 4, hipMemcpyDeviceToHost, st));
         if (!c) break;  // (nothing new: every later level finds an empty frontier)
-        hipLaunchKernelGGL(k_collect, dim3(blocks(c, kThreads)), dim3(kThreads), 0, st, j->cand, c, j->key, j->pairs);
+        hipLaunchKernelGGL(k_collect, dim3((uint32_t)blocks(c, kThreads)), dim3(kThreads), 0, st, j->cand, c, j->key, j->pairs);
         EX_HIP(hipGetLastError());
         pairs.resize(c);
         EX_HIP(staged_copy(pairs.data(), j->pairs, (size_t)c * sizeof(U2), hipMemcpyDeviceToHost, st));
@@ -434,7 +331,7 @@ int extract_bfs(ExtractJob *j, uint32_t origin, uint64_t dist, std::vector<uint3
         for (uint32_t k = 0; k < c; ++k) next[k] = (uint32_t)pairs[k].b;
         cur ^= 1;
         EX_HIP(staged_copy(j->list[cur], next.data(), (size_t)c * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_commit, dim3(blocks(c, kThreads)), dim3(kThreads), 0, st, j->list[cur], (uint64_t)c, (uint64_t)order->size(),
+        hipLaunchKernelGGL(k_commit, dim3((uint32_t)blocks(c, kThreads)), dim3(kThreads), 0, st, j->list[cur], (uint64_t)c, (uint64_t)order->size(),
                            j->state, j->rank, true);
         order->insert(order->end(), next.begin(), next.end());
         n_front = c;
@@ -446,10 +343,10 @@ int extract_bfs(ExtractJob *j, uint32_t origin, uint64_t dist, std::vector<uint3
 int extract_positions(ExtractJob *j) {
     const ExtractGraph &g = j->g;
     hipStream_t st = j->st;
-    if (g.n_paths) hipLaunchKernelGGL(k_heads, dim3(blocks(g.n_paths, kThreads)), dim3(kThreads), 0, st, g.pstart, g.n_paths, j->heads);
+    if (g.n_paths) hipLaunchKernelGGL(k_heads, dim3((uint32_t)blocks(g.n_paths, kThreads)), dim3(kThreads), 0, st, g.pstart, g.n_paths, j->heads);
     const PosOp op{g.steps, j->heads, g.seg_seq, g.n_segs, j->words, j->pos};
-    scan_count(op, g.n_steps, j->step_sp, st);
-    scan_apply(op, g.n_steps, j->step_sp, st);
+    scan_count<kThreads, kPer>(op, g.n_steps, j->step_sp, st);
+    scan_apply<kThreads, kPer>(op, g.n_steps, j->step_sp, st);
     EX_HIP(hipGetLastError());
     uint32_t f = 0;
     if (int rc = j->flags_error(&f)) return rc;
@@ -461,8 +358,8 @@ int extract_prefix_lens(ExtractJob *j, uint64_t max_dist, uint32_t *plen) {
     const ExtractGraph &g = j->g;
     if (!g.n_paths) return FLATGFA_OK;
     uint32_t *d = nullptr;
-    EX_HIP(j->alloc(&d, g.n_paths));
-    hipLaunchKernelGGL(k_prefix_len, dim3(blocks(g.n_paths, kThreads)), dim3(kThreads), 0, j->st, j->pos, g.pstart, g.n_paths, max_dist, d);
+    EX_HIP(j->mem.alloc(&d, g.n_paths));
+    hipLaunchKernelGGL(k_prefix_len, dim3((uint32_t)blocks(g.n_paths, kThreads)), dim3(kThreads), 0, j->st, j->pos, g.pstart, g.n_paths, max_dist, d);
     EX_HIP(hipGetLastError());
     EX_HIP(staged_copy(plen, d, (size_t)g.n_paths * 4, hipMemcpyDeviceToHost, j->st));
     return FLATGFA_OK;
@@ -473,8 +370,8 @@ int extract_count(ExtractJob *j, ExtractTotals *t) {
     hipStream_t st = j->st;
     const StepOp sop{g.steps, j->heads, j->state, g.seg_seq, g.pstart, j->pos, g.n_paths, g.n_steps, nullptr, nullptr};
     const LinkOp lop{g.links, j->state, g.n_align, j->words, nullptr, nullptr, nullptr};
-    scan_count(sop, g.n_steps, j->step_sp, st);
-    scan_count(lop, g.n_links, j->link_sp, st);
+    scan_count<kThreads, kPer>(sop, g.n_steps, j->step_sp, st);
+    scan_count<kThreads, kPer>(lop, g.n_links, j->link_sp, st);
     EX_HIP(hipGetLastError());
     U2 a, b;
     uint32_t f = 0;
@@ -503,15 +400,15 @@ int extract_fill(ExtractJob *j, const ExtractOut &out) {
     }
     if (t.steps) {
         const StepOp sop{g.steps, j->heads, j->state, g.seg_seq, g.pstart, j->pos, g.n_paths, g.n_steps, out.steps, out.recs};
-        scan_apply(sop, g.n_steps, j->step_sp, st);
+        scan_apply<kThreads, kPer>(sop, g.n_steps, j->step_sp, st);
     }
     if (t.links) {
-        EX_HIP(j->alloc(&j->al_src, t.links));
-        EX_HIP(j->alloc(&j->al_dst, t.links));
+        EX_HIP(j->mem.alloc(&j->al_src, t.links));
+        EX_HIP(j->mem.alloc(&j->al_dst, t.links));
         const LinkOp lop{g.links, j->state, g.n_align, j->words, out.links, j->al_src, j->al_dst};
-        scan_apply(lop, g.n_links, j->link_sp, st);
+        scan_apply<kThreads, kPer>(lop, g.n_links, j->link_sp, st);
         if (t.ops)
-            hipLaunchKernelGGL(k_gather<uint32_t>, dim3(blocks(t.ops, kGatherTile)), dim3(kThreads), 0, st, out.align_src, g.n_align, j->al_src,
+            hipLaunchKernelGGL(k_gather<uint32_t>, dim3((uint32_t)blocks(t.ops, kGatherTile)), dim3(kThreads), 0, st, out.align_src, g.n_align, j->al_src,
                                j->al_dst, t.links, t.ops, out.align);
     }
     EX_HIP(hipGetLastError());
@@ -521,7 +418,7 @@ int extract_fill(ExtractJob *j, const ExtractOut &out) {
 int gather_bytes(const uint8_t *src, uint64_t src_len, const uint32_t *src_start, const uint32_t *dst_off, uint64_t n, uint64_t total,
                  uint8_t *dst, hipStream_t st) {
     if (!total || !n) return FLATGFA_OK;
-    hipLaunchKernelGGL(k_gather<uint8_t>, dim3(blocks(total, kGatherTile)), dim3(kThreads), 0, st, src, src_len, src_start, dst_off, n, total, dst);
+    hipLaunchKernelGGL(k_gather<uint8_t>, dim3((uint32_t)blocks(total, kGatherTile)), dim3(kThreads), 0, st, src, src_len, src_start, dst_off, n, total, dst);
     EX_HIP(hipGetLastError());
     return FLATGFA_OK;
 }
@@ -529,7 +426,7 @@ int gather_bytes(const uint8_t *src, uint64_t src_len, const uint32_t *src_start
 int gather_u32(const uint32_t *src, uint64_t src_len, const uint32_t *src_start, const uint32_t *dst_off, uint64_t n, uint64_t total,
                uint32_t *dst, hipStream_t st) {
     if (!total || !n) return FLATGFA_OK;
-    hipLaunchKernelGGL(k_gather<uint32_t>, dim3(blocks(total, kGatherTile)), dim3(kThreads), 0, st, src, src_len, src_start, dst_off, n, total, dst);
+    hipLaunchKernelGGL(k_gather<uint32_t>, dim3((uint32_t)blocks(total, kGatherTile)), dim3(kThreads), 0, st, src, src_len, src_start, dst_off, n, total, dst);
     EX_HIP(hipGetLastError());
     return FLATGFA_OK;
 }
@@ -539,22 +436,22 @@ int position_find(const uint32_t *steps, uint64_t n, const uint32_t *seg_seq, ui
     *index = n;
     *step_start = 0;
     if (!n) return FLATGFA_OK;
-    ExtractJob job;  // (its allocations, freed on every way out)
-    job.st = st;
+    DeviceMem mem;
+    mem.st = st;
     uint64_t *pos = nullptr;
     unsigned long long *res = nullptr;
     uint32_t *flags = nullptr;
-    Spine sp;
-    EX_HIP(job.alloc(&pos, n));
-    EX_HIP(job.alloc(&res, 1));
-    EX_HIP(job.alloc(&flags, 1));
-    EX_HIP(job.alloc_spine(&sp, n));
+    Spine<SV> sp;
+    EX_HIP(mem.alloc(&pos, n));
+    EX_HIP(mem.alloc(&res, 1));
+    EX_HIP(mem.alloc(&flags, 1));
+    EX_HIP(sp.alloc(&mem, blocks(n, kTile)));
     EX_HIP(hipMemsetAsync(res, 0xFF, 8, st));
     EX_HIP(hipMemsetAsync(flags, 0, 4, st));
     const PosOp op{steps, nullptr, seg_seq, n_segs, flags, pos};
-    scan_count(op, n, sp, st);
-    scan_apply(op, n, sp, st);
-    hipLaunchKernelGGL(k_find_pos, dim3(stride_blocks(n)), dim3(kThreads), 0, st, pos, steps, seg_seq, n_segs, n, offset, res);
+    scan_count<kThreads, kPer>(op, n, sp, st);
+    scan_apply<kThreads, kPer>(op, n, sp, st);
+    hipLaunchKernelGGL(k_find_pos, dim3(stride_blocks(n, kThreads, kMaxGrid)), dim3(kThreads), 0, st, pos, steps, seg_seq, n_segs, n, offset, res);
     EX_HIP(hipGetLastError());
     uint32_t f = 0;
     unsigned long long r = 0;

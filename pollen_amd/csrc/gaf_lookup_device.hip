@@ -36,6 +36,7 @@
 
 #include "../../include/flatgfa.h"
 #include "device_common.hpp"
+#include "device_scan.hpp"
 #include "gaf_lookup_device.hpp"
 #include "prof.hpp"
 
@@ -58,41 +59,6 @@ __device__ __forceinline__ uint32_t eq_bytes(uint32_t w, uint32_t c) {
     return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;
 }
 
-__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {
-    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t u = shfl_up_u64(v, d);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-
-// Exclusive scan over the workgroup's 256 lanes; *total = the sum.  Contains barriers: every lane calls it.
-__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t *total) {
-    __shared__ uint64_t wsum[kThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t incl = wave_incl_scan(v, lane);
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) {
-        if (w < wave) before += wsum[w];
-        all += wsum[w];
-    }
-    __syncthreads();  // (wsum is reused by the next call)
-    *total = all;
-    return before + incl - v;
-}
-
 // ---- scans (u64, exclusive, in place) ----
 
 __global__ __launch_bounds__(kThreads) void k_lk_scan_local(uint64_t *__restrict__ a, uint64_t n, uint64_t *__restrict__ block_sum) {
@@ -104,7 +70,7 @@ __global__ __launch_bounds__(kThreads) void k_lk_scan_local(uint64_t *__restrict
         sum += v[k];
     }
     uint64_t total;
-    uint64_t run = block_excl_scan(sum, &total);
+    uint64_t run = block_excl_scan<uint64_t, kThreads>(sum, &total);
 #pragma unroll
     for (uint32_t k = 0; k < kScanItems; ++k) {
         if (first + k < n) a[first + k] = run;
@@ -169,7 +135,7 @@ __global__ __launch_bounds__(kThreads) void k_lk_nl_count(const uint8_t *__restr
              (uint32_t)__builtin_popcount(eq_bytes(v.z, '\n')) + (uint32_t)__builtin_popcount(eq_bytes(v.w, '\n'));
     }
     uint64_t total;
-    (void)block_excl_scan(c, &total);
+    (void)block_excl_scan<uint64_t, kThreads>(c, &total);
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
 }
 
@@ -185,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void k_lk_nl_scatter(const uint8_t *__res
              (uint32_t)__builtin_popcount(eq_bytes(v[k].z, '\n')) + (uint32_t)__builtin_popcount(eq_bytes(v[k].w, '\n'));
     }
     uint64_t total;
-    uint64_t at = tile_first[blockIdx.x] + block_excl_scan(c, &total);
+    uint64_t at = tile_first[blockIdx.x] + block_excl_scan<uint64_t, kThreads>(c, &total);
     if (!c) return;
 #pragma unroll
     for (uint32_t k = 0; k < kLaneBytes / 16; ++k) {
@@ -549,14 +515,7 @@ void gaf_lookup_free(GafLookupJob *j) {
 }
 const GafArrays &gaf_lookup_arrays(const GafLookupJob *j) { return j->arr; }
 
-#define LK_HIP(expr)                                                          \
-    do {                                                                      \
-        hipError_t _e = (expr);                                               \
-        if (_e != hipSuccess) {                                               \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));     \
-            return FLATGFA_ERR_HIP;                                           \
-        }                                                                     \
-    } while (0)
+#define LK_HIP(expr) FGFA_HIP("", expr)
 
 int gaf_lookup_count(GafLookupJob *j, const uint8_t *d_text, size_t len, const GafGraph &g, bool seqs, uint64_t base,
                      hipStream_t stream, GafTotals *totals) {

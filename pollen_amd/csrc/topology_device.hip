@@ -3,7 +3,8 @@
 //   k_link_count    one pass over the links: the row of every link's canonical key is counted (a link and its reverse
 //                   complement share one key, so a step pair needs one lookup), and so are the two link ends per segment
 //                   (the degree).  A link naming a segment out of range raises a flag bit and is left out.
-//   k_scan_u32      the exclusive scan of the row counts, in place, in three launches (tile sums, k_spine, tiles again).
+//   k_scan          (device_scan.hpp, over RowOp) the exclusive scan of the row counts, in place, in three launches (tile
+//                   sums, k_spine, tiles again).
 //   k_link_scatter  the low half of every key goes into its row, behind a cursor per row.
 //   k_sort_rows     rows longer than kLinear are sorted, one workgroup per row (a bitonic network in which every compare
 //                   points upwards, so the padding to a power of two stays virtual); shorter rows are probed linearly.
@@ -21,6 +22,7 @@
 
 #include "../../include/flatgfa.h"
 #include "device_common.hpp"
+#include "device_scan.hpp"
 #include "host_copy.hpp"
 #include "topology_device.hpp"
 
@@ -41,59 +43,12 @@ __device__ __forceinline__ uint64_t canon(uint32_t from, uint32_t to) {
     return x < y ? x : y;
 }
 
-// Inclusive scan of one value per lane over the workgroup, left in sh.  Contains barriers: every lane calls it.
-template <class T>
-__device__ __forceinline__ void block_scan(T *sh, T mine) {
-    const uint32_t t = threadIdx.x;
-    sh[t] = mine;
-    __syncthreads();
-    for (uint32_t d = 1; d < kThreads; d <<= 1) {
-        T x = sh[t];
-        if (t >= d) x += sh[t - d];
-        __syncthreads();
-        sh[t] = x;
-        __syncthreads();
-    }
-}
-
-// One workgroup: the exclusive scan of the tiles' sums, and the total.
-__global__ __launch_bounds__(kThreads) void k_spine(const uint64_t *__restrict__ aggr, uint64_t n_tiles, uint64_t *__restrict__ prefix,
-                                                    uint64_t *total) {
-    __shared__ uint64_t sh[kThreads];
-    uint64_t carry = 0;
-    for (uint64_t b = 0; b < n_tiles; b += kThreads) {
-        const uint64_t i = b + threadIdx.x;
-        block_scan(sh, i < n_tiles ? aggr[i] : (uint64_t)0);
-        if (i < n_tiles) prefix[i] = carry + (threadIdx.x ? sh[threadIdx.x - 1] : (uint64_t)0);
-        carry += sh[kThreads - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-// data[i] becomes the sum of data[0 .. i): every lane holds its elements in registers before any is written.
-template <bool kApply>
-__global__ __launch_bounds__(kThreads) void k_scan_u32(uint32_t *data, uint64_t n, uint64_t *__restrict__ aggr, const uint64_t *__restrict__ prefix) {
-    __shared__ uint32_t sh[kThreads];
-    const uint64_t base = (uint64_t)blockIdx.x * kTile + (uint64_t)threadIdx.x * kPer;
-    uint32_t item[kPer], acc = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kPer; ++q) {
-        item[q] = base + q < n ? data[base + q] : 0u;
-        acc += item[q];
-    }
-    block_scan(sh, acc);
-    if (!kApply) {
-        if (threadIdx.x == kThreads - 1) aggr[blockIdx.x] = sh[kThreads - 1];
-        return;
-    }
-    uint32_t run = (uint32_t)prefix[blockIdx.x] + (threadIdx.x ? sh[threadIdx.x - 1] : 0u);
-#pragma unroll
-    for (uint32_t q = 0; q < kPer; ++q) {
-        if (base + q < n) data[base + q] = run;
-        run += item[q];
-    }
-}
+// The row scan: data[i] becomes the sum of data[0 .. i), in place (k_scan holds a lane's elements before it stores any).
+struct RowOp {
+    uint32_t *data;
+    __device__ Sum<uint32_t> load(uint64_t i) const { return Sum<uint32_t>{data[i]}; }
+    __device__ void store(uint64_t i, uint32_t before, const Sum<uint32_t> &) const { data[i] = before; }
+};
 
 // preprocess.py:39-41: every link adds one entry to outs[from] and one to ins[to] -- here one key, and two link ends.
 __global__ __launch_bounds__(kThreads) void k_link_count(const uint32_t *__restrict__ links, uint64_t n_links, uint32_t n_segs, uint32_t *row,
@@ -180,31 +135,21 @@ __device__ __forceinline__ bool supported(const IndexView &ix, uint32_t a, uint3
     return lo < ix.row[h + 1] && ix.to[lo] == want;
 }
 
-// the last path of [lo, hi] that starts at or before step j of the paths laid one behind another: the one that holds it
-__device__ __forceinline__ uint32_t path_of(const uint32_t *pstart, uint32_t lo, uint32_t hi, uint64_t j) {
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo + 1) >> 1);
-        if (pstart[mid] <= j) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 template <bool kApply>
-__global__ __launch_bounds__(kThreads) void k_steps(IndexView ix, TopoSteps sp, uint64_t n_tiles, uint64_t *aggr, const uint64_t *__restrict__ prefix,
+__global__ __launch_bounds__(kThreads) void k_steps(IndexView ix, TopoSteps sp, uint64_t n_tiles, Sum<uint64_t> *aggr, const uint64_t *__restrict__ prefix,
                                                     uint4 *__restrict__ recs, uint32_t *flags) {
-    __shared__ uint32_t sh[kThreads];
+    __shared__ Sum<uint32_t> sh[kThreads];
     __shared__ uint32_t ends[2];
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        if (kApply && !aggr[tile]) continue;  // (the same for every lane)
+        if (kApply && !aggr[tile].v) continue;  // (the same for every lane)
         const uint64_t t0 = tile * kTile, t1 = min(t0 + kTile, sp.n_lin);
-        if (threadIdx.x < 2) ends[threadIdx.x] = path_of(sp.pstart, 0, sp.n_paths - 1, threadIdx.x ? t1 - 1 : t0);
+        if (threadIdx.x < 2) ends[threadIdx.x] = last_start_at_or_before(sp.pstart, 0, sp.n_paths - 1, threadIdx.x ? t1 - 1 : t0);
         __syncthreads();
         const uint64_t base = t0 + (uint64_t)threadIdx.x * kPer;
         uint4 rec[kPer];
         uint32_t miss = 0;  // bit q: this lane's step q has an unsupported pair
         if (base < t1) {
-            uint32_t p = path_of(sp.pstart, ends[0], ends[1], base);
+            uint32_t p = last_start_at_or_before(sp.pstart, ends[0], ends[1], base);
             uint64_t ps = sp.pstart[p], pe = sp.pstart[p + 1], pb = sp.pbegin[p];
 #pragma unroll
             for (uint32_t q = 0; q < kPer; ++q) {
@@ -229,11 +174,11 @@ __global__ __launch_bounds__(kThreads) void k_steps(IndexView ix, TopoSteps sp, 
                 }
             }
         }
-        block_scan(sh, (uint32_t)__popc(miss));
+        block_scan<kThreads>(sh, Sum<uint32_t>{(uint32_t)__popc(miss)});
         if (!kApply) {
-            if (threadIdx.x == kThreads - 1) aggr[tile] = sh[kThreads - 1];
+            if (threadIdx.x == kThreads - 1) aggr[tile].v = sh[kThreads - 1].v;
         } else {
-            uint64_t at = prefix[tile] + (threadIdx.x ? sh[threadIdx.x - 1] : 0u);
+            uint64_t at = prefix[tile] + (threadIdx.x ? sh[threadIdx.x - 1].v : 0u);
 #pragma unroll
             for (uint32_t q = 0; q < kPer; ++q)
                 if ((miss >> q) & 1u) recs[at++] = rec[q];
@@ -242,37 +187,9 @@ __global__ __launch_bounds__(kThreads) void k_steps(IndexView ix, TopoSteps sp, 
     }
 }
 
-inline uint64_t blocks(uint64_t n, uint64_t per) { return (n + per - 1) / per; }
-inline uint32_t stride_blocks(uint64_t n, uint64_t per) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(blocks(n, per), 1), kMaxGrid); }
-
-// device allocations given back on every way out
-struct Scratch {
-    std::vector<void *> mem;
-    hipStream_t st = nullptr;
-    ~Scratch() {
-        if (mem.empty()) return;
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *p : mem) (void)hipFree(p);
-    }
-    template <class T>
-    hipError_t alloc(T **p, uint64_t count) {
-        *p = nullptr;
-        const hipError_t e = hipMalloc((void **)p, std::max<uint64_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) mem.push_back(*p);
-        return e;
-    }
-};
-
 }  // namespace
 
-#define TP_HIP(expr)                                                                     \
-    do {                                                                                 \
-        hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess) {                                                          \
-            set_error(std::string("topology: ") + #expr + ": " + hipGetErrorString(_e)); \
-            return FLATGFA_ERR_HIP;                                                      \
-        }                                                                                \
-    } while (0)
+#define TP_HIP(expr) FGFA_HIP("topology: ", expr)
 
 void topo_index_free(TopoIndex *ix) {
     if (ix->mem) (void)hipFree(ix->mem);
@@ -301,26 +218,24 @@ int topo_index_build(const uint32_t *links, uint64_t L, uint32_t S, hipStream_t 
         TopoIndex *ix;
         ~Guard() { if (ix) topo_index_free(ix); }
     } guard{&ix};
-    Scratch sc;
+    DeviceMem sc;
     sc.st = st;
     uint32_t *cursor = nullptr, *list = nullptr, *words4 = nullptr;
-    uint64_t *aggr = nullptr, *prefix = nullptr;
+    Spine<Sum<uint32_t>> rows;
     const uint64_t list_cap = L / (kLinear + 1) + 1;  // (a listed row holds more than kLinear of the L entries)
     TP_HIP(sc.alloc(&cursor, n_rows));
     TP_HIP(sc.alloc(&list, list_cap));
     TP_HIP(sc.alloc(&words4, 4));  // flags, long-row count
-    TP_HIP(sc.alloc(&aggr, tiles));
-    TP_HIP(sc.alloc(&prefix, tiles + 1));
+    TP_HIP(rows.alloc(&sc, tiles));
     TP_HIP(hipMemsetAsync(mem, 0, words * 4, st));
     TP_HIP(hipMemsetAsync(cursor, 0, std::max<uint64_t>(n_rows, 1) * 4, st));
     TP_HIP(hipMemsetAsync(words4, 0, 16, st));
-    if (L) hipLaunchKernelGGL(k_link_count, dim3(stride_blocks(L, kThreads)), dim3(kThreads), 0, st, links, L, S, ix.row, ix.deg, words4);
-    hipLaunchKernelGGL((k_scan_u32<false>), dim3((uint32_t)tiles), dim3(kThreads), 0, st, ix.row, n_scan, aggr, prefix);
-    hipLaunchKernelGGL(k_spine, dim3(1), dim3(kThreads), 0, st, aggr, tiles, prefix, prefix + tiles);
-    hipLaunchKernelGGL((k_scan_u32<true>), dim3((uint32_t)tiles), dim3(kThreads), 0, st, ix.row, n_scan, aggr, prefix);
+    if (L) hipLaunchKernelGGL(k_link_count, dim3(stride_blocks(L, kThreads, kMaxGrid)), dim3(kThreads), 0, st, links, L, S, ix.row, ix.deg, words4);
+    scan_count<kThreads, kPer>(RowOp{ix.row}, n_scan, rows, st);
+    scan_apply<kThreads, kPer>(RowOp{ix.row}, n_scan, rows, st);
     if (L) {
-        hipLaunchKernelGGL(k_link_scatter, dim3(stride_blocks(L, kThreads)), dim3(kThreads), 0, st, links, L, S, ix.row, cursor, ix.to);
-        hipLaunchKernelGGL(k_long_rows, dim3(stride_blocks(n_rows, kThreads)), dim3(kThreads), 0, st, ix.row, n_rows, list, (uint32_t)list_cap,
+        hipLaunchKernelGGL(k_link_scatter, dim3(stride_blocks(L, kThreads, kMaxGrid)), dim3(kThreads), 0, st, links, L, S, ix.row, cursor, ix.to);
+        hipLaunchKernelGGL(k_long_rows, dim3(stride_blocks(n_rows, kThreads, kMaxGrid)), dim3(kThreads), 0, st, ix.row, n_rows, list, (uint32_t)list_cap,
                            words4 + 1);
     }
     TP_HIP(hipGetLastError());
@@ -350,11 +265,11 @@ int topo_degree(const TopoIndex &ix, hipStream_t st, uint64_t *out) {
 }
 
 struct ValidateJob {
-    Scratch sc;
+    DeviceMem sc;
     IndexView ix{};
     TopoSteps sp;
     uint64_t tiles = 0, total = 0;
-    uint64_t *aggr = nullptr, *prefix = nullptr;
+    Spine<Sum<uint32_t>> pairs;  // missing pairs per tile of steps
     uint32_t *flags = nullptr;
     bool counted = false;
 };
@@ -371,17 +286,16 @@ int validate_count(ValidateJob *j, const TopoIndex &ix, const TopoSteps &sp, hip
     j->total = 0;
     j->counted = !sp.n_lin;
     if (!sp.n_lin) return FLATGFA_OK;  // (no path has a step)
-    TP_HIP(j->sc.alloc(&j->aggr, j->tiles));
-    TP_HIP(j->sc.alloc(&j->prefix, j->tiles + 1));
+    TP_HIP(j->pairs.alloc(&j->sc, j->tiles));
     TP_HIP(j->sc.alloc(&j->flags, 1));
     TP_HIP(hipMemsetAsync(j->flags, 0, 4, st));
-    hipLaunchKernelGGL((k_steps<false>), dim3(stride_blocks(j->tiles, 1)), dim3(kThreads), 0, st, j->ix, sp, j->tiles, j->aggr, j->prefix,
-                       (uint4 *)nullptr, j->flags);
-    hipLaunchKernelGGL(k_spine, dim3(1), dim3(kThreads), 0, st, j->aggr, j->tiles, j->prefix, j->prefix + j->tiles);
+    hipLaunchKernelGGL((k_steps<false>), dim3(stride_blocks(j->tiles, 1, kMaxGrid)), dim3(kThreads), 0, st, j->ix, sp, j->tiles, j->pairs.aggr,
+                       j->pairs.prefix, (uint4 *)nullptr, j->flags);
+    hipLaunchKernelGGL((k_spine<Sum<uint64_t>, kThreads>), dim3(1), dim3(kThreads), 0, st, j->pairs.aggr, j->tiles, j->pairs.prefix, j->pairs.total);
     TP_HIP(hipGetLastError());
     uint32_t f = 0;
     TP_HIP(staged_copy(&f, j->flags, 4, hipMemcpyDeviceToHost, st));
-    TP_HIP(staged_copy(&j->total, j->prefix + j->tiles, 8, hipMemcpyDeviceToHost, st));
+    TP_HIP(staged_copy(&j->total, j->pairs.total, 8, hipMemcpyDeviceToHost, st));
     if (f & kBadStep) {
         set_error("topology: a step refers to a segment id that is out of range");
         return FLATGFA_ERR_BOUNDS;
@@ -399,7 +313,7 @@ int validate_fill(ValidateJob *j, flatgfa_missing_link_t *out) {
     hipStream_t st = j->sc.st;
     uint4 *recs = nullptr;
     TP_HIP(j->sc.alloc(&recs, j->total));
-    hipLaunchKernelGGL((k_steps<true>), dim3(stride_blocks(j->tiles, 1)), dim3(kThreads), 0, st, j->ix, j->sp, j->tiles, j->aggr, j->prefix, recs,
+    hipLaunchKernelGGL((k_steps<true>), dim3(stride_blocks(j->tiles, 1, kMaxGrid)), dim3(kThreads), 0, st, j->ix, j->sp, j->tiles, j->pairs.aggr, j->pairs.prefix, recs,
                        j->flags);
     TP_HIP(hipGetLastError());
     TP_HIP(staged_copy(out, recs, (size_t)j->total * sizeof(uint4), hipMemcpyDeviceToHost, st));

@@ -141,6 +141,9 @@ def test_shape_constants_are_the_kernels():
     rows = np.bincount(hub.links["from_"], minlength=6)
     assert rows[0] > ts.LINEAR + 1 and rows[2] == ts.LINEAR and rows[4] == ts.LINEAR + 1
     assert tm.degree(ts.BY_NAME["degree_hub"].pools())[0] > 65535
+    n_scan = {name: 2 * len(ts.BY_NAME[name].pools().segs) + 1 for name in ts.ROWS}  # the entries of the row scan
+    assert n_scan["rows_last_tile_one_short"] == ts.TILE - 1 and n_scan["rows_last_tile_of_one"] == ts.TILE + 1
+    assert -(-n_scan["rows_past_a_spine_round"] // ts.TILE) > ts.THREADS
 
 
 def test_new_symbols_are_in_the_built_library():

@@ -205,6 +205,24 @@ def _degree_hub():
     return make_pools(50, [0, 8, 0, 9, 10, 10, 10, 11, 20, 22, 23, 21], [(0, 2), (2, 4), (4, 6), (6, 8), (8, 10), (10, 12)], links)
 
 
+def _rows(S: int):
+    """S segments, so a row array of 2 S + 1 entries (one per handle, and the end of the last row) for the in-place scan.  Links
+    lie in the rows on both sides of every edge of the row tiles named below and in the two topmost rows, 2 S - 2 and 2 S - 1
+    (the only key of row 2 S - 1 is the palindrome (S-1)- -> (S-1)+), so a prefix that is off at any of them misplaces a row
+    that a two-step path then looks up; one pair in a top row is left unsupported."""
+    edges = [e for e in (TILE, 2 * TILE, (THREADS - 1) * TILE, THREADS * TILE) if e < 2 * S]  # (in handles: the first row of a tile)
+    segs = sorted({s for e in edges for s in (e // 2 - 1, e // 2) if s + 1 < S} | {0, S - 2})
+    top = int(fwd(S - 1))
+    links = [(int(fwd(s)), int(fwd(s + 1))) for s in segs] + [(top ^ 1, top)]
+    pairs = links + [(top, top), (top ^ 1, int(fwd(S - 2)) ^ 1)]  # (S-1)+ -> (S-1)+: none; (S-1)- -> (S-2)-: the reverse of a link
+    steps = [h for pr in pairs for h in pr]
+    return make_pools(S, steps, [(2 * k, 2 * k + 2) for k in range(len(pairs))], links), [(len(links), 0)]
+
+
+# Row arrays whose last tile lacks one entry (2 S + 1 is odd and a tile even: a full last tile does not exist), whose last tile
+# holds one entry, and of more tiles than the one workgroup of the spine takes in a round
+ROWS = {"rows_last_tile_one_short": TILE // 2 - 1, "rows_last_tile_of_one": TILE // 2, "rows_past_a_spine_round": THREADS * TILE // 2 + 1}
+
 SHAPES = [Shape("edge_%d_%s" % (k, how), "the pair (X, Y) with X the last step of a lane, a wave or a workgroup's tile: %s" % how,
                 (lambda k=k, how=how: planted(SMALL_N, [k], how)), missing=[(0, k)] if how == "none" else [])
           for k in EDGES for how in ("none", "rev", "fwd")] + [
@@ -226,7 +244,7 @@ SHAPES = [Shape("edge_%d_%s" % (k, how), "the pair (X, Y) with X the last step o
     Shape("no_paths", "P = 0", lambda: make_pools(9, [0, 2, 4], [], chain_links(9)), missing=[]),
     Shape("no_links", "L = 0 and one path", lambda: make_pools(9, [0, 2, 4], [(0, 3)], []), missing=[(0, 0), (0, 1)]),
     Shape("nothing", "S = P = L = 0", lambda: make_pools(0, [], [], []), missing=[]),
-]
+] + [Shape(name, "a row array of 2 * %d + 1 entries" % S, (lambda S=S: _rows(S)[0]), missing=_rows(S)[1]) for name, S in ROWS.items()]
 BY_NAME = {s.name: s for s in SHAPES}
 assert len(BY_NAME) == len(SHAPES)
-BIG = {"grid_round_none", "grid_round_rev", "grid_round_paths"}
+BIG = {"grid_round_none", "grid_round_rev", "grid_round_paths", "rows_past_a_spine_round"}

@@ -116,7 +116,7 @@ def main():
                              os.path.abspath(__file__), "--child", path], capture_output=True, timeout=900)
         stats = glob.glob(os.path.join(trace, "**", "*kernel_stats.csv"), recursive=True)
         if pr.returncode == 0 and stats:
-            rows = [x for x in csv.DictReader(open(stats[0])) if any(k in x["Name"] for k in ("k_steps", "k_link", "k_scan_u32", "k_spine", "k_sort_rows", "k_long_rows"))]
+            rows = [x for x in csv.DictReader(open(stats[0])) if any(k in x["Name"] for k in ("k_steps", "k_link", "k_scan<", "k_spine", "k_sort_rows", "k_long_rows"))]
             r["kernels"] = {x["Name"][:70]: round(float(x["TotalDurationNs"]) / 1e6, 3) for x in rows}
             count = [float(x["TotalDurationNs"]) / 3e6 for x in rows if "k_steps<false>" in x["Name"] or "k_stepsILb0" in x["Name"]]
             if count:
