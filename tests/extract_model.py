@@ -173,6 +173,10 @@ _OPS = "MNDI"  # print.rs:13-22 (Insertion prints D, Deletion prints I)
 
 def _align(p, a, b):
     ops = p.alignment[a:b]
+    if len(ops) > 4096:  # (megabase spans: every distinct op is formatted once)
+        u, inv = np.unique(ops, return_inverse=True)
+        words = [b"%d%s" % (int(o) >> 8, _OPS[int(o) & 0xFF].encode()) for o in u]
+        return b"".join(map(words.__getitem__, inv.tolist()))
     return b"0M" if len(ops) == 0 else b"".join(b"%d%s" % (int(o) >> 8, _OPS[int(o) & 0xFF].encode()) for o in ops)
 
 

@@ -51,6 +51,16 @@ def test_model_print_matches_the_library_printer():
         assert em.text(q) == cm.text(q), sh.name
 
 
+def test_long_alignment_spans_print_like_short_ones():
+    # past 4 096 ops _align formats every distinct op once: the same bytes as op by op
+    import numpy as np
+    rng = np.random.default_rng(0)
+    p = fo.parse_gfa(b"S\t1\tAC\n")
+    p.alignment = ((rng.integers(0, 1 << 24, 9000) << 8) | rng.integers(0, 4, 9000)).astype(np.uint32)
+    for a, b in ((0, 9000), (17, 4114), (17, 4113)):
+        assert em._align(p, a, b) == b"".join(b"%d%s" % (int(o) >> 8, "MNDI"[int(o) & 0xFF].encode()) for o in p.alignment[a:b])
+
+
 def test_position_by_hand():
     p = fo.parse_gfa(b"S\t1\tAC\nS\t2\tGGG\nS\t7\tT\nP\tx\t1+,2-,7+\t*\nP\ty\t7-\t*\n")
     assert em.position(p, 0, 0) == (0, 0) and em.position(p, 0, 1) == (0, 1)

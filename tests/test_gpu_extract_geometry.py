@@ -14,11 +14,12 @@ from test_gpu_extract import extract_id, load_pools, same
 pytestmark = pytest.mark.gpu
 
 
-def with_links(p: fo.Pools, f, t, rng):
+def with_links(p: fo.Pools, f, t, rng, n_ops=None):
+    """p with the links f[i] -> t[i], random orientations, and n_ops[i] (0 .. 2 where not given) alignment ops each."""
     lk = np.zeros(len(f), fo.LINK_DT)
     lk["from_"] = (np.asarray(f, np.uint32) << 1) | rng.integers(0, 2, len(f)).astype(np.uint32)
     lk["to"] = (np.asarray(t, np.uint32) << 1) | rng.integers(0, 2, len(f)).astype(np.uint32)
-    n_ops = rng.integers(0, 3, len(f))
+    n_ops = rng.integers(0, 3, len(f)) if n_ops is None else n_ops
     off = np.concatenate([[0], np.cumsum(n_ops)])
     lk["ov_start"], lk["ov_end"] = off[:-1], off[1:]
     q = fo.Pools(**{n: getattr(p, n) for n in fo.POOL_ORDER})
@@ -140,3 +141,86 @@ def test_position_on_a_path_past_one_grid():
             k = int(np.searchsorted(ends, off, side="right"))
             want = None if k == len(st) else (int(p.segs[st[k] >> 1]["name"]), off - (int(ends[k - 1]) if k else 0), int(st[k]) & 1 == 0)
             assert g.position(p.path_name(pid), off) == want, (pid, off)
+
+
+def test_heads_and_kept_links_planted_on_tile_and_spine_round_edges():
+    # the scan's tile is 1 024 elements and its spine goes round every 256 tiles: paths start exactly at steps 1 024, 2 048,
+    # 262 144 (the first step behind a round) and 262 145, with member steps on both sides of every start; the links kept
+    # at 1 023, 1 024, 262 143 and 262 144 carry alignment ops and the links next to them none
+    rng = np.random.default_rng(6)
+    path_lens = np.array([1024, 1024, 260_096, 1, 2500], np.int64)
+    starts = np.cumsum(path_lens)[:-1]
+    assert list(starts) == [1024, 2048, 262_144, 262_145]
+    n = int(path_lens.sum())
+    member = rng.random(n) < 0.4
+    for s in starts:
+        member[s - 1:s + 2] = True
+    p = planted(rng, 3000, member, path_lens)
+    L = 262_144 + 1700
+    kept = rng.random(L) < 0.05
+    edges = np.array([1023, 1024, 262_143, 262_144])
+    kept[edges] = True
+    kept[[1022, 262_145]], kept[[1025, 262_142]] = True, False
+    f = np.where(kept, rng.integers(1, 10, L), rng.integers(10, 3000, L))
+    t = np.where(kept, rng.integers(1, 10, L), rng.integers(10, 3000, L))
+    f[:9], t[:9] = 0, np.arange(1, 10)  # (what makes 1 .. 9 the origin's neighbours)
+    n_ops = rng.integers(0, 3, L)
+    n_ops[edges] = [1, 2, 2, 1]
+    n_ops[[1022, 1025, 262_142, 262_145]] = 0
+    p = with_links(p, f, t, rng, n_ops)
+    res = check(p, [(0, 1, 0, 0), (0, 1, 40, 2)])
+    want = res[0][1]
+    assert len(want.segs) == 10 and len(want.steps) == int(member.sum())
+    # every planted start opens a subpath at position 0 of its path, and the step before it closes one
+    names = [want.path_name(k) for k in range(len(want.paths))]
+    for k in range(1, 5):
+        assert sum(nm.startswith(b"p%d:0-" % k) for nm in names) == 1
+    assert len(want.links) == int(kept[9:].sum()) + 9 and len(want.alignment) == int(n_ops[9:][kept[9:]].sum() + n_ops[:9].sum())
+
+
+def shared_span_graph(n_segs, n_links, self_loops):
+    """n_segs segments that share one sequence span of 2^20 bases, chained by links; or one segment with n_links self-loops
+    that all carry the whole alignment pool of 2^20 ops.  (Spans may overlap: the loader wants each inside its pool.)"""
+    rng = np.random.default_rng(8)
+    big = 1 << 20
+    segs = np.zeros(n_segs, fo.SEG_DT)
+    segs["name"], segs["seq_start"], segs["seq_end"] = np.arange(1, n_segs + 1), 0, (4 if self_loops else big)
+    lk = np.zeros(n_links, fo.LINK_DT)
+    if self_loops:
+        lk["from_"], lk["to"], lk["ov_start"], lk["ov_end"] = 0, rng.integers(0, 2, n_links), 0, big
+        align = ((rng.integers(1, 200, big) << 8) | rng.integers(0, 4, big)).astype(np.uint32)
+    else:
+        lk["from_"], lk["to"] = np.arange(n_links) << 1, (np.arange(1, n_links + 1) << 1) | rng.integers(0, 2, n_links)
+        align = np.zeros(0, np.uint32)
+    z = np.zeros(0, np.uint8)
+    return fo.Pools(header=np.frombuffer(b"VN:Z:1.0", np.uint8).copy(), segs=segs, paths=np.zeros(0, fo.PATH_DT), links=lk,
+                    steps=np.zeros(0, np.uint32), seq_data=rng.choice(np.frombuffer(b"ACGT", np.uint8), 4 if self_loops else big),
+                    overlaps=np.zeros(0, fo.SPAN_DT), alignment=align, name_data=z, optional_data=z, line_order=z)
+
+
+def refused(p, origin, c):
+    g, path = load_pools(p)
+    try:
+        with pytest.raises(pa.FlatGFAError) as e:
+            extract_id(g, origin, c, 0, 0)
+        return e.value
+    finally:
+        g.close()
+        os.unlink(path)
+
+
+def test_alignment_ops_reaching_32_bits_are_refused():
+    # 4 096 self-loops (kept at c = 0: both ends are the origin) times 2^20 ops is 2^32 exactly: a 32-bit total reads 0
+    e = refused(shared_span_graph(1, 4096, True), 0, 0)
+    assert e.code == -6 and "would hold 4294967296 alignment ops" in str(e)
+    # ... and eight of them make a subgraph of 2^23 ops
+    (q, want), = check(shared_span_graph(1, 8, True), [(0, 0, 0, 0)])
+    assert len(want.links) == 8 and len(want.alignment) == 8 << 20 and int(want.links["ov_end"][-1]) == 8 << 20
+
+
+def test_sequences_reaching_32_bits_are_refused():
+    # 4 097 segments of 2^20 bases: the 4 096th takes the subgraph's sequences to 2^32
+    e = refused(shared_span_graph(4097, 4096, False), 2048, 4097)
+    assert e.code == -6 and "sequences or optional data pass 2^32 - 1 bytes" in str(e)
+    (q, want), = check(shared_span_graph(8, 7, False), [(4, 8, 0, 0)])
+    assert len(want.segs) == 8 and len(want.seq_data) == 8 << 20
