@@ -1,6 +1,8 @@
 // extern "C" surface of libflatgfa.so: the flatgfa-c drop-in (Part 1 of include/flatgfa.h)
-// plus the additive loaders and depth queries (Part 2).  Device work is delegated to the
-// flatgfa_dev_* entry points in depth_device.hip through the HIP runtime API only.
+// plus the additive loaders, the depth queries and the host routes of the other features (Part 2).  The kernels live in the
+// .hip files -- depth_device.hip and its kin for depth, gaf_device.hip, gaf_lookup_device.hip, chop_device.hip,
+// extract_device.hip, topology_device.hip for the rest -- and are reached through their headers; this file uses the HIP runtime
+// API only.  Every host route that is not a depth query holds what it has on the device in one DevScope (below).
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
@@ -139,14 +141,106 @@ static bool steps_name_segments(CStore *cs) {
 // (sharded.hip reads the pools of a handle)
 const fgfa::View &flatgfa_capi_view(flatgfa_t gfa) { return gfa->view; }
 
-#define CAPI_HIP(expr)                                                                      \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-            return FLATGFA_ERR_HIP;                                                         \
-        }                                                                                   \
-    } while (0)
+#define CAPI_HIP(expr) FGFA_HIP("", expr)
+
+namespace {
+// How many HIP devices there are; none is the error of every entry that needs one, which names itself in `who` ("chop has",
+// "the depth queries have").
+int count_devices(const std::string &who, int *ndev) {
+    *ndev = 0;
+    if (hipGetDeviceCount(ndev) != hipSuccess || *ndev <= 0) {
+        set_error("no HIP device is visible; " + who + " no CPU fallback");
+        return FLATGFA_ERR_NO_DEVICE;
+    }
+    return FLATGFA_OK;
+}
+
+// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree -- holds on the device,
+// given back on every way out: the work stream is waited for, then the job, the events and the memory go, then the streams
+// return to the pool.  A thread that still copies on one of the streams is joined first: its joiner is declared after the scope.
+struct DevScope {
+    int device = 0;
+    bool resident = false;         // the graph has an image on `device`, which the call may read in place
+    hipStream_t stream = nullptr;  // the work stream: the first one taken
+    std::vector<hipStream_t> streams;
+    std::vector<hipEvent_t> events;
+    std::vector<void *> mem;
+    void *job = nullptr;  // the feature's job object (no route has two) and how it is freed
+    void (*job_free)(void *) = nullptr;
+    DevScope() = default;
+    DevScope(const DevScope &) = delete;
+    DevScope &operator=(const DevScope &) = delete;
+    ~DevScope() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (job) job_free(job);
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        for (void *p : mem) (void)hipFree(p);
+        for (hipStream_t s : streams) stream_release(device, s);
+    }
+    hipError_t take_stream(hipStream_t *out) {
+        *out = nullptr;
+        const hipError_t e = stream_acquire(device, out);
+        if (e == hipSuccess) streams.push_back(*out);
+        return e;
+    }
+    hipError_t make_event(hipEvent_t *out) {
+        *out = nullptr;
+        const hipError_t e = hipEventCreateWithFlags(out, hipEventDisableTiming);
+        if (e == hipSuccess) events.push_back(*out);
+        return e;
+    }
+    template <class J, void (*Free)(J *)>
+    J *hold(J *j) {
+        job = j;
+        job_free = [](void *p) { Free(static_cast<J *>(p)); };
+        return j;
+    }
+    template <class T>
+    hipError_t alloc(T **p, size_t count) {  // (at least one element)
+        *p = nullptr;
+        const hipError_t e = hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) mem.push_back(*p);
+        return e;
+    }
+    // a device copy of host memory
+    template <class T>
+    hipError_t upload(T **p, const void *src, size_t count) {
+        hipError_t e = alloc(p, count);
+        if (e == hipSuccess && count) e = fgfa_dev::staged_copy(*p, src, count * sizeof(T), hipMemcpyHostToDevice, stream);
+        return e;
+    }
+    // one allocation given back early (NULL: nothing)
+    hipError_t release(void *p) {
+        if (!p) return hipSuccess;
+        mem.erase(std::remove(mem.begin(), mem.end(), p), mem.end());
+        return hipFree(p);
+    }
+};
+
+// The device a call on `gfa` runs on (the one it is resident on, else 0), made current, with the work stream.
+int open_scope(CStore *gfa, DevScope *sc, const char *what) {
+    {
+        std::lock_guard<std::mutex> lk(gfa->dev_mu);
+        if (gfa->on_device) sc->device = gfa->device, sc->resident = true;  // (beside the graph; it is not made resident)
+    }
+    int ndev = 0;
+    if (int rc = count_devices(std::string(what) + " has", &ndev)) return rc;
+    CAPI_HIP(hipSetDevice(sc->device));
+    CAPI_HIP(sc->take_stream(&sc->stream));
+    return FLATGFA_OK;
+}
+
+struct Joiner {
+    std::thread &t;
+    ~Joiner() { if (t.joinable()) t.join(); }
+};
+
+// The size GAF text is cut to for the device (fgfa::cut_lines): 64 MiB, or what the tests ask for.
+size_t gaf_chunk_bytes() {
+    if (const char *h = test_hook("FLATGFA_GAF_CHUNK_BYTES")) return std::max<size_t>(1, strtoull(h, nullptr, 10));
+    return (size_t)64 << 20;
+}
+}  // namespace
 
 extern "C" {
 
@@ -389,10 +483,7 @@ int flatgfa_keep_host_memory(int on) {
 
 int flatgfa_warm_device(int device) {
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("no HIP device is visible; the depth queries have no CPU fallback");
-        return FLATGFA_ERR_NO_DEVICE;
-    }
+    if (int rc = count_devices("the depth queries have", &ndev)) return rc;
     if (device < 0 || device >= ndev) { set_error("device index out of range"); return FLATGFA_ERR_ARG; }
     CAPI_HIP(hipSetDevice(device));
     CAPI_HIP(fgfa_dev::warm_staging(device));  // (the staging buffers and this device's events, kept by the process)
@@ -424,10 +515,7 @@ static int ensure_device(CStore *cs, int device) {
     }
     if (device < 0) device = 0;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("no HIP device is visible; the depth queries have no CPU fallback");
-        return FLATGFA_ERR_NO_DEVICE;
-    }
+    if (int rc = count_devices("the depth queries have", &ndev)) return rc;
     if (device >= ndev) { set_error("device index out of range"); return FLATGFA_ERR_ARG; }
     const fgfa::View &v = cs->view;
     if (v.steps.len > 0xFFFFFFFFull || v.segs.len > 0x80000000ull || v.paths.len > 0xFFFFFFFFull) {
@@ -916,73 +1004,33 @@ int flatgfa_pangenotype_matrix(flatgfa_t gfa, const uint8_t *const *gaf, const s
         if (gaf_len[f] && !gaf[f]) { set_error("flatgfa_pangenotype_matrix: NULL text with a length"); return FLATGFA_ERR_ARG; }
     if (n_files == 0) return FLATGFA_OK;
     std::lock_guard<std::mutex> op(gfa->op_mu);
-    int device = 0;
-    {
-        std::lock_guard<std::mutex> lk(gfa->dev_mu);
-        if (gfa->on_device) device = gfa->device;  // (beside the graph, when it is resident; it is not made so)
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("no HIP device is visible; the pangenotype matrix has no CPU fallback");
-        return FLATGFA_ERR_NO_DEVICE;
-    }
-    CAPI_HIP(hipSetDevice(device));
-    int rc = ensure_gaf_names(gfa, device);
+    DevScope sc;
+    if (int rc = open_scope(gfa, &sc, "the pangenotype matrix")) return rc;
+    int rc = ensure_gaf_names(gfa, sc.device);
     if (rc) return rc;
     const size_t S = gfa->view.segs.len, W = (S + 63) / 64;
 
-    // Chunks cut after a '\n', at most `target` bytes unless one line is longer; the bytes behind a file's last '\n' are dropped.
-    size_t target = (size_t)64 << 20;
-    if (const char *h = test_hook("FLATGFA_GAF_CHUNK_BYTES")) target = std::max<size_t>(1, strtoull(h, nullptr, 10));  // tests
-    struct Piece {
-        uint32_t file;
-        size_t begin, end;
-    };
-    std::vector<Piece> pieces;
-    size_t cap = 16;
+    // Every file's chunks (fgfa::cut_lines), one file behind another; the bytes behind a file's last '\n' are dropped.
+    std::vector<std::pair<size_t, size_t>> pieces;
+    std::vector<size_t> first(n_files + 1, 0);  // file f's pieces are [first[f], first[f + 1])
+    const size_t target = gaf_chunk_bytes();
     for (uint32_t f = 0; f < n_files; ++f) {
-        const uint8_t *t = gaf[f];
-        const size_t n = gaf_len[f];
-        const void *last = n ? memrchr(t, '\n', n) : nullptr;
-        const size_t end = last ? (size_t)((const uint8_t *)last - t) + 1 : 0;
-        for (size_t b = 0; b < end;) {
-            size_t e = end;
-            if (end - b > target) {
-                const void *q = memrchr(t + b, '\n', target);
-                if (!q) q = memchr(t + b + target, '\n', end - b - target);  // a line longer than a chunk grows it
-                e = (size_t)((const uint8_t *)q - t) + 1;
-            }
-            pieces.push_back(Piece{f, b, e});
-            cap = std::max(cap, e - b);
-            b = e;
-        }
+        fgfa::cut_lines(gaf[f], gaf_len[f], target, &pieces);
+        first[f + 1] = pieces.size();
     }
+    size_t cap = 16;
+    for (const auto &pc : pieces) cap = std::max(cap, pc.second - pc.first);
     cap = (cap + 255) & ~(size_t)255;
     const size_t scratch_words = fgfa_dev::gaf_scratch_words(nullptr, cap);  // (the text buffers are 256-byte aligned)
 
-    // One allocation: two text buffers and their scratch, the row, the first bad offset.  Freed before returning.
+    // One allocation: two text buffers and their scratch, the row, the first bad offset.
     uint8_t *block = nullptr;
     const size_t per = (cap + scratch_words * 8 + 255) & ~(size_t)255;
-    CAPI_HIP(hipMalloc(&block, 2 * per + W * 8 + 8));
-    hipStream_t ks = nullptr, cs = nullptr;
+    CAPI_HIP(sc.alloc(&block, 2 * per + W * 8 + 8));
+    hipStream_t ks = sc.stream, cs = nullptr;
     hipEvent_t done[2] = {nullptr, nullptr};
-    struct Release {
-        int device;
-        uint8_t *&block;
-        hipStream_t &ks, &cs;
-        hipEvent_t *done;
-        ~Release() {
-            if (ks) (void)hipStreamSynchronize(ks);
-            for (int i = 0; i < 2; ++i)
-                if (done[i]) (void)hipEventDestroy(done[i]);
-            (void)hipFree(block);
-            stream_release(device, ks);
-            stream_release(device, cs);
-        }
-    } release{device, block, ks, cs, done};
-    CAPI_HIP(stream_acquire(device, &ks));
-    CAPI_HIP(stream_acquire(device, &cs));
-    for (int i = 0; i < 2; ++i) CAPI_HIP(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
+    CAPI_HIP(sc.take_stream(&cs));
+    for (int i = 0; i < 2; ++i) CAPI_HIP(sc.make_event(&done[i]));
     uint8_t *d_text[2] = {block, block + per};
     uint64_t *d_scratch[2] = {reinterpret_cast<uint64_t *>(block + cap), reinterpret_cast<uint64_t *>(block + per + cap)};
     uint64_t *d_row = reinterpret_cast<uint64_t *>(block + 2 * per), *d_bad = d_row + W;
@@ -992,12 +1040,12 @@ int flatgfa_pangenotype_matrix(flatgfa_t gfa, const uint8_t *const *gaf, const s
     for (uint32_t f = 0; f < n_files; ++f) {
         if (W) CAPI_HIP(hipMemsetAsync(d_row, 0, W * 8, ks));
         CAPI_HIP(hipMemsetAsync(d_bad, 0xFF, 8, ks));
-        for (; k < pieces.size() && pieces[k].file == f; ++k) {
+        for (; k < first[f + 1]; ++k) {
             const int b = (int)(k & 1);
             if (used[b]) CAPI_HIP(hipEventSynchronize(done[b]));  // the scan that read this buffer is over
-            const size_t len = pieces[k].end - pieces[k].begin;
-            CAPI_HIP(fgfa_dev::staged_copy(d_text[b], gaf[f] + pieces[k].begin, len, hipMemcpyHostToDevice, cs));  // (beside the scan of the piece before, on ks)
-            CAPI_HIP(fgfa_dev::gaf_scan(d_text[b], len, gfa->gaf_names, d_row, d_bad, pieces[k].begin, d_scratch[b], ks));
+            const size_t len = pieces[k].second - pieces[k].first;
+            CAPI_HIP(fgfa_dev::staged_copy(d_text[b], gaf[f] + pieces[k].first, len, hipMemcpyHostToDevice, cs));  // (beside the scan of the piece before, on ks)
+            CAPI_HIP(fgfa_dev::gaf_scan(d_text[b], len, gfa->gaf_names, d_row, d_bad, pieces[k].first, d_scratch[b], ks));
             CAPI_HIP(hipEventRecord(done[b], ks));
             used[b] = true;
         }
@@ -1144,90 +1192,55 @@ struct GafResult {
 // -- when nothing in it is bad -- its answer comes back through the same staging, the `-s` text in pieces of a bounded size.
 static int gaf_lookup_host(flatgfa_t gfa, const uint8_t *gaf, size_t len, GafMode mode, GafResult *res) {
     std::lock_guard<std::mutex> op(gfa->op_mu);
-    int device = 0;
-    {
-        std::lock_guard<std::mutex> lk(gfa->dev_mu);
-        if (gfa->on_device) device = gfa->device;  // (beside the graph, when it is resident; it is not made so)
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("no HIP device is visible; the GAF lookup has no CPU fallback");
-        return FLATGFA_ERR_NO_DEVICE;
-    }
-    CAPI_HIP(hipSetDevice(device));
+    DevScope sc;
+    if (int rc = open_scope(gfa, &sc, "the GAF lookup")) return rc;
+    const int device = sc.device;
     fgfa_dev::GafGraph graph;
     int rc = ensure_gaf_graph(gfa, device, &graph);
     if (rc) return rc;
     if (mode == kGafEvents) res->line_first.push_back(0);
 
-    size_t target = (size_t)64 << 20, out_bound = (size_t)64 << 20;
-    if (const char *h = test_hook("FLATGFA_GAF_CHUNK_BYTES")) target = std::max<size_t>(1, strtoull(h, nullptr, 10));   // tests
+    size_t out_bound = (size_t)64 << 20;
     if (const char *h = test_hook("FLATGFA_GAF_OUT_BYTES")) out_bound = std::max<size_t>(1, strtoull(h, nullptr, 10));  // tests
-    const void *last_nl = len ? memrchr(gaf, '\n', len) : nullptr;
-    const size_t end = last_nl ? (size_t)((const uint8_t *)last_nl - gaf) + 1 : 0;  // (what follows the last '\n' is not a line)
-
-    // The chunks: cut after a '\n', at most `target` bytes unless one line is longer.
-    std::vector<std::pair<size_t, size_t>> pieces;
-    size_t text_cap = 16;
-    for (size_t b = 0; b < end;) {
-        size_t e = end;
-        if (end - b > target) {
-            const void *q = memrchr(gaf + b, '\n', target);
-            if (!q) q = memchr(gaf + b + target, '\n', end - b - target);  // a line longer than a chunk grows it
-            e = (size_t)((const uint8_t *)q - gaf) + 1;
-        }
-        pieces.emplace_back(b, e);
-        text_cap = std::max(text_cap, e - b);
-        b = e;
-    }
+    std::vector<std::pair<size_t, size_t>> pieces;  // the chunks (what follows the last '\n' is not a line)
+    fgfa::cut_lines(gaf, len, gaf_chunk_bytes(), &pieces);
     if (pieces.empty()) return FLATGFA_OK;
+    size_t text_cap = 16;
+    for (const auto &pc : pieces) text_cap = std::max(text_cap, pc.second - pc.first);
     text_cap = (text_cap + 255) & ~(size_t)255;
 
     // Two text buffers: the chunk behind the one being looked up travels to the device meanwhile, on a thread and a stream of
     // its own (a staged copy returns when the bytes have arrived).
     hipError_t up_err = hipSuccess;  // (declared before the thread that writes it is: it outlives the join)
-    struct Release {
-        int device = 0;
-        hipStream_t st = nullptr, cs = nullptr;
-        uint8_t *d_text = nullptr, *d_out = nullptr;
-        fgfa_dev::GafLookupJob *job = nullptr;
-        std::thread up;
-        ~Release() {
-            if (up.joinable()) up.join();
-            fgfa_dev::gaf_lookup_free(job);
-            if (d_text) (void)hipFree(d_text);
-            if (d_out) (void)hipFree(d_out);
-            stream_release(device, st);
-            stream_release(device, cs);
-        }
-    } r;
-    r.device = device;
-    CAPI_HIP(stream_acquire(device, &r.st));
-    CAPI_HIP(stream_acquire(device, &r.cs));
-    r.job = fgfa_dev::gaf_lookup_new();
-    CAPI_HIP(hipMalloc(&r.d_text, (pieces.size() > 1 ? 2 : 1) * text_cap));
+    std::thread up;
+    Joiner joiner{up};  // (declared after the scope: the copy is over before the scope gives its buffer and stream back)
+    const hipStream_t st = sc.stream;
+    hipStream_t cs = nullptr;
+    CAPI_HIP(sc.take_stream(&cs));
+    fgfa_dev::GafLookupJob *job = sc.hold<fgfa_dev::GafLookupJob, fgfa_dev::gaf_lookup_free>(fgfa_dev::gaf_lookup_new());
+    uint8_t *d_texts = nullptr, *d_out = nullptr;
+    CAPI_HIP(sc.alloc(&d_texts, (pieces.size() > 1 ? 2 : 1) * text_cap));
     size_t out_cap = 0;
-    up_err = fgfa_dev::staged_copy(r.d_text, gaf + pieces[0].first, pieces[0].second - pieces[0].first, hipMemcpyHostToDevice, r.cs);
+    up_err = fgfa_dev::staged_copy(d_texts, gaf + pieces[0].first, pieces[0].second - pieces[0].first, hipMemcpyHostToDevice, cs);
     for (size_t k = 0; k < pieces.size(); ++k) {
-        if (r.up.joinable()) r.up.join();
+        if (up.joinable()) up.join();
         CAPI_HIP(up_err);
         const size_t b = pieces[k].first, n = pieces[k].second - b;
-        uint8_t *d_text = r.d_text + (k & 1) * text_cap;
+        uint8_t *d_text = d_texts + (k & 1) * text_cap;
         if (k + 1 < pieces.size()) {  // (its buffer was read by chunk k - 1, which is done: every count and copy-back waited)
-            uint8_t *d_next = r.d_text + ((k + 1) & 1) * text_cap;
+            uint8_t *d_next = d_texts + ((k + 1) & 1) * text_cap;
             const uint8_t *src = gaf + pieces[k + 1].first;
             const size_t bytes = pieces[k + 1].second - pieces[k + 1].first;
-            hipStream_t cs = r.cs;
-            r.up = std::thread([=, &up_err] {
+            up = std::thread([=, &up_err] {
                 up_err = hipSetDevice(device);
                 if (up_err == hipSuccess) up_err = fgfa_dev::staged_copy(d_next, src, bytes, hipMemcpyHostToDevice, cs);
             });
         }
         fgfa_dev::GafTotals t;
-        rc = fgfa_dev::gaf_lookup_count(r.job, d_text, n, graph, mode == kGafSeqs, b, r.st, &t);
+        rc = fgfa_dev::gaf_lookup_count(job, d_text, n, graph, mode == kGafSeqs, b, st, &t);
         if (!rc) rc = gaf_lookup_verdict(t, mode == kGafSeqs);  // (chunks go in text order: the first bad chunk holds the lowest offset)
         if (rc) return rc;
-        const fgfa_dev::GafArrays &ar = fgfa_dev::gaf_lookup_arrays(r.job);
+        const fgfa_dev::GafArrays &ar = fgfa_dev::gaf_lookup_arrays(job);
         const uint64_t L = t.n_lines, E = t.n_events;
         if (mode == kGafSeqs) {
             if (res->text_len + t.seq_bytes + 1 > res->text_cap) {
@@ -1240,14 +1253,15 @@ static int gaf_lookup_host(flatgfa_t gfa, const uint8_t *gaf, size_t len, GafMod
             for (uint64_t o = 0; o < t.seq_bytes;) {  // the chunk's text, a bounded piece at a time
                 const uint64_t m = std::min<uint64_t>(out_bound, t.seq_bytes - o);
                 if (m > out_cap) {  // (at most a few times a call: it grows to twice what was needed, up to the bound)
-                    if (r.d_out) CAPI_HIP(hipFree(r.d_out));
-                    r.d_out = nullptr;
+                    uint8_t *old = d_out;
+                    d_out = nullptr;
+                    CAPI_HIP(sc.release(old));
                     out_cap = std::min<uint64_t>(out_bound, 2 * std::max<uint64_t>(m, t.seq_bytes));
-                    CAPI_HIP(hipMalloc(&r.d_out, out_cap + 16));
+                    CAPI_HIP(sc.alloc(&d_out, out_cap + 16));
                 }
-                rc = fgfa_dev::gaf_lookup_gather(r.job, o, o + m, r.d_out, r.st);
+                rc = fgfa_dev::gaf_lookup_gather(job, o, o + m, d_out, st);
                 if (rc) return rc;
-                CAPI_HIP(fgfa_dev::staged_copy(res->text + res->text_len, r.d_out, m, hipMemcpyDeviceToHost, r.st));
+                CAPI_HIP(fgfa_dev::staged_copy(res->text + res->text_len, d_out, m, hipMemcpyDeviceToHost, st));
                 res->text_len += m;
                 o += m;
             }
@@ -1257,9 +1271,9 @@ static int gaf_lookup_host(flatgfa_t gfa, const uint8_t *gaf, size_t len, GafMod
             res->name_off.resize(L0 + L);
             res->name_len.resize(L0 + L);
             // (line_first[L0] of this chunk is 0 on the device and E0 here: copied from the chunk's second entry on)
-            CAPI_HIP(fgfa_dev::staged_copy(&res->line_first[L0 + 1], ar.line_first + 1, L * 8, hipMemcpyDeviceToHost, r.st));
-            CAPI_HIP(fgfa_dev::staged_copy(&res->name_off[L0], ar.line_end, L * 8, hipMemcpyDeviceToHost, r.st));
-            CAPI_HIP(fgfa_dev::staged_copy(&res->name_len[L0], ar.name_len, L * 8, hipMemcpyDeviceToHost, r.st));
+            CAPI_HIP(fgfa_dev::staged_copy(&res->line_first[L0 + 1], ar.line_first + 1, L * 8, hipMemcpyDeviceToHost, st));
+            CAPI_HIP(fgfa_dev::staged_copy(&res->name_off[L0], ar.line_end, L * 8, hipMemcpyDeviceToHost, st));
+            CAPI_HIP(fgfa_dev::staged_copy(&res->name_len[L0], ar.name_len, L * 8, hipMemcpyDeviceToHost, st));
             for (uint64_t l = L; l-- > 0;) {  // a line starts behind the '\n' of the one before
                 res->name_off[L0 + l] = b + (l ? res->name_off[L0 + l - 1] + 1 : 0);
                 res->line_first[L0 + l + 1] += E0;
@@ -1269,10 +1283,10 @@ static int gaf_lookup_host(flatgfa_t gfa, const uint8_t *gaf, size_t len, GafMod
             res->a.resize(E0 + E);
             res->b.resize(E0 + E);
             if (E) {
-                CAPI_HIP(fgfa_dev::staged_copy(&res->handle[E0], ar.handle, E * 4, hipMemcpyDeviceToHost, r.st));
-                CAPI_HIP(fgfa_dev::staged_copy(&res->kind[E0], ar.kind, E, hipMemcpyDeviceToHost, r.st));
-                CAPI_HIP(fgfa_dev::staged_copy(&res->a[E0], ar.a, E * 8, hipMemcpyDeviceToHost, r.st));
-                CAPI_HIP(fgfa_dev::staged_copy(&res->b[E0], ar.b, E * 8, hipMemcpyDeviceToHost, r.st));
+                CAPI_HIP(fgfa_dev::staged_copy(&res->handle[E0], ar.handle, E * 4, hipMemcpyDeviceToHost, st));
+                CAPI_HIP(fgfa_dev::staged_copy(&res->kind[E0], ar.kind, E, hipMemcpyDeviceToHost, st));
+                CAPI_HIP(fgfa_dev::staged_copy(&res->a[E0], ar.a, E * 8, hipMemcpyDeviceToHost, st));
+                CAPI_HIP(fgfa_dev::staged_copy(&res->b[E0], ar.b, E * 8, hipMemcpyDeviceToHost, st));
             }
         }
         res->n_lines += L;
@@ -1447,40 +1461,11 @@ int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
         set_error("flatgfa_chop: graph too large for 32-bit ids");
         return FLATGFA_ERR_TOO_LARGE;
     }
-    int device = 0;
-    bool resident = false;
-    {
-        std::lock_guard<std::mutex> lk(gfa->dev_mu);
-        if (gfa->on_device) device = gfa->device, resident = true;  // (beside the graph, reading its image; it is not made resident)
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("no HIP device is visible; chop has no CPU fallback");
-        return FLATGFA_ERR_NO_DEVICE;
-    }
-    CAPI_HIP(hipSetDevice(device));
-    struct Release {
-        int device = 0;
-        hipStream_t stream = nullptr;
-        std::vector<void *> mem;
-        fgfa_dev::ChopJob *job = nullptr;
-        ~Release() {
-            if (stream) (void)hipStreamSynchronize(stream);
-            fgfa_dev::chop_free(job);
-            for (void *p : mem) (void)hipFree(p);
-            stream_release(device, stream);
-        }
-    } rel;
-    rel.device = device;
-    CAPI_HIP(stream_acquire(device, &rel.stream));
-    hipStream_t st = rel.stream;
-    auto dmalloc = [&](size_t bytes, void **p) -> hipError_t {
-        *p = nullptr;
-        if (!bytes) return hipSuccess;
-        const hipError_t e = hipMalloc(p, bytes);
-        if (e == hipSuccess) rel.mem.push_back(*p);
-        return e;
-    };
+    DevScope sc;
+    if (int rc = open_scope(gfa, &sc, "chop")) return rc;
+    const bool resident = sc.resident;  // (its image is read in place)
+    hipStream_t st = sc.stream;
+    // (an array of no elements stays NULL below, which chop_fill reads as "not wanted": sc.alloc would make it one element long)
     // what chop reads: the steps, spans and lengths (the resident image's, when there is one), the seq starts, the links
     const size_t Pa = (P + 63) & ~(size_t)63, Sa = (S + 63) & ~(size_t)63;
     std::vector<uint32_t> host((resident ? 0 : 2 * Pa + Sa) + Sa + 1);
@@ -1492,7 +1477,7 @@ int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
     in.n_segs = (uint32_t)S;
     in.n_links = L;
     uint32_t *d_small = nullptr;
-    CAPI_HIP(dmalloc(host.size() * 4 + (S + 1) * 4, (void **)&d_small));
+    CAPI_HIP(sc.alloc(&d_small, host.size() + S + 1));
     uint32_t *d_seg_first = d_small + host.size();
     in.seq_start = d_small;
     if (resident) {
@@ -1511,38 +1496,34 @@ int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
         in.path_end = in.path_begin + Pa;
         in.seg_len = in.path_end + Pa;
         uint32_t *d_steps = nullptr;
-        CAPI_HIP(dmalloc(N * 4, (void **)&d_steps));
-        CAPI_HIP(fgfa_dev::staged_copy(d_steps, v.steps.data, N * 4, hipMemcpyHostToDevice, st));
+        if (N) CAPI_HIP(sc.upload(&d_steps, v.steps.data, N));
         in.steps = d_steps;
     }
     CAPI_HIP(fgfa_dev::staged_copy(d_small, host.data(), host.size() * 4, hipMemcpyHostToDevice, nullptr));
     if (L) {
         uint32_t *d_links = nullptr;
-        CAPI_HIP(dmalloc(L * 16, (void **)&d_links));
+        CAPI_HIP(sc.alloc(&d_links, L * 4));
         CAPI_HIP(fgfa_dev::staged_copy(d_links, v.links.data, L * 16, hipMemcpyHostToDevice, nullptr));
         in.links = d_links;
     }
-    rel.job = fgfa_dev::chop_new();
+    fgfa_dev::ChopJob *job = sc.hold<fgfa_dev::ChopJob, fgfa_dev::chop_free>(fgfa_dev::chop_new());
     uint64_t S2 = 0, N2 = 0, L2 = 0;
-    int rc = fgfa_dev::chop_count(rel.job, in, max_size, links != 0, d_seg_first, st, &S2, &N2, &L2);
+    int rc = fgfa_dev::chop_count(job, in, max_size, links != 0, d_seg_first, st, &S2, &N2, &L2);
     if (rc) return rc;
     // the outputs, now that their sizes are known to fit
     fgfa_dev::ChopOut o;
-    CAPI_HIP(dmalloc(N2 * 4, (void **)&o.steps));
-    CAPI_HIP(dmalloc(2 * Pa * 4, (void **)&o.path_begin));
+    if (N2) CAPI_HIP(sc.alloc(&o.steps, N2));
+    if (Pa) CAPI_HIP(sc.alloc(&o.path_begin, 2 * Pa));
     o.path_end = o.path_begin ? o.path_begin + Pa : nullptr;
-    CAPI_HIP(dmalloc(S2 * 24, (void **)&o.seg_recs));
-    CAPI_HIP(dmalloc(L2 * 16, (void **)&o.links));
-    rc = fgfa_dev::chop_fill(rel.job, o, st);
+    if (S2) CAPI_HIP(sc.alloc(&o.seg_recs, S2 * 6));
+    if (L2) CAPI_HIP(sc.alloc(&o.links, L2 * 4));
+    rc = fgfa_dev::chop_fill(job, o, st);
     if (rc) return rc;
     auto cs = std::make_unique<CStore>();
     fgfa::Store &h = cs->heap;
     // (the host pools are allocated beside the kernels; the largest, the steps, on a thread of its own)
     std::thread alloc([&] { h.steps.resize(N2); });
-    struct Joiner {
-        std::thread &t;
-        ~Joiner() { if (t.joinable()) t.join(); }
-    } joiner{alloc};
+    Joiner joiner{alloc};
     h.header.assign(v.header.begin(), v.header.end());
     h.seq_data.assign(v.seq_data.begin(), v.seq_data.end());
     h.name_data.assign(v.name_data.begin(), v.name_data.end());
@@ -1570,55 +1551,6 @@ int64_t flatgfa_find_seg(flatgfa_t gfa, uint64_t name) {
         if (v.segs[i].name == name) return (int64_t)i;
     return -1;
 }
-
-extern "C++" {
-namespace {
-// What one extract or position call holds on the device, given back on every way out.
-struct DevScope {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::vector<void *> mem;
-    fgfa_dev::ExtractJob *job = nullptr;
-    ~DevScope() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        fgfa_dev::extract_free(job);
-        for (void *p : mem) (void)hipFree(p);
-        stream_release(device, stream);
-    }
-    template <class T>
-    hipError_t alloc(T **p, size_t count) {
-        *p = nullptr;
-        const hipError_t e = hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) mem.push_back(*p);
-        return e;
-    }
-    // a device copy of host memory
-    template <class T>
-    hipError_t upload(T **p, const void *src, size_t count) {
-        hipError_t e = alloc(p, count);
-        if (e == hipSuccess && count) e = fgfa_dev::staged_copy(*p, src, count * sizeof(T), hipMemcpyHostToDevice, stream);
-        return e;
-    }
-};
-
-// The device a call on `gfa` runs on (the one it is resident on, else 0), made current, with a stream.
-int open_scope(flatgfa_t gfa, DevScope *sc, bool *resident, const char *what) {
-    *resident = false;
-    {
-        std::lock_guard<std::mutex> lk(gfa->dev_mu);
-        if (gfa->on_device) sc->device = gfa->device, *resident = true;  // (beside the graph; it is not made resident)
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error(std::string("no HIP device is visible; ") + what + " has no CPU fallback");
-        return FLATGFA_ERR_NO_DEVICE;
-    }
-    CAPI_HIP(hipSetDevice(sc->device));
-    CAPI_HIP(stream_acquire(sc->device, &sc->stream));
-    return FLATGFA_OK;
-}
-}  // namespace
-}  // extern "C++"
 
 int flatgfa_extract(flatgfa_t gfa, uint32_t origin_seg, uint64_t link_distance, uint64_t max_distance_subpaths, uint64_t num_iterations,
                     flatgfa_t *out) {
@@ -1653,8 +1585,7 @@ int flatgfa_extract(flatgfa_t gfa, uint32_t origin_seg, uint64_t link_distance, 
         }
     }
     DevScope sc;
-    bool resident = false;
-    if (int rc = open_scope(gfa, &sc, &resident, "extract")) return rc;
+    if (int rc = open_scope(gfa, &sc, "extract")) return rc;
     hipStream_t st = sc.stream;
     if (int rc = ensure_gaf_seqs(gfa, sc.device)) return rc;  // (lengths and sequences, kept with the handle)
 
@@ -1670,7 +1601,7 @@ int flatgfa_extract(flatgfa_t gfa, uint32_t origin_seg, uint64_t link_distance, 
     CAPI_HIP(sc.upload(&d_links, v.links.data, L * 4));
     g.pstart = d_pstart;
     g.links = d_links;
-    if (resident) d_steps = gfa->d_steps;  // (used in place)
+    if (sc.resident) d_steps = gfa->d_steps;  // (used in place)
     else CAPI_HIP(sc.upload(&d_steps, v.steps.data, N));
     if (!tiling) {
         uint32_t *d_pb = nullptr, *d_lin = nullptr;
@@ -1681,8 +1612,7 @@ int flatgfa_extract(flatgfa_t gfa, uint32_t origin_seg, uint64_t link_distance, 
     }
     g.steps = d_steps;
 
-    sc.job = fgfa_dev::extract_new();
-    fgfa_dev::ExtractJob *job = sc.job;
+    fgfa_dev::ExtractJob *job = sc.hold<fgfa_dev::ExtractJob, fgfa_dev::extract_free>(fgfa_dev::extract_new());
     int rc = fgfa_dev::extract_begin(job, g, st);
     if (rc) return rc;
     std::vector<uint32_t> order;  // old ids in new-id order (seg_map, extract.rs:9, inverted)
@@ -1792,11 +1722,10 @@ int flatgfa_position(flatgfa_t gfa, uint32_t path, uint64_t offset, uint32_t *ha
     if (sp.start > sp.end || sp.end > v.steps.len) { set_error("flatgfa_position: the path has a step span outside the steps pool"); return FLATGFA_ERR_BOUNDS; }
     if (v.segs.len > 0x80000000ull) { set_error("flatgfa_position: graph too large for 32-bit ids"); return FLATGFA_ERR_TOO_LARGE; }
     DevScope sc;
-    bool resident = false;
-    if (int rc = open_scope(gfa, &sc, &resident, "position")) return rc;
+    if (int rc = open_scope(gfa, &sc, "position")) return rc;
     if (int rc = ensure_gaf_seqs(gfa, sc.device)) return rc;
     const uint32_t *d_steps = nullptr;
-    if (resident) {
+    if (sc.resident) {
         d_steps = gfa->d_steps + sp.start;
     } else {
         uint32_t *d = nullptr;
@@ -1911,27 +1840,23 @@ int flatgfa_validate(flatgfa_t gfa, flatgfa_missing_link_t **out, uint64_t *n) {
         pstart[p + 1] = (uint32_t)n_lin;
     }
     DevScope sc;
-    bool resident = false;
-    if (int rc = open_scope(gfa, &sc, &resident, "validate")) return rc;
+    if (int rc = open_scope(gfa, &sc, "validate")) return rc;
     if (int rc = ensure_topo(gfa, &sc)) return rc;
     fgfa_dev::TopoSteps ts;
     uint32_t *d_pstart = nullptr, *d_pbegin = nullptr, *d_steps = nullptr;
     CAPI_HIP(sc.upload(&d_pstart, pstart.data(), P + 1));
     CAPI_HIP(sc.upload(&d_pbegin, pbegin.data(), P + 1));
-    if (resident) d_steps = gfa->d_steps;  // (read in place)
+    if (sc.resident) d_steps = gfa->d_steps;  // (read in place)
     else CAPI_HIP(sc.upload(&d_steps, v.steps.data, N));
     ts.steps = d_steps, ts.pstart = d_pstart, ts.pbegin = d_pbegin, ts.n_paths = (uint32_t)P, ts.n_lin = n_lin;
-    struct JobGuard {
-        fgfa_dev::ValidateJob *j;
-        ~JobGuard() { fgfa_dev::validate_free(j); }
-    } job{fgfa_dev::validate_new()};  // (declared after the scope: freed before its stream goes back)
+    fgfa_dev::ValidateJob *job = sc.hold<fgfa_dev::ValidateJob, fgfa_dev::validate_free>(fgfa_dev::validate_new());
     uint64_t count = 0;
-    if (int rc = fgfa_dev::validate_count(job.j, gfa->topo, ts, sc.stream, &count)) return rc;
+    if (int rc = fgfa_dev::validate_count(job, gfa->topo, ts, sc.stream, &count)) return rc;
     *n = count;
     if (!out || !count) return FLATGFA_OK;
     flatgfa_missing_link_t *recs = (flatgfa_missing_link_t *)malloc((size_t)count * sizeof *recs);
     if (!recs) { set_error("flatgfa_validate: out of memory"); return FLATGFA_ERR_IO; }
-    if (int rc = fgfa_dev::validate_fill(job.j, recs)) {
+    if (int rc = fgfa_dev::validate_fill(job, recs)) {
         free(recs);
         return rc;
     }
@@ -1961,8 +1886,7 @@ int flatgfa_degree(flatgfa_t gfa, uint64_t *degree_out) {
     if (!gfa || !degree_out) { set_error("flatgfa_degree: NULL argument"); return FLATGFA_ERR_ARG; }
     std::lock_guard<std::mutex> op(gfa->op_mu);
     DevScope sc;
-    bool resident = false;
-    if (int rc = open_scope(gfa, &sc, &resident, "degree")) return rc;
+    if (int rc = open_scope(gfa, &sc, "degree")) return rc;
     if (int rc = ensure_topo(gfa, &sc)) return rc;
     return fgfa_dev::topo_degree(gfa->topo, sc.stream, degree_out);
 }

@@ -20,6 +20,18 @@ namespace fgfa_dev {
 void set_error(const std::string &s);
 const char *last_error();
 }  // namespace fgfa_dev
+
+// `return FLATGFA_ERR_HIP` with "<prefix><expr>: <what HIP says>" as the error where expr fails (for code that has
+// HIP's runtime header and flatgfa.h before it: every user, host or device side)
+#define FGFA_HIP(prefix, expr)                                                                    \
+    do {                                                                                          \
+        hipError_t _e = (expr);                                                                   \
+        if (_e != hipSuccess) {                                                                   \
+            fgfa_dev::set_error(std::string(prefix) + #expr + ": " + hipGetErrorString(_e));      \
+            return FLATGFA_ERR_HIP;                                                               \
+        }                                                                                         \
+    } while (0)
+
 // An empty launch on `stream`: what makes the runtime load this library's code object (flatgfa_warm_device).
 namespace fgfa_dev {
 void warm_launch(void *stream);

@@ -24,16 +24,6 @@
 #include "../../include/flatgfa.h"
 #include "device_common.hpp"
 
-// `return FLATGFA_ERR_HIP` with "<prefix><expr>: <what HIP says>" as the error where expr fails
-#define FGFA_HIP(prefix, expr)                                                                    \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess) {                                                                   \
-            fgfa_dev::set_error(std::string(prefix) + #expr + ": " + hipGetErrorString(_e));      \
-            return FLATGFA_ERR_HIP;                                                               \
-        }                                                                                         \
-    } while (0)
-
 namespace fgfa_dev {
 
 // ---- waves ----

@@ -1177,4 +1177,19 @@ void emit_degree(const View &v, const uint64_t *degree, std::string *out) {  // 
     }
 }
 
+void cut_lines(const uint8_t *text, size_t len, size_t target, std::vector<std::pair<size_t, size_t>> *pieces) {
+    const void *last = len ? memrchr(text, '\n', len) : nullptr;
+    const size_t end = last ? (size_t)((const uint8_t *)last - text) + 1 : 0;
+    for (size_t b = 0; b < end;) {
+        size_t e = end;
+        if (end - b > target) {
+            const void *q = memrchr(text + b, '\n', target);
+            if (!q) q = memchr(text + b + target, '\n', end - b - target);  // a line longer than a chunk grows it
+            e = (size_t)((const uint8_t *)q - text) + 1;
+        }
+        pieces->emplace_back(b, e);
+        b = e;
+    }
+}
+
 }  // namespace fgfa

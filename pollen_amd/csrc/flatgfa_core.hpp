@@ -273,6 +273,12 @@ bool emit_missing_links(const View &v, const MissingLink *recs, size_t n, std::s
 // slow_odgi/slow_odgi/degree.py:7, 17
 void emit_degree(const View &v, const uint64_t *degree, std::string *out);
 
+// The chunks GAF text travels to the device in (the pangenotype matrix and the GAF lookup: DESIGN.md sections 9 and 11), appended
+// to `pieces` as [begin, end): each ends just behind a '\n' and is at most `target` bytes long unless one line is longer, which
+// grows it to that line's end.  They tile the text up to its last '\n'; what follows that is no line and is in no piece (no '\n'
+// at all: no piece).
+void cut_lines(const uint8_t *text, size_t len, size_t target, std::vector<std::pair<size_t, size_t>> *pieces);
+
 // The synthetic-graph generator of SURVEY.md 8(d) (spec: oracle/synth.py).
 // model 0 = pangenome, 1 = uniform, 2 = chromosome, 3 = haplotype (oracle/synth.py has the spec).
 void synth_store(uint64_t seed, uint32_t S, uint32_t P, uint32_t L, int model, bool with_seq, Store *out);

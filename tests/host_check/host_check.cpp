@@ -8,11 +8,16 @@
 //
 //   host_check FILE.gfa ...     prints one digest line per phase; the digests of a sanitized build must
 //                               equal those of the plain build (the test compares them).
+//   host_check --cut-lines TARGET FILE
+//                               prints the pieces cut_lines makes of FILE's bytes, one "begin end" per line
+//                               (tests/test_cut_lines.py compares them with its own chunker).
 // No depth is computed here (the product has no CPU depth path): the emitters get made-up counts.
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../pollen_amd/csrc/flatgfa_core.hpp"
@@ -100,7 +105,36 @@ static uint64_t exercise(const Store &st, uint64_t h) {
     return h;
 }
 
+// What cut_lines promises, checked on one text; false with a word on stderr where it does not hold.
+static bool cut_lines_sound(const std::string &t, size_t target, const std::vector<std::pair<size_t, size_t>> &pieces) {
+    const size_t last = t.rfind('\n'), end = last == std::string::npos ? 0 : last + 1;
+    size_t at = 0;
+    for (const auto &pc : pieces) {
+        const bool tiles = pc.first == at && pc.second > pc.first && pc.second <= end && t[pc.second - 1] == '\n';
+        // longer than the target: one line and nothing else
+        const bool fits = tiles && (pc.second - pc.first <= target || t.find('\n', pc.first) == pc.second - 1);
+        if (!fits) {
+            fprintf(stderr, "host_check: cut_lines: piece [%zu, %zu) of a text of %zu bytes, target %zu\n", pc.first, pc.second, t.size(), target);
+            return false;
+        }
+        at = pc.second;
+    }
+    if (at != end) fprintf(stderr, "host_check: cut_lines: the pieces end at %zu, the last line at %zu\n", at, end);
+    return at == end;
+}
+
 int main(int argc, char **argv) {
+    if (argc == 4 && !strcmp(argv[1], "--cut-lines")) {
+        std::string t;
+        if (!slurp(argv[3], &t)) {
+            fprintf(stderr, "host_check: cannot read %s\n", argv[3]);
+            return 2;
+        }
+        std::vector<std::pair<size_t, size_t>> pieces;
+        cut_lines((const uint8_t *)t.data(), t.size(), (size_t)strtoull(argv[2], nullptr, 10), &pieces);
+        for (const auto &pc : pieces) printf("%zu %zu\n", pc.first, pc.second);
+        return 0;
+    }
     uint64_t all = 0xcbf29ce484222325ull;
     std::vector<std::string> texts;
     for (int i = 1; i < argc; ++i) {
@@ -293,6 +327,35 @@ int main(int argc, char **argv) {
         h = fnv(h, tab.data(), tab.size());
     }
     printf("threads %016llx\n", (unsigned long long)h);
+    all = fnv(all, &h, 8);
+    // 6. the GAF chunker: texts of short, empty and long lines, from heap blocks of their exact size (a read past either end
+    //    is a finding), at targets from one byte to more than the text
+    h = 0xcbf29ce484222325ull;
+    size_t n_pieces = 0;
+    for (int round = 0; round < 400; ++round) {
+        std::string t;
+        const size_t lines = rng(seed) % 12;
+        for (size_t l = 0; l < lines; ++l) {
+            const size_t kind = rng(seed) % 4;
+            t.append(kind == 0 ? 0 : kind == 1 ? rng(seed) % 8 : kind == 2 ? rng(seed) % 40 : rng(seed) % 300, 'x');
+            t.push_back('\n');
+        }
+        if (round % 3 == 0) t.append(rng(seed) % 20, 'y');  // a tail that is no line
+        const size_t targets[] = {1, 2, 1 + (size_t)(rng(seed) % 64), t.size(), t.size() + 1, (size_t)64 << 20};
+        for (size_t target : targets) {
+            if (!target) continue;
+            std::vector<uint8_t> exact(t.begin(), t.end());
+            std::vector<std::pair<size_t, size_t>> pieces;
+            cut_lines(exact.data(), exact.size(), target, &pieces);
+            if (!cut_lines_sound(t, target, pieces)) return 4;
+            n_pieces += pieces.size();
+            for (const auto &pc : pieces) {
+                const uint64_t be[2] = {pc.first, pc.second};
+                h = fnv(h, be, sizeof be);
+            }
+        }
+    }
+    printf("cut_lines %016llx pieces=%zu\n", (unsigned long long)h, n_pieces);
     all = fnv(all, &h, 8);
     printf("all %016llx\n", (unsigned long long)all);
     return 0;

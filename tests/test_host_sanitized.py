@@ -4,8 +4,8 @@
 flatgfa_core.cpp + synth.cpp three ways: plain, AddressSanitizer + UBSan (-fno-sanitize-recover), and
 ThreadSanitizer.  The driver parses every golden fixture (both parser modes), hundreds of mutated
 texts and damaged .flatgfa images (from an odd address: the reference's pools are align-1,
-file.rs:163-167), round-trips them through the printer and both containers, and runs the threaded
-step-list parse and the table formatter's threads.  All three builds must finish clean and print
+file.rs:163-167), round-trips them through the printer and both containers, runs the threaded
+step-list parse and the table formatter's threads, and cuts made-up GAF texts into chunks (cut_lines).  All three builds must finish clean and print
 the same digests."""
 import glob
 import os
@@ -38,8 +38,8 @@ def test_sanitized_builds_are_clean_and_agree(binaries):
     plain = run(binaries["plain"])
     assert plain.returncode == 0, plain.stderr
     lines = plain.stdout.strip().splitlines()
-    assert [ln.split()[0] for ln in lines] == ["fixtures", "mutated_texts", "damaged_images", "bed_and_floats", "threads", "all"]
-    assert "accepted=" in lines[1] and "refused=" in lines[2]
+    assert [ln.split()[0] for ln in lines] == ["fixtures", "mutated_texts", "damaged_images", "bed_and_floats", "threads", "cut_lines", "all"]
+    assert "accepted=" in lines[1] and "refused=" in lines[2] and "pieces=" in lines[5]
     for kind in ("asan", "tsan"):
         r = run(binaries[kind])
         assert r.returncode == 0, f"{kind}: {r.stderr[-3000:]}"
