@@ -302,15 +302,6 @@ extern "C" int flatgfa_dev_path_overlaps_impl(const flatgfa_dev_graph_t *g, int 
                                               uint32_t **qbits_cache, size_t *qbits_bytes, bool *qbits_all, const uint32_t *query_ids, uint32_t n_q, uint8_t *touch_out,
                                               uint32_t *status, hipStream_t stream);
 
-#define HIP_TRY(expr, fail_stmt)                                                            \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-            fail_stmt;                                                                      \
-        }                                                                                   \
-    } while (0)
-
 static int atomic_seg_depth(flatgfa_dev_plan_t *pl, uint32_t *depth_out, uint32_t *uniq_out, hipStream_t stream);
 
 static flatgfa_dev_plan_t *plan_create_impl(const flatgfa_dev_graph_t *g, const uint32_t *hb, const uint32_t *he, uint32_t scan_workgroups,
@@ -395,18 +386,10 @@ static void marks_poll(flatgfa_dev_plan_t *pl, bool wait) {
 }
 static void marks_start(flatgfa_dev_plan_t *pl) {
     if (!pl->fast.eligible) return;
-    bool any = pl->fast.marks_wanted;
-    for (uint32_t r = 0; r < pl->fast.n_more; ++r) any = any || pl->fast.more[r].marks_wanted;
-    if (!any) return;
+    if (!any_range(pl->fast, [](const FastPlan &q) { return q.marks_wanted; })) return;
     // (the job's scratch and stream belong to the plan's device, whatever device the calling thread has current)
-    int cur = pl->device;
-    if (hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); return; }
-    struct Restore {
-        int dev;
-        bool on;
-        ~Restore() { if (on) (void)hipSetDevice(dev); }
-    } restore{cur, cur != pl->device};
-    if (restore.on && hipSetDevice(pl->device) != hipSuccess) { (void)hipGetLastError(); restore.on = false; return; }
+    DeviceGuard guard;
+    if (guard.dev < 0 || !guard.switch_to(pl->device)) { (void)hipGetLastError(); return; }
     if (!pl->side) {  // (one such stream per device for the whole process: creating a stream costs as much as the first answer)
         static std::mutex mu;
         static hipStream_t pool[64] = {};
@@ -427,72 +410,267 @@ static void marks_start(flatgfa_dev_plan_t *pl) {
     }
 }
 
-// What a plan is beyond its handle: the bucketed path's plan (which kernel walks which path, the scratch), sized and
-// timed on the graph.  Everything runs on the null stream.  With `first_depth` the query that sizes the record buckets
-// leaves its result in the caller's buffers (and every timing run behind it writes the same counts there): the plan's
-// creation IS the first query.  *first_st: the status bits that query raised (1 = an id out of range).
-static bool plan_build_fast(flatgfa_dev_plan_t *pl, uint32_t *first_depth, uint32_t *first_uniq, uint32_t *first_st) {
+// ---- the stages of a plan's creation (plan_build_fast runs them in this order) ----
+
+// Steps kept in the Infinity Cache.  k_scan streams the steps past the caches (nt: whole lines read once),
+// which is right for what does not fit them -- but a resident graph is queried again and again, and the
+// first so-many megabytes of its steps, read WITHOUT the hint, are still in the 256 MiB cache when the next
+// call comes (the nt reads of the rest hit there but do not allocate, so they do not push it out): cfg-L's
+// k_scan 102 -> 88 us with 160 MB.  Only as much as the call's other traffic leaves room for -- its
+// records are written and read back through the same cache (8 bytes each), its results written (8
+// bytes per segment): a graph of 64 M segments has none to spare and would pay 12 % for the lines the
+// plain reads push out of the L2 -- and only what the device's other plans have not claimed.
+// FLATGFA_MALL_MB=n pins the amount (0: none).
+static void claim_cache(flatgfa_dev_plan_t *pl) {
     const flatgfa_dev_graph_t *g = &pl->g;
-    const uint32_t *hb = pl->hb.data(), *he = pl->he.data();
-    const uint32_t scan_workgroups = pl->scan_workgroups;
-    const auto tick = [](const char *what) { plan_tick(what); };
+    if (!(pl->fast.eligible && g->n_steps && pl->fast.n_items)) return;  // (k_scan's reads: the wave-per-path kernels and the partition read plainly anyway)
+    uint64_t records = 0;
+    for_each_range(pl->fast, [&](const FastPlan &q) { records += q.est_records; });
+    int64_t budget = (244ll << 20) - 8ll * (int64_t)g->n_segs - 8ll * (int64_t)records;
+    budget = std::min<int64_t>(budget, 160ll << 20);
+    if (const char *f = getenv("FLATGFA_MALL_MB")) budget = (int64_t)strtoull(f, nullptr, 10) << 20;
+    budget = std::min<int64_t>(budget, (int64_t)g->n_steps * 4);
+    {
+        std::lock_guard<std::mutex> lk(g_cache_mu);
+        const bool pinned = getenv("FLATGFA_MALL_MB") != nullptr;  // (the thresholds below are the plan's own rule: a pinned amount is taken as given)
+        CacheShare *share = nullptr;
+        for (CacheShare &c : g_cache_shares)
+            if (c.device == pl->device && c.steps == g->steps) share = &c;
+        if (pl->device < 0 || pl->device >= 64) {
+            budget = 0;
+        } else if (share && !pinned) {  // another plan keeps this array's first bytes resident already: the same stretch, no second claim
+            budget = std::min<int64_t>(share->bytes, (int64_t)g->n_steps * 4);
+            share->users += 1;
+            pl->cache_claim = share->bytes;
+            pl->cache_claim_shared = true;
+        } else {
+            if (!pinned) {
+                budget = std::min<int64_t>(budget, (160ll << 20) - g_cache_claimed[pl->device]);
+                if (budget < (32ll << 20) || (int64_t)g->n_steps * 4 < (64ll << 20)) budget = 0;  // (not worth the L2 lines; graphs of a few million steps are launch-bound anyway)
+            }
+            budget = std::max<int64_t>(budget, 0);
+            g_cache_claimed[pl->device] += budget;
+            pl->cache_claim = budget;
+            if (budget && !pinned) {
+                g_cache_shares.push_back(CacheShare{pl->device, g->steps, budget, 1});
+                pl->cache_claim_shared = true;
+            }
+        }
+    }
+    for_each_range(pl->fast, [&](FastPlan &q) { q.mall_steps = (uint64_t)budget / 4; });
+}
+
+// What the sizing query and the trials of a plan's creation write: the caller's buffers (the first answer) or scratch.
+struct TrialOutputs {
+    uint32_t *depth, *uniq;
+};
+static int bucketed_query(flatgfa_dev_plan_t *pl, const TrialOutputs &out) {
+    return fast_seg_depth(pl->fast, pl->g, out.depth, out.uniq, pl->status, nullptr);
+}
+
+// An even layout -- every sub-bucket as deep as the fullest -- that had to grow to gigabytes (paths that run along
+// the graph fill a few sub-buckets of a window and leave the others empty: 2000 contigs of 100 k steps on 4 M
+// segments, 0.8 GB of steps, 4.8 GB of buckets): the plan is made again with its buckets laid out to the count.
+// 1: made again (and to be sized again), 0: the plan stays as it is, -1: a HIP error.
+static int remake_with_packed_buckets(flatgfa_dev_plan_t *pl) {
+    if (!pl->fast.eligible || getenv("FLATGFA_PACKED")) return 0;
+    uint64_t even_bytes = 0;
+    for_each_range(pl->fast, [&](const FastPlan &q) { if (!q.packed) even_bytes += ((uint64_t)q.n_win + 1) * q.n_slots * q.cap * 4; });
+    if (even_bytes <= (2ull << 30)) return 0;
+    // (a plan that cannot have packed buckets -- paths that single waves walk, pass 1 by partition -- is not made again to find
+    // that out: a million tiny paths paid 12 ms of their 25 for it)
+    if (!all_ranges(pl->fast, [](const FastPlan &q) { return q.can_pack; })) return 0;
+    FastPlan again;
+    if (!fast_plan_create(pl->g, pl->hb.data(), pl->he.data(), &again, pl->scan_workgroups, true)) return -1;
+    if (!(again.eligible && all_ranges(again, [](const FastPlan &q) { return q.packed; }))) {
+        fast_plan_destroy(&again);
+        return 0;
+    }
+    for_each_range(again, [&](FastPlan &q) { q.mall_steps = pl->fast.mall_steps; });
+    plan_tick("the plan made again with packed buckets");
+    fast_plan_destroy(&pl->fast);
+    pl->fast = again;
+    plan_tick("the even plan's scratch freed");
+    return 1;
+}
+
+// Sizes the sub-buckets for this graph with one query into `out`, so that no later call runs out of room (the record
+// counts per sub-bucket depend on the steps only): a caller that consumes results on the stream -- an all-reduce right
+// behind the kernels -- never sees an incomplete vector.  *complete: `out` holds a whole query's counts.  False on a HIP error.
+static bool size_buckets(flatgfa_dev_plan_t *pl, const TrialOutputs &out, uint32_t *first_st, bool *complete) {
+    *complete = false;
+    for (int layout = 0; layout < 2; ++layout) {
+        for (int attempt = 0; attempt < 10 && pl->fast.eligible; ++attempt) {
+            uint32_t st = 0;
+            if (bucketed_query(pl, out) != FLATGFA_OK || hipMemcpy(&st, pl->status, 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemset(pl->status, 0, 4) != hipSuccess)
+                return false;
+            *first_st |= st & 1u;
+            *complete = !(st & (4u | 16u));
+            if (!(st & 4u)) break;  // (an out-of-range id is reported by the query that meets it)
+            (void)fast_plan_grow(&pl->fast);
+        }
+        plan_tick("sizing query");
+        {   // ... and with headroom: k_scan deals its items to the workgroups as they come, so another call may
+            // fill a sub-bucket that was half full this time to the brim (see flatgfa_dev_status)
+            uint32_t fullest = 0;
+            if (hipMemcpy(&fullest, pl->status + 2, 4, hipMemcpyDeviceToHost) == hipSuccess && fullest && pl->fast.eligible) (void)fast_plan_grow(&pl->fast, true);
+            (void)hipMemset(pl->status, 0, 12);
+        }
+        plan_tick("headroom");
+        if (layout != 0) break;
+        const int again = remake_with_packed_buckets(pl);
+        if (again < 0) return false;
+        if (!again) break;
+    }
+    return true;
+}
+
+// One timed choice between two variants of a query.  Each variant runs `reps` times on the null stream between two events,
+// the variants taking turns (or, variant_outer, all of variant 0 before all of variant 1); best[v] is variant v's fastest
+// repetition, its first left out.  set(v) shapes the plan for variant v, run(v) enqueues the query.  The status word is
+// cleared behind the trial (what a repetition raised shows up again in the caller's own query).
+struct Trial {
+    bool ok = false;                  // every call of the runtime succeeded: best[] can be compared
+    float best[2] = {1e30f, 1e30f};   // ms
+};
+struct TrialEvents {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool ok;
+    TrialEvents() { ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess; }
+    ~TrialEvents() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+template <class SetFn, class RunFn>
+static Trial time_two_ways(uint32_t *status, int reps, bool variant_outer, SetFn set, RunFn run) {
+    Trial t;
+    {
+        TrialEvents ev;
+        t.ok = ev.ok;
+        for (int i = 0; i < 2 * reps && t.ok; ++i) {
+            const int which = variant_outer ? i / reps : i % 2, rep = variant_outer ? i % reps : i / 2;
+            set(which != 0);
+            t.ok = hipEventRecord(ev.e0, nullptr) == hipSuccess;
+            const int rc = run(which != 0);
+            float ms = 0;
+            t.ok = t.ok && rc == FLATGFA_OK && hipEventRecord(ev.e1, nullptr) == hipSuccess && hipEventSynchronize(ev.e1) == hipSuccess &&
+                   hipEventElapsedTime(&ms, ev.e0, ev.e1) == hipSuccess;
+            if (t.ok && rep) t.best[which] = std::min(t.best[which], ms);
+        }
+    }
+    (void)hipMemset(status, 0, 4);
+    return t;
+}
+
+// More than a record for two steps: pass 1 by partition (k_scan_dense) may beat pass 1 by runs.
+// The plan was sized for it (it makes the most records); now both are timed.
+static void choose_pass1(flatgfa_dev_plan_t *pl, const TrialOutputs &out) {
+    const auto maybe = [](const FastPlan &q) { return q.dense_maybe; };
+    const auto set_dense = [&](bool on) { for_each_range(pl->fast, [&](FastPlan &q) { q.dense = on; }); };
+    if (pl->fast.eligible && all_ranges(pl->fast, maybe)) {
+        const Trial t = time_two_ways(pl->status, 3, false, set_dense, [&](bool) { return bucketed_query(pl, out); });
+        set_dense(t.ok && t.best[1] < t.best[0]);
+        if (getenv("FLATGFA_TIMING")) fprintf(stderr, "plan: pass 1 by runs %.1f us, by partition %.1f us\n", t.best[0] * 1e3, t.best[1] * 1e3);
+    } else if (pl->fast.eligible && any_range(pl->fast, maybe)) {  // (ranges that disagree: all of them by runs, nothing left at an untimed default)
+        for_each_range(pl->fast, [](FastPlan &q) { q.dense = q.dense && !q.dense_maybe; });
+    }
+}
+
+// Pass 2 can look, before it maps a step's 64 records to their items, whether the step lies
+// inside the item of the step before: a win where a path has hundreds of records per window
+// (paths along the graph: -10 %; ids without runs: -35 %), a few instructions lost where it
+// has a dozen (+4 %).  Timed on this graph, both ways.
+static void choose_item_shortcut(flatgfa_dev_plan_t *pl, const TrialOutputs &out) {
+    const auto set_big = [&](bool on) { for_each_range(pl->fast, [&](FastPlan &q) { q.big_groups = on; }); };
+    if (pl->fast.eligible && !pl->fast.tagged && !test_hook("FLATGFA_BIG_GROUPS")) {  // (a tagged plan walks sub-buckets, not items)
+        const Trial t = time_two_ways(pl->status, 3, false, set_big, [&](bool) { return bucketed_query(pl, out); });
+        set_big(t.ok && t.best[1] * 1.02f < t.best[0]);  // (it has to win by more than the noise of two runs)
+        if (getenv("FLATGFA_TIMING")) fprintf(stderr, "plan: pass 2 item by item %.1f us, with the one-item shortcut %.1f us\n", t.best[0] * 1e3, t.best[1] * 1e3);
+    } else if (const char *f = test_hook("FLATGFA_BIG_GROUPS")) {
+        set_big(strtol(f, nullptr, 10) != 0);
+    }
+}
+
+// Pass 2 of a tagged call can keep track of which tag owns each of a wave's bitsets (k_accum<..., OWN>): where a pass-1
+// workgroup takes hundreds of items of which a window sees a few -- tags twenty apart in a sub-bucket -- every step of
+// 64 records holds several, and the plain walk claims them one stretch after the other (160 000 contigs on 16 M
+// segments: pass 2 2.48 -> 1.62 ms); where the tags are dense it costs 4-9 %.  Timed on this graph, both ways, when
+// the workgroups take more items than a wave has bitsets.
+static void choose_bitset_owners(flatgfa_dev_plan_t *pl, const TrialOutputs &out) {
+    const auto many_items = [](const FastPlan &q) {
+        return q.tagged && !q.dense && (q.wb == 12 || q.wb == 13) && (uint64_t)q.n_items + q.max_back > 2ull * q.acc_slots * std::min<uint32_t>(std::max(q.n_items, 1u), q.n_slots);
+    };
+    if (!(pl->fast.eligible && any_range(pl->fast, many_items)) || test_hook("FLATGFA_ACC_OWN")) return;
+    const auto set_own = [&](bool on) { for_each_range(pl->fast, [&](FastPlan &q) { q.acc_own = on; }); };
+    const Trial t = time_two_ways(pl->status, 3, false, set_own, [&](bool) { return bucketed_query(pl, out); });
+    set_own(t.ok && t.best[1] * 1.02f < t.best[0]);  // (it has to win by more than the noise of two runs)
+    if (getenv("FLATGFA_TIMING")) fprintf(stderr, "plan: pass 2 with bitsets by tag %.1f us, by owner %.1f us\n", t.best[0] * 1e3, t.best[1] * 1e3);
+}
+
+// Small graphs are launch-bound: three kernels of the bucketed path against one of the
+// atomic path (10 k segments / 1 M steps: 76 us against 26).  Up to 8 M steps both are
+// timed here, on this graph, and the plan keeps the faster one.  FLATGFA_DEPTH_PATH=bucketed
+// (or any of the knobs that shape the bucketed path) skips the comparison.
+static void choose_bucketed_or_atomic(flatgfa_dev_plan_t *pl, const TrialOutputs &out) {
+    bool shaped = getenv("FLATGFA_DEPTH_PATH") != nullptr;
+    for (const char *k : {"FLATGFA_PIECE_STEPS", "FLATGFA_SHORT_MAX", "FLATGFA_SHORT_ANY", "FLATGFA_ACC_PARTS", "FLATGFA_RANGE_SEGS",
+#ifdef FGFA_MEASURE
+                          "FLATGFA_DEBUG_SKIP",
+#endif
+                          "FLATGFA_WB", "FLATGFA_DENSE", "FLATGFA_TAGGED", "FLATGFA_PATH_GROUPS"})
+        shaped = shaped || test_hook(k) != nullptr;
+    if (!pl->fast.eligible || shaped || pl->g.n_steps > (8u << 20)) return;
+    const Trial t = time_two_ways(pl->status, 4, true, [](bool) {}, [&](bool atomic) { return atomic ? atomic_seg_depth(pl, out.depth, out.uniq, nullptr) : bucketed_query(pl, out); });
+    // (an out-of-range id shows up again in the caller's own first query)
+    if (t.ok && t.best[1] < t.best[0]) fast_plan_destroy(&pl->fast);
+    if (getenv("FLATGFA_TIMING")) fprintf(stderr, "plan: bucketed %.1f us, atomic %.1f us\n", t.best[0] * 1e3, t.best[1] * 1e3);
+}
+
+// A device buffer that goes with its scope.
+struct DeviceScratch {
+    uint32_t *p = nullptr;
+    ~DeviceScratch() { if (p) (void)hipFree(p); }
+};
+
+// The bucketed plan sized and its open choices timed, with queries into the caller's buffers (the first answer) or into
+// scratch: size_buckets, then choose_pass1, choose_item_shortcut, choose_bitset_owners, choose_bucketed_or_atomic.
+// (FLATGFA_BUCKET_CAP keeps its forced capacity, and gets none of this: the tests want the overflow route.)
+static bool size_and_choose(flatgfa_dev_plan_t *pl, uint32_t *first_depth, uint32_t *first_uniq, uint32_t *first_st, bool *complete) {
+    const size_t n_segs = pl->g.n_segs;
+    DeviceScratch scratch;
+    uint32_t *&tmp = scratch.p;
+    const size_t need = (first_depth ? 0 : n_segs) + (first_uniq ? 0 : n_segs);
+    if (need) FGFA_HIP_OR(hipMalloc(&tmp, need * 4), return false);
+    const TrialOutputs out{first_depth ? first_depth : tmp, first_uniq ? first_uniq : (first_depth ? tmp : tmp + n_segs)};
+    if (!size_buckets(pl, out, first_st, complete)) return false;
+    choose_pass1(pl, out);
+    choose_item_shortcut(pl, out);
+    choose_bitset_owners(pl, out);
+    choose_bucketed_or_atomic(pl, out);
+    plan_tick("timed choices");
+    return true;
+}
+
+// What a plan is beyond its handle: the bucketed path's plan (which kernel walks which path, the scratch), sized and
+// timed on the graph, in stages: fast_plan_create, claim_cache, then size_and_choose's.  Everything runs on the null stream.
+// With `first_depth` the query that sizes the record buckets leaves its result in the caller's buffers (and every timing
+// run behind it writes the same counts there): the plan's creation IS the first query.  *first_st: the status bits that
+// query raised (1 = an id out of range).
+static bool plan_build_fast(flatgfa_dev_plan_t *pl, uint32_t *first_depth, uint32_t *first_uniq, uint32_t *first_st) {
     *first_st = 0;
     // FLATGFA_DEPTH_PATH=atomic forces the simple global-atomic kernels (used by the tests to
     // cover both device paths); anything else lets eligibility decide.
     const char *force = getenv("FLATGFA_DEPTH_PATH");
     if (!(force && std::string(force) == "atomic")) {
-        if (!fast_plan_create(pl->g, hb, he, &pl->fast, scan_workgroups)) return false;
+        if (!fast_plan_create(pl->g, pl->hb.data(), pl->he.data(), &pl->fast, pl->scan_workgroups)) return false;
     }
-    tick("fast_plan_create (lists, items, scratch)");
-    // Steps kept in the Infinity Cache.  k_scan streams the steps past the caches (nt: whole lines read once),
-    // which is right for what does not fit them -- but a resident graph is queried again and again, and the
-    // first so-many megabytes of its steps, read WITHOUT the hint, are still in the 256 MiB cache when the next
-    // call comes (the nt reads of the rest hit there but do not allocate, so they do not push it out): cfg-L's
-    // k_scan 102 -> 88 us with 160 MB.  Only as much as the call's other traffic leaves room for -- its
-    // records are written and read back through the same cache (8 bytes each), its results written (8
-    // bytes per segment): a graph of 64 M segments has none to spare and would pay 12 % for the lines the
-    // plain reads push out of the L2 -- and only what the device's other plans have not claimed.
-    // FLATGFA_MALL_MB=n pins the amount (0: none).
-    if (pl->fast.eligible && g->n_steps && pl->fast.n_items) {  // (k_scan's reads: the wave-per-path kernels and the partition read plainly anyway)
-        uint64_t records = pl->fast.est_records;
-        for (uint32_t r = 0; r < pl->fast.n_more; ++r) records += pl->fast.more[r].est_records;
-        int64_t budget = (244ll << 20) - 8ll * (int64_t)g->n_segs - 8ll * (int64_t)records;
-        budget = std::min<int64_t>(budget, 160ll << 20);
-        if (const char *f = getenv("FLATGFA_MALL_MB")) budget = (int64_t)strtoull(f, nullptr, 10) << 20;
-        budget = std::min<int64_t>(budget, (int64_t)g->n_steps * 4);
-        {
-            std::lock_guard<std::mutex> lk(g_cache_mu);
-            const bool pinned = getenv("FLATGFA_MALL_MB") != nullptr;  // (the thresholds below are the plan's own rule: a pinned amount is taken as given)
-            CacheShare *share = nullptr;
-            for (CacheShare &c : g_cache_shares)
-                if (c.device == pl->device && c.steps == g->steps) share = &c;
-            if (pl->device < 0 || pl->device >= 64) {
-                budget = 0;
-            } else if (share && !pinned) {  // another plan keeps this array's first bytes resident already: the same stretch, no second claim
-                budget = std::min<int64_t>(share->bytes, (int64_t)g->n_steps * 4);
-                share->users += 1;
-                pl->cache_claim = share->bytes;
-                pl->cache_claim_shared = true;
-            } else {
-                if (!pinned) {
-                    budget = std::min<int64_t>(budget, (160ll << 20) - g_cache_claimed[pl->device]);
-                    if (budget < (32ll << 20) || (int64_t)g->n_steps * 4 < (64ll << 20)) budget = 0;  // (not worth the L2 lines; graphs of a few million steps are launch-bound anyway)
-                }
-                budget = std::max<int64_t>(budget, 0);
-                g_cache_claimed[pl->device] += budget;
-                pl->cache_claim = budget;
-                if (budget && !pinned) {
-                    g_cache_shares.push_back(CacheShare{pl->device, g->steps, budget, 1});
-                    pl->cache_claim_shared = true;
-                }
-            }
-        }
-        pl->fast.mall_steps = (uint64_t)budget / 4;
-        for (uint32_t r = 0; r < pl->fast.n_more; ++r) pl->fast.more[r].mall_steps = pl->fast.mall_steps;
-    }
+    plan_tick("fast_plan_create (lists, items, scratch)");
+    claim_cache(pl);
     // A caller that wants its first answer from the atomic kernels' plan gets it here.
     const auto atomic_first = [&]() -> bool {
-        if (!first_depth || !g->n_segs) return true;
+        if (!first_depth || !pl->g.n_segs) return true;
         uint32_t st = 0;
         if (atomic_seg_depth(pl, first_depth, first_uniq, nullptr) != FLATGFA_OK || hipMemcpy(&st, pl->status, 4, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemset(pl->status, 0, 4) != hipSuccess)
@@ -500,222 +678,16 @@ static bool plan_build_fast(flatgfa_dev_plan_t *pl, uint32_t *first_depth, uint3
         *first_st |= st;
         return true;
     };
-    // Size the sub-buckets for this graph now, with one query into scratch outputs (or the caller's: the first
-    // answer), so that no later call runs out of room (the record counts per sub-bucket depend on the steps only):
-    // a caller that consumes results on the stream -- an all-reduce right behind the kernels --
-    // never sees an incomplete vector.  (FLATGFA_BUCKET_CAP keeps its forced capacity: the
-    // tests want the overflow route.)
-    if (pl->fast.eligible && !pl->fast.cap_forced && g->n_segs) {
-        uint32_t *tmp = nullptr;
-        const size_t need = (first_depth ? 0 : (size_t)g->n_segs) + (first_uniq ? 0 : (size_t)g->n_segs);
-        if (need) HIP_TRY(hipMalloc(&tmp, need * 4), return false);
-        uint32_t *const out_d = first_depth ? first_depth : tmp;
-        uint32_t *const out_u = first_uniq ? first_uniq : (first_depth ? tmp : tmp + g->n_segs);
-        bool complete = false;  // the outputs hold a whole query's counts
-        for (int layout = 0; layout < 2; ++layout) {
-        for (int attempt = 0; attempt < 10 && pl->fast.eligible; ++attempt) {
-            uint32_t st = 0;
-            if (fast_seg_depth(pl->fast, pl->g, out_d, out_u, pl->status, nullptr) != FLATGFA_OK ||
-                hipMemcpy(&st, pl->status, 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemset(pl->status, 0, 4) != hipSuccess) {
-                if (tmp) (void)hipFree(tmp);
-                return false;
-            }
-            *first_st |= st & 1u;
-            complete = !(st & (4u | 16u));
-            if (!(st & 4u)) break;  // (an out-of-range id is reported by the query that meets it)
-            (void)fast_plan_grow(&pl->fast);
-        }
-        tick("sizing query");
-        {   // ... and with headroom: k_scan deals its items to the workgroups as they come, so another call may
-            // fill a sub-bucket that was half full this time to the brim (see flatgfa_dev_status)
-            uint32_t fullest = 0;
-            if (hipMemcpy(&fullest, pl->status + 2, 4, hipMemcpyDeviceToHost) == hipSuccess && fullest && pl->fast.eligible) (void)fast_plan_grow(&pl->fast, true);
-            (void)hipMemset(pl->status, 0, 12);
-        }
-        tick("headroom");
-        // An even layout -- every sub-bucket as deep as the fullest -- that had to grow to gigabytes (paths that run along
-        // the graph fill a few sub-buckets of a window and leave the others empty: 2000 contigs of 100 k steps on 4 M
-        // segments, 0.8 GB of steps, 4.8 GB of buckets): the plan is made again with its buckets laid out to the count.
-        if (layout == 0 && pl->fast.eligible && !getenv("FLATGFA_PACKED")) {
-            uint64_t even_bytes = 0;
-            const auto add = [&](const FastPlan &q) { if (!q.packed) even_bytes += ((uint64_t)q.n_win + 1) * q.n_slots * q.cap * 4; };
-            add(pl->fast);
-            for (uint32_t r = 0; r < pl->fast.n_more; ++r) add(pl->fast.more[r]);
-            if (even_bytes <= (2ull << 30)) break;
-            // (a plan that cannot have packed buckets -- paths that single waves walk, pass 1 by partition -- is not made again to find
-            // that out: a million tiny paths paid 12 ms of their 25 for it)
-            bool could = pl->fast.can_pack;
-            for (uint32_t r = 0; r < pl->fast.n_more; ++r) could = could && pl->fast.more[r].can_pack;
-            if (!could) break;
-            FastPlan again;
-            if (!fast_plan_create(pl->g, hb, he, &again, scan_workgroups, true)) { if (tmp) (void)hipFree(tmp); return false; }
-            bool all_packed = again.eligible && again.packed;
-            for (uint32_t r = 0; r < again.n_more; ++r) all_packed = all_packed && again.more[r].packed;
-            if (!all_packed) {
-                fast_plan_destroy(&again);
-                break;
-            }
-            again.mall_steps = pl->fast.mall_steps;
-            for (uint32_t r = 0; r < again.n_more; ++r) again.more[r].mall_steps = again.mall_steps;
-            tick("the plan made again with packed buckets");
-            fast_plan_destroy(&pl->fast);
-            pl->fast = again;
-            tick("the even plan's scratch freed");
-        } else {
-            break;
-        }
-        }
-        // More than a record for two steps: pass 1 by partition (k_scan_dense) may beat pass 1 by runs.
-        // The plan was sized for it (it makes the most records); now both are timed.
-        {
-            bool maybe = pl->fast.eligible && pl->fast.dense_maybe, any_maybe = maybe;  // all ranges / some range
-            for (uint32_t r = 0; r < pl->fast.n_more; ++r) {
-                maybe = maybe && pl->fast.more[r].dense_maybe;
-                any_maybe = any_maybe || (pl->fast.eligible && pl->fast.more[r].dense_maybe);
-            }
-            if (maybe) {
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                float best[2] = {1e30f, 1e30f};
-                bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-                const auto set_dense = [&](bool on) {
-                    pl->fast.dense = on;
-                    for (uint32_t r = 0; r < pl->fast.n_more; ++r) pl->fast.more[r].dense = on;
-                };
-                for (int rep = 0; rep < 3 && ok; ++rep) {
-                    for (int which = 0; which < 2 && ok; ++which) {
-                        set_dense(which != 0);
-                        ok = hipEventRecord(e0, nullptr) == hipSuccess;
-                        const int rc = fast_seg_depth(pl->fast, pl->g, out_d, out_u, pl->status, nullptr);
-                        float ms = 0;
-                        ok = ok && rc == FLATGFA_OK && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-                             hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-                        if (ok && rep) best[which] = std::min(best[which], ms);
-                    }
-                }
-                if (e0) (void)hipEventDestroy(e0);
-                if (e1) (void)hipEventDestroy(e1);
-                (void)hipMemset(pl->status, 0, 4);
-                set_dense(ok && best[1] < best[0]);
-                if (getenv("FLATGFA_TIMING")) fprintf(stderr, "plan: pass 1 by runs %.1f us, by partition %.1f us\n", best[0] * 1e3, best[1] * 1e3);
-            } else if (any_maybe) {  // (ranges that disagree: all of them by runs, nothing left at an untimed default)
-                pl->fast.dense = pl->fast.dense && !pl->fast.dense_maybe;
-                for (uint32_t r = 0; r < pl->fast.n_more; ++r) pl->fast.more[r].dense = pl->fast.more[r].dense && !pl->fast.more[r].dense_maybe;
-            }
-        }
-        // Pass 2 can look, before it maps a step's 64 records to their items, whether the step lies
-        // inside the item of the step before: a win where a path has hundreds of records per window
-        // (paths along the graph: -10 %; ids without runs: -35 %), a few instructions lost where it
-        // has a dozen (+4 %).  Timed on this graph, both ways.
-        if (pl->fast.eligible && !pl->fast.tagged && !test_hook("FLATGFA_BIG_GROUPS")) {  // (a tagged plan walks sub-buckets, not items)
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            float best[2] = {1e30f, 1e30f};
-            bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-            for (int rep = 0; rep < 3 && ok; ++rep) {
-                for (int which = 0; which < 2 && ok; ++which) {
-                    pl->fast.big_groups = which != 0;
-                    for (uint32_t r = 0; r < pl->fast.n_more; ++r) pl->fast.more[r].big_groups = which != 0;
-                    ok = hipEventRecord(e0, nullptr) == hipSuccess;
-                    const int rc = fast_seg_depth(pl->fast, pl->g, out_d, out_u, pl->status, nullptr);
-                    float ms = 0;
-                    ok = ok && rc == FLATGFA_OK && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-                         hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-                    if (ok && rep) best[which] = std::min(best[which], ms);
-                }
-            }
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-            (void)hipMemset(pl->status, 0, 4);
-            const bool big = ok && best[1] * 1.02f < best[0];  // (it has to win by more than the noise of two runs)
-            pl->fast.big_groups = big;
-            for (uint32_t r = 0; r < pl->fast.n_more; ++r) pl->fast.more[r].big_groups = big;
-            if (getenv("FLATGFA_TIMING")) fprintf(stderr, "plan: pass 2 item by item %.1f us, with the one-item shortcut %.1f us\n", best[0] * 1e3, best[1] * 1e3);
-        } else if (const char *f = test_hook("FLATGFA_BIG_GROUPS")) {
-            pl->fast.big_groups = strtol(f, nullptr, 10) != 0;
-            for (uint32_t r = 0; r < pl->fast.n_more; ++r) pl->fast.more[r].big_groups = pl->fast.big_groups;
-        }
-        // Pass 2 of a tagged call can keep track of which tag owns each of a wave's bitsets (k_accum<..., OWN>): where a pass-1
-        // workgroup takes hundreds of items of which a window sees a few -- tags twenty apart in a sub-bucket -- every step of
-        // 64 records holds several, and the plain walk claims them one stretch after the other (160 000 contigs on 16 M
-        // segments: pass 2 2.48 -> 1.62 ms); where the tags are dense it costs 4-9 %.  Timed on this graph, both ways, when
-        // the workgroups take more items than a wave has bitsets.
-        {
-            const auto many_items = [](const FastPlan &q) {
-                return q.tagged && !q.dense && (q.wb == 12 || q.wb == 13) && (uint64_t)q.n_items + q.max_back > 2ull * q.acc_slots * std::min<uint32_t>(std::max(q.n_items, 1u), q.n_slots);
-            };
-            bool any = pl->fast.eligible && many_items(pl->fast);
-            for (uint32_t r = 0; r < pl->fast.n_more; ++r) any = any || (pl->fast.eligible && many_items(pl->fast.more[r]));
-            const auto set_own = [&](bool on) {
-                pl->fast.acc_own = on;
-                for (uint32_t r = 0; r < pl->fast.n_more; ++r) pl->fast.more[r].acc_own = on;
-            };
-            if (any && !test_hook("FLATGFA_ACC_OWN")) {
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                float best[2] = {1e30f, 1e30f};
-                bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-                for (int rep = 0; rep < 3 && ok; ++rep) {
-                    for (int which = 0; which < 2 && ok; ++which) {
-                        set_own(which != 0);
-                        ok = hipEventRecord(e0, nullptr) == hipSuccess;
-                        const int rc = fast_seg_depth(pl->fast, pl->g, out_d, out_u, pl->status, nullptr);
-                        float ms = 0;
-                        ok = ok && rc == FLATGFA_OK && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-                             hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-                        if (ok && rep) best[which] = std::min(best[which], ms);
-                    }
-                }
-                if (e0) (void)hipEventDestroy(e0);
-                if (e1) (void)hipEventDestroy(e1);
-                (void)hipMemset(pl->status, 0, 4);
-                set_own(ok && best[1] * 1.02f < best[0]);  // (it has to win by more than the noise of two runs)
-                if (getenv("FLATGFA_TIMING")) fprintf(stderr, "plan: pass 2 with bitsets by tag %.1f us, by owner %.1f us\n", best[0] * 1e3, best[1] * 1e3);
-            }
-        }
-        // Small graphs are launch-bound: three kernels of the bucketed path against one of the
-        // atomic path (10 k segments / 1 M steps: 76 us against 26).  Up to 8 M steps both are
-        // timed here, on this graph, and the plan keeps the faster one.  FLATGFA_DEPTH_PATH=bucketed
-        // (or any of the knobs that shape the bucketed path) skips the comparison.
-        bool shaped = force != nullptr;
-        for (const char *k : {"FLATGFA_PIECE_STEPS", "FLATGFA_SHORT_MAX", "FLATGFA_SHORT_ANY", "FLATGFA_ACC_PARTS", "FLATGFA_RANGE_SEGS",
-#ifdef FGFA_MEASURE
-                              "FLATGFA_DEBUG_SKIP",
-#endif
-                              "FLATGFA_WB", "FLATGFA_DENSE", "FLATGFA_TAGGED", "FLATGFA_PATH_GROUPS"})
-            shaped = shaped || test_hook(k) != nullptr;
-        if (pl->fast.eligible && !shaped && g->n_steps <= (8u << 20)) {
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            float best[2] = {1e30f, 1e30f};
-            bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-            for (int which = 0; which < 2 && ok; ++which) {
-                for (int rep = 0; rep < 4 && ok; ++rep) {
-                    ok = hipEventRecord(e0, nullptr) == hipSuccess;
-                    const int rc = which ? atomic_seg_depth(pl, out_d, out_u, nullptr)
-                                         : fast_seg_depth(pl->fast, pl->g, out_d, out_u, pl->status, nullptr);
-                    float ms = 0;
-                    ok = ok && rc == FLATGFA_OK && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-                         hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-                    if (ok && rep) best[which] = std::min(best[which], ms);
-                }
-            }
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-            (void)hipMemset(pl->status, 0, 4);  // (an out-of-range id shows up again in the caller's own first query)
-            if (ok && best[1] < best[0]) fast_plan_destroy(&pl->fast);
-            if (getenv("FLATGFA_TIMING")) fprintf(stderr, "plan: bucketed %.1f us, atomic %.1f us\n", best[0] * 1e3, best[1] * 1e3);
-        }
-        tick("timed choices");
-        if (tmp) (void)hipFree(tmp);
-        // (a plan that could not be given room -- it then runs the atomic kernels -- left an incomplete vector behind)
-        if (!complete && !atomic_first()) return false;
-    } else if (!atomic_first()) {
-        return false;
-    }
+    bool complete = false;  // the caller's buffers hold a whole query's counts
+    if (pl->fast.eligible && !pl->fast.cap_forced && pl->g.n_segs && !size_and_choose(pl, first_depth, first_uniq, first_st, &complete)) return false;
+    // (a plan that was not sized, or could not be given room -- it then runs the atomic kernels -- left no vector, or an incomplete one, behind)
+    if (!complete && !atomic_first()) return false;
     // Everything above went through the null stream, which a caller's non-blocking stream does not
     // wait for -- and a memset of device memory need not have happened when hipMemset returns: a
     // plan without a trial call (no paths, say) could have its status words read, on the caller's
     // stream, before they were cleared (seen once: a freed block's contents taken for status bits).
     (void)hipStreamSynchronize(nullptr);
-    tick("null stream drained");
+    plan_tick("null stream drained");
     // ... and what can wait until the first answer is out -- the per-block no-claim marks -- is enqueued, on a stream of the
     // plan's own, by whatever the caller does with the plan next (marks_poll)
     pl->marks_to_start = true;
@@ -732,8 +704,8 @@ static flatgfa_dev_plan_t *plan_create_impl(const flatgfa_dev_graph_t *g, const 
     if (g->n_paths && (!hb || !he)) {
         cb.resize(g->n_paths);
         ce.resize(g->n_paths);
-        HIP_TRY(fgfa_dev::staged_copy(cb.data(), g->path_begin, (size_t)g->n_paths * 4, hipMemcpyDeviceToHost, nullptr), return nullptr);
-        HIP_TRY(fgfa_dev::staged_copy(ce.data(), g->path_end, (size_t)g->n_paths * 4, hipMemcpyDeviceToHost, nullptr), return nullptr);
+        FGFA_HIP_OR(fgfa_dev::staged_copy(cb.data(), g->path_begin, (size_t)g->n_paths * 4, hipMemcpyDeviceToHost, nullptr), return nullptr);
+        FGFA_HIP_OR(fgfa_dev::staged_copy(ce.data(), g->path_end, (size_t)g->n_paths * 4, hipMemcpyDeviceToHost, nullptr), return nullptr);
         hb = cb.data();
         he = ce.data();
     }
@@ -753,15 +725,15 @@ static flatgfa_dev_plan_t *plan_create_impl(const flatgfa_dev_graph_t *g, const 
     pl->he.assign(he, he + g->n_paths);
     pl->scan_workgroups = scan_workgroups;
     if (const char *c = getenv("FLATGFA_CHECK_NO_CLAIM")) pl->check_facts = c[0] != '0' && c[0] != 0;
-    HIP_TRY(hipGetDevice(&pl->device), { delete pl; return nullptr; });
+    FGFA_HIP_OR(hipGetDevice(&pl->device), { delete pl; return nullptr; });
     pl->n_cus = device_cus(pl->device);
     pl->n_items = (uint32_t)items.size();
     pl->n_windows = g->n_segs ? (uint32_t)(((uint64_t)g->n_segs + kWinBits - 1) / kWinBits) : 1;
-    HIP_TRY(hipMalloc(&pl->status, 256), { delete pl; return nullptr; });
-    HIP_TRY(hipMemset(pl->status, 0, 256), { flatgfa_dev_plan_destroy(pl); return nullptr; });
+    FGFA_HIP_OR(hipMalloc(&pl->status, 256), { delete pl; return nullptr; });
+    FGFA_HIP_OR(hipMemset(pl->status, 0, 256), { flatgfa_dev_plan_destroy(pl); return nullptr; });
     if (!items.empty()) {
-        HIP_TRY(hipMalloc(&pl->items, items.size() * sizeof(WorkItem)), { flatgfa_dev_plan_destroy(pl); return nullptr; });
-        HIP_TRY(fgfa_dev::staged_copy(pl->items, items.data(), items.size() * sizeof(WorkItem), hipMemcpyHostToDevice, nullptr),
+        FGFA_HIP_OR(hipMalloc(&pl->items, items.size() * sizeof(WorkItem)), { flatgfa_dev_plan_destroy(pl); return nullptr; });
+        FGFA_HIP_OR(fgfa_dev::staged_copy(pl->items, items.data(), items.size() * sizeof(WorkItem), hipMemcpyHostToDevice, nullptr),
                 { flatgfa_dev_plan_destroy(pl); return nullptr; });
     }
     {   // (per device, like the other kernels' attributes)
@@ -798,27 +770,26 @@ static void plan_release_fast(flatgfa_dev_plan_t *pl) {
 
 extern "C" int flatgfa_dev_plan_steps_changed(flatgfa_dev_plan_t *pl, void *stream_) {
     if (!pl) { set_error("dev_plan_steps_changed: NULL plan"); return FLATGFA_ERR_ARG; }
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream_), return FLATGFA_ERR_HIP);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev), return FLATGFA_ERR_HIP);
-    if (dev != pl->device) HIP_TRY(hipSetDevice(pl->device), return FLATGFA_ERR_HIP);
+    FGFA_HIP_OR(hipStreamSynchronize((hipStream_t)stream_), return FLATGFA_ERR_HIP);
+    DeviceGuard guard;  // (every exit below leaves the caller's device current)
+    if (!guard.switch_to(pl->device)) { set_error("dev_plan_steps_changed: cannot switch to the plan's device"); return FLATGFA_ERR_HIP; }
+    fgfa_dev::TempScope temporaries;  // (as plan_create_impl: what the plan's creation takes from the thread's arena is taken back)
     plan_release_fast(pl);
-    // everything else that was derived from the step values: the overlap query's bitmaps, the (seg_len, depth) table
+    // everything else that was derived from the step values: the overlap query's bitmaps (the (seg_len, depth) table is
+    // filled anew by every call that reads it)
     for (void **p : {(void **)&pl->overlap_bits, (void **)&pl->overlap_qbits}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
     pl->overlap_qbytes = 0;
     pl->overlap_qall = false;
-    HIP_TRY(hipMemset(pl->status, 0, 256), return FLATGFA_ERR_HIP);
+    FGFA_HIP_OR(hipMemset(pl->status, 0, 256), return FLATGFA_ERR_HIP);
     pl->calls_since_status = 0;
     pl->last_fast = false;
     pl->last_depth = pl->last_uniq = nullptr;
     pl->last_len = pl->last_weighted = nullptr;
     uint32_t st = 0;
-    const bool ok = plan_build_fast(pl, nullptr, nullptr, &st);
-    if (dev != pl->device) (void)hipSetDevice(dev);
-    return ok ? FLATGFA_OK : FLATGFA_ERR_HIP;
+    return plan_build_fast(pl, nullptr, nullptr, &st) ? FLATGFA_OK : FLATGFA_ERR_HIP;
 }
 
 extern "C" void flatgfa_dev_release_scratch(void) { fgfa_dev::fast_release_scratch(); }
@@ -857,7 +828,7 @@ static int atomic_seg_depth(flatgfa_dev_plan_t *pl, uint32_t *depth_out, uint32_
                            g.path_begin, g.path_end, g.n_paths, g.n_segs, pl->n_windows, depth_out, uniq_out,
                            pl->status);
     }
-    HIP_TRY(hipGetLastError(), return FLATGFA_ERR_HIP);
+    FGFA_HIP_OR(hipGetLastError(), return FLATGFA_ERR_HIP);
     return FLATGFA_OK;
 }
 
@@ -889,7 +860,7 @@ static int path_sums_launch(flatgfa_dev_plan_t *pl, const uint32_t *path_ids, ui
     uint32_t split = std::max<uint32_t>(1u, std::min<uint32_t>(64u, (uint32_t)(pl->n_cus * 16) / n_ids));
     uint64_t jobs = (uint64_t)n_ids * split;
     uint32_t grid = (uint32_t)std::min<uint64_t>(jobs, (uint64_t)pl->n_cus * 32u);
-    if (!pl->len_depth) HIP_TRY(hipMalloc(&pl->len_depth, (size_t)std::max<uint32_t>(g.n_segs, 1u) * sizeof(uint2)), return FLATGFA_ERR_HIP);
+    if (!pl->len_depth) FGFA_HIP_OR(hipMalloc(&pl->len_depth, (size_t)std::max<uint32_t>(g.n_segs, 1u) * sizeof(uint2)), return FLATGFA_ERR_HIP);
     {
         ProfScope ps("k_pack_len_depth", stream);
         const uint32_t pgrid = std::max<uint32_t>(1u, std::min<uint32_t>((g.n_segs + 255) / 256, (uint32_t)pl->n_cus * 8u));
@@ -901,7 +872,7 @@ static int path_sums_launch(flatgfa_dev_plan_t *pl, const uint32_t *path_ids, ui
                            g.n_paths, g.n_segs, pl->len_depth, path_ids, n_ids, split, by_path,
                            (unsigned long long *)length_out, (unsigned long long *)weighted_out, pl->status);
     }
-    HIP_TRY(hipGetLastError(), return FLATGFA_ERR_HIP);
+    FGFA_HIP_OR(hipGetLastError(), return FLATGFA_ERR_HIP);
     return FLATGFA_OK;
 }
 
@@ -918,8 +889,8 @@ extern "C" int flatgfa_dev_path_sums(flatgfa_dev_plan_t *pl, const uint32_t *pat
     hipStream_t stream = (hipStream_t)stream_;
     {
         ProfScope ps("memset_path_sums", stream);
-        HIP_TRY(hipMemsetAsync(length_out, 0, (size_t)n_ids * 8, stream), return FLATGFA_ERR_HIP);
-        HIP_TRY(hipMemsetAsync(weighted_out, 0, (size_t)n_ids * 8, stream), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipMemsetAsync(length_out, 0, (size_t)n_ids * 8, stream), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipMemsetAsync(weighted_out, 0, (size_t)n_ids * 8, stream), return FLATGFA_ERR_HIP);
     }
     return path_sums_launch(pl, path_ids, n_ids, depth, length_out, weighted_out, 0u, stream);
 }
@@ -938,8 +909,8 @@ static int path_depth_all_enqueue(flatgfa_dev_plan_t *pl, uint32_t *depth_out, u
     }
     {
         ProfScope ps("memset_path_sums", stream);
-        HIP_TRY(hipMemsetAsync(length_out, 0, (size_t)g.n_paths * 8, stream), return FLATGFA_ERR_HIP);
-        HIP_TRY(hipMemsetAsync(weighted_out, 0, (size_t)g.n_paths * 8, stream), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipMemsetAsync(length_out, 0, (size_t)g.n_paths * 8, stream), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipMemsetAsync(weighted_out, 0, (size_t)g.n_paths * 8, stream), return FLATGFA_ERR_HIP);
     }
     int rc = use_fast ? fast_seg_depth(pl->fast, g, depth_out, nullptr, pl->status, stream)
                       : atomic_seg_depth(pl, depth_out, nullptr, stream);
@@ -947,8 +918,8 @@ static int path_depth_all_enqueue(flatgfa_dev_plan_t *pl, uint32_t *depth_out, u
     if (!pl->all_ids) {
         std::vector<uint32_t> ids(g.n_paths);
         for (uint32_t i = 0; i < g.n_paths; ++i) ids[i] = i;
-        HIP_TRY(hipMalloc(&pl->all_ids, (size_t)g.n_paths * 4), return FLATGFA_ERR_HIP);
-        HIP_TRY(fgfa_dev::staged_copy(pl->all_ids, ids.data(), (size_t)g.n_paths * 4, hipMemcpyHostToDevice, nullptr), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipMalloc(&pl->all_ids, (size_t)g.n_paths * 4), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(fgfa_dev::staged_copy(pl->all_ids, ids.data(), (size_t)g.n_paths * 4, hipMemcpyHostToDevice, nullptr), return FLATGFA_ERR_HIP);
     }
     return path_sums_launch(pl, pl->all_ids, g.n_paths, depth_out, length_out, weighted_out, 1u, stream);
 }
@@ -963,8 +934,8 @@ extern "C" int flatgfa_dev_path_depth_all(flatgfa_dev_plan_t *pl, uint32_t *dept
     if (g.n_paths == 0) return g.n_segs ? flatgfa_dev_seg_depth(pl, depth_out, nullptr, stream_) : FLATGFA_OK;
     if (!g.seg_len && g.n_segs) { set_error("dev_path_depth_all: graph image has no seg_len array"); return FLATGFA_ERR_ARG; }
     if (g.n_segs == 0) {
-        HIP_TRY(hipMemsetAsync(length_out, 0, (size_t)g.n_paths * 8, (hipStream_t)stream_), return FLATGFA_ERR_HIP);
-        HIP_TRY(hipMemsetAsync(weighted_out, 0, (size_t)g.n_paths * 8, (hipStream_t)stream_), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipMemsetAsync(length_out, 0, (size_t)g.n_paths * 8, (hipStream_t)stream_), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipMemsetAsync(weighted_out, 0, (size_t)g.n_paths * 8, (hipStream_t)stream_), return FLATGFA_ERR_HIP);
         return FLATGFA_OK;
     }
     marks_poll(pl, false);
@@ -996,8 +967,8 @@ extern "C" int flatgfa_dev_status(flatgfa_dev_plan_t *pl, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     for (int attempt = 0;; ++attempt) {
         uint32_t st3[3] = {0, 0, 0};  // the flags; -; the fullest sub-bucket beyond half of the capacity
-        HIP_TRY(hipMemcpyAsync(st3, pl->status, 12, hipMemcpyDeviceToHost, stream), return FLATGFA_ERR_HIP);
-        HIP_TRY(hipStreamSynchronize(stream), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipMemcpyAsync(st3, pl->status, 12, hipMemcpyDeviceToHost, stream), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipStreamSynchronize(stream), return FLATGFA_ERR_HIP);
         const uint32_t st = st3[0];
         const uint32_t n_calls = pl->calls_since_status;
         if (attempt == 0) {
@@ -1009,11 +980,11 @@ extern "C" int flatgfa_dev_status(flatgfa_dev_plan_t *pl, void *stream_) {
             // come, so a later call may fill it differently -- on a graph whose paths run along it,
             // twice as much when two of a workgroup's items meet in a window.  Make room now (no call
             // is in flight), not when a call enqueued among others has already run out.
-            HIP_TRY(hipMemsetAsync(pl->status + 2, 0, 4, stream), return FLATGFA_ERR_HIP);
+            FGFA_HIP_OR(hipMemsetAsync(pl->status + 2, 0, 4, stream), return FLATGFA_ERR_HIP);
             if (!(st & (4u | 16u)) && pl->fast.eligible) (void)fast_plan_grow(&pl->fast, true);  // (a plan at its limit stays as it is)
         }
         if (!st) return FLATGFA_OK;
-        HIP_TRY(hipMemsetAsync(pl->status, 0, 4, stream), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipMemsetAsync(pl->status, 0, 4, stream), return FLATGFA_ERR_HIP);
         if (st & 1u) {
             set_error("a step refers to a segment id (or a query to a path id) that is out of range");
             return FLATGFA_ERR_BOUNDS;
@@ -1079,12 +1050,9 @@ extern "C" int flatgfa_dev_plan_describe(flatgfa_dev_plan_t *pl, char *out, int 
             " bucket_cap=" + std::to_string(f.cap);
         // the record buckets of all ranges and path groups: how they are laid out, what they take
         const auto records_of = [](const FastPlan &q) { return q.packed ? q.bucket_records : ((uint64_t)q.n_win + 1) * q.n_slots * q.cap; };
-        uint64_t recs = records_of(f);
-        bool packed = f.packed;
-        for (uint32_t r = 0; r < f.n_more; ++r) {
-            recs += records_of(f.more[r]);
-            packed = packed || f.more[r].packed;
-        }
+        uint64_t recs = 0;
+        for_each_range(f, [&](const FastPlan &q) { recs += records_of(q); });
+        const bool packed = any_range(f, [](const FastPlan &q) { return q.packed; });
         s += std::string(" buckets=") + (packed ? "packed" : "even") + " scratch_mb=" + std::to_string((recs * 4 + (1u << 20) - 1) >> 20) +
              " cache_resident_mb=" + std::to_string((f.mall_steps * 4) >> 20);
     }
@@ -1186,7 +1154,7 @@ extern "C" void flatgfa_dev_pipeline_destroy(flatgfa_dev_pipeline_t *p) {
 extern "C" flatgfa_dev_pipeline_t *flatgfa_dev_pipeline_create(const flatgfa_dev_graph_t *g, const uint32_t *hb, const uint32_t *he, int calls_in_flight) {
     if (!g || calls_in_flight < 1 || calls_in_flight > 8) { set_error("dev_pipeline_create: bad argument (1 .. 8 calls in flight)"); return nullptr; }
     auto *p = new flatgfa_dev_pipeline();
-    HIP_TRY(hipGetDevice(&p->device), { delete p; return nullptr; });
+    FGFA_HIP_OR(hipGetDevice(&p->device), { delete p; return nullptr; });
     for (int k = 0; k < calls_in_flight; ++k) {
         hipStream_t st = nullptr;
         hipEvent_t ev = nullptr;
@@ -1219,8 +1187,8 @@ extern "C" int flatgfa_dev_pipeline_seg_depth(flatgfa_dev_pipeline_t *p, uint32_
     if (!p || p->plans.empty()) { set_error("dev_pipeline_seg_depth: NULL pipeline"); return FLATGFA_ERR_ARG; }
     const size_t lane = (size_t)(p->n_calls % p->plans.size());
     if (after_stream != (void *)-1) {  // (-1: nothing to wait for)
-        HIP_TRY(hipEventRecord(p->after, (hipStream_t)after_stream), return FLATGFA_ERR_HIP);
-        HIP_TRY(hipStreamWaitEvent(p->streams[lane], p->after, 0), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipEventRecord(p->after, (hipStream_t)after_stream), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipStreamWaitEvent(p->streams[lane], p->after, 0), return FLATGFA_ERR_HIP);
     }
     p->n_calls += 1;
     return flatgfa_dev_seg_depth(p->plans[lane], depth_out, uniq_out, p->streams[lane]);
@@ -1231,8 +1199,8 @@ extern "C" int flatgfa_dev_pipeline_path_depth_all(flatgfa_dev_pipeline_t *p, ui
     if (!p || p->plans.empty()) { set_error("dev_pipeline_path_depth_all: NULL pipeline"); return FLATGFA_ERR_ARG; }
     const size_t lane = (size_t)(p->n_calls % p->plans.size());
     if (after_stream != (void *)-1) {
-        HIP_TRY(hipEventRecord(p->after, (hipStream_t)after_stream), return FLATGFA_ERR_HIP);
-        HIP_TRY(hipStreamWaitEvent(p->streams[lane], p->after, 0), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipEventRecord(p->after, (hipStream_t)after_stream), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipStreamWaitEvent(p->streams[lane], p->after, 0), return FLATGFA_ERR_HIP);
     }
     p->n_calls += 1;
     return flatgfa_dev_path_depth_all(p->plans[lane], depth_out, length_out, weighted_out, p->streams[lane]);
@@ -1241,8 +1209,8 @@ extern "C" int flatgfa_dev_pipeline_path_depth_all(flatgfa_dev_pipeline_t *p, ui
 extern "C" int flatgfa_dev_pipeline_join(flatgfa_dev_pipeline_t *p, void *stream) {
     if (!p) { set_error("dev_pipeline_join: NULL pipeline"); return FLATGFA_ERR_ARG; }
     for (size_t k = 0; k < p->streams.size(); ++k) {
-        HIP_TRY(hipEventRecord(p->joined[k], p->streams[k]), return FLATGFA_ERR_HIP);
-        HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, p->joined[k], 0), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipEventRecord(p->joined[k], p->streams[k]), return FLATGFA_ERR_HIP);
+        FGFA_HIP_OR(hipStreamWaitEvent((hipStream_t)stream, p->joined[k], 0), return FLATGFA_ERR_HIP);
     }
     return FLATGFA_OK;
 }

@@ -381,14 +381,7 @@ __global__ __launch_bounds__(256) void k_block_flags(const uint4 *__restrict__ i
     }
 }
 
-#define FAST_TRY(expr)                                                                      \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-            return false;                                                                   \
-        }                                                                                   \
-    } while (0)
+#define FAST_TRY(expr) FGFA_HIP_OR(expr, return false)
 
 // The bucket array: capacity per (window, sub-bucket), bounded by the 24-bit slot arithmetic of
 // put() and by memory: up to 2^30 records (4 GB) without asking; beyond -- a graph of many windows
@@ -437,14 +430,14 @@ static void bucket_cache_give(uint32_t *p, uint64_t bytes) {
 }  // namespace
 void fast_release_scratch() {
     std::lock_guard<std::mutex> lk(g_bucket_cache_mu);
-    int cur = -1;
-    const bool have = hipGetDevice(&cur) == hipSuccess;
-    for (int dev = 0; dev < 64; ++dev) {
-        if (!g_bucket_cache[dev].p) continue;
-        if (hipSetDevice(dev) == hipSuccess) (void)hipFree(g_bucket_cache[dev].p);
-        g_bucket_cache[dev] = BucketCache();
+    {
+        DeviceGuard guard;
+        for (int dev = 0; dev < 64; ++dev) {
+            if (!g_bucket_cache[dev].p) continue;
+            if (guard.switch_to(dev)) (void)hipFree(g_bucket_cache[dev].p);
+            g_bucket_cache[dev] = BucketCache();
+        }
     }
-    if (have) (void)hipSetDevice(cur);
     (void)hipGetLastError();
 }
 namespace {
@@ -1317,7 +1310,8 @@ static void adopt_plans(std::vector<FastPlan> *plans, FastPlan *fp) {
     *fp = (*plans)[0];
     fp->n_more = (uint32_t)plans->size() - 1;
     fp->more = fp->n_more ? new FastPlan[fp->n_more] : nullptr;
-    for (uint32_t r = 0; r < fp->n_more; ++r) fp->more[r] = (*plans)[r + 1];
+    size_t k = 0;
+    for_each_range(*fp, [&](FastPlan &q) { if (k++) q = (*plans)[k - 1]; });
     plans->clear();
 }
 
@@ -1726,7 +1720,7 @@ bool fast_plan_grow(FastPlan *fp, bool ahead_of_need) {
 }
 
 void fast_plan_destroy(FastPlan *fp) {
-    for (uint32_t r = 0; r < fp->n_more; ++r) fast_plan_destroy(&fp->more[r]);
+    for_each_range(*fp, [&](FastPlan &q) { if (&q != fp) fast_plan_destroy(&q); });
     delete[] fp->more;
     // (perm, elist, wave_off, fat_off and fat_woff lie in lists_slab)
     if (fp->buckets && !fp->packed && fp->cap) {

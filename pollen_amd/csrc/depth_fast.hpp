@@ -125,6 +125,28 @@ struct FastPlan {
     uint32_t n_other = 0;
 };
 
+// A plan's ranges and path groups, one after the other: the first plan itself, then more[0 .. n_more).  `Plan` is FastPlan or
+// const FastPlan, and fn takes a reference to the same.
+template <class Plan, class Fn>
+inline void for_each_range(Plan &fp, Fn fn) {
+    fn(fp);
+    for (uint32_t r = 0; r < fp.n_more; ++r) {
+        Plan &q = fp.more[r];
+        fn(q);
+    }
+}
+// ... and whether `pred` holds for all of them / for at least one
+template <class Pred>
+inline bool all_ranges(const FastPlan &fp, Pred pred) {
+    bool all = true;
+    for_each_range(fp, [&](const FastPlan &q) { all = all && pred(q); });
+    return all;
+}
+template <class Pred>
+inline bool any_range(const FastPlan &fp, Pred pred) {
+    return !all_ranges(fp, [&](const FastPlan &q) { return !pred(q); });
+}
+
 // The per-block no-claim marks of a plan (k_visit_bits, k_chunk_flags, k_block_flags: three more reads of the steps) are
 // not on the way to the first answer: a job enqueues them on a stream of its own; once they are there they are looked
 // at on the host (do enough blocks qualify?) and installed between two calls.

@@ -21,16 +21,36 @@ void set_error(const std::string &s);
 const char *last_error();
 }  // namespace fgfa_dev
 
-// `return FLATGFA_ERR_HIP` with "<prefix><expr>: <what HIP says>" as the error where expr fails (for code that has
-// HIP's runtime header and flatgfa.h before it: every user, host or device side)
-#define FGFA_HIP(prefix, expr)                                                                    \
+// The one HIP check: where expr fails, "<prefix><expr>: <what HIP says>" becomes the thread's error and `fail_stmt` runs (a
+// return, or a block that cleans up first).  For code that has HIP's runtime header and flatgfa.h before it: every user,
+// host or device side.  FGFA_HIP_OR is the form without a prefix; FGFA_HIP returns FLATGFA_ERR_HIP.
+#define FGFA_HIP_CHECK(prefix, expr, fail_stmt)                                                   \
     do {                                                                                          \
         hipError_t _e = (expr);                                                                   \
         if (_e != hipSuccess) {                                                                   \
             fgfa_dev::set_error(std::string(prefix) + #expr + ": " + hipGetErrorString(_e));      \
-            return FLATGFA_ERR_HIP;                                                               \
+            fail_stmt;                                                                            \
         }                                                                                         \
     } while (0)
+#define FGFA_HIP_OR(expr, fail_stmt) FGFA_HIP_CHECK("", expr, fail_stmt)
+#define FGFA_HIP(prefix, expr) FGFA_HIP_CHECK(prefix, expr, return FLATGFA_ERR_HIP)
+
+// The calling thread's current device is its own business: whatever an entry point switches to, it switches back.  Saves
+// the current device when it is made and restores it when it goes; switch_to leaves a device that is current already alone.
+namespace fgfa_dev {
+struct DeviceGuard {
+    int dev = -1;
+    DeviceGuard() { if (hipGetDevice(&dev) != hipSuccess) dev = -1; }
+    ~DeviceGuard() { if (dev >= 0) (void)hipSetDevice(dev); }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+    bool switch_to(int device) {
+        int cur = -1;
+        if (hipGetDevice(&cur) == hipSuccess && cur == device) return true;
+        return hipSetDevice(device) == hipSuccess;
+    }
+};
+}  // namespace fgfa_dev
 
 // An empty launch on `stream`: what makes the runtime load this library's code object (flatgfa_warm_device).
 namespace fgfa_dev {

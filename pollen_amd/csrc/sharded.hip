@@ -43,6 +43,7 @@
 #include "flatgfa_core.hpp"
 #include "host_copy.hpp"
 
+using fgfa_dev::DeviceGuard;  // (the calling thread's current device is its own business: what the entry points switch to, they switch back)
 using fgfa_dev::set_error;
 
 const fgfa::View &flatgfa_capi_view(flatgfa_t gfa);  // capi.cpp
@@ -117,13 +118,6 @@ __global__ __launch_bounds__(256) void k_pack_touch(uint32_t *__restrict__ packe
 __global__ __launch_bounds__(256) void k_add_into(uint32_t *__restrict__ acc, const uint32_t *__restrict__ x, size_t n) {
     for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) acc[i] += x[i];
 }
-
-// The calling thread's current device is its own business: whatever the entry points switch to, they switch back.
-struct DeviceGuard {
-    int dev = -1;
-    DeviceGuard() { if (hipGetDevice(&dev) != hipSuccess) dev = -1; }
-    ~DeviceGuard() { if (dev >= 0) (void)hipSetDevice(dev); }
-};
 
 struct Piece {
     uint32_t path;    // the path this is (a piece of)
