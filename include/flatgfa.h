@@ -308,6 +308,23 @@ int flatgfa_degree_table(flatgfa_t gfa, char **text, size_t *len);
 /* The bytes `fgfa depth -b FILE.bed` prints (window_depth.rs:203-211, cli/cmds.rs:246-255); the BED
  * text is parsed as flatbed.rs:125-158 does. */
 int flatgfa_bed_depth_table(flatgfa_t gfa, const uint8_t *bed, size_t bed_len, char **text, size_t *len);
+/* Interval and window depth over many paths in one call, the interval walk on the GPU as well (the three entries above
+ * take one path per call and walk it on the host; their results are these, path by path).  Interval k lies on path
+ * path_ids[k]; a group is a maximal run of equal path_ids, and each group is one interval_depth of the reference
+ * (window_depth.rs:116-147) with a cursor of its own: within a group the intervals may be unsorted, overlapping or inverted
+ * and get what the reference's loop gives them, bit for bit; the same path in two separate runs is two groups.  Node depth
+ * stays on the device; only the n_intervals doubles come back.  A path id >= flatgfa_path_count: FLATGFA_ERR_BOUNDS, nothing
+ * written.  n_intervals == 0: FLATGFA_OK. */
+int flatgfa_intervals_depth(flatgfa_t gfa, const uint32_t *path_ids, const uint64_t *starts, const uint64_t *ends,
+                            uint64_t n_intervals, double *depth_out);
+/* The concatenation, in order, of what `fgfa window-depth P SIZE` prints for each listed path (`fgfa window-depth-all SIZE`);
+ * path_ids == NULL: all paths.  window == 0: FLATGFA_ERR_ARG. */
+int flatgfa_window_depth_paths_table(flatgfa_t gfa, const uint32_t *path_ids, uint32_t n_ids, uint64_t window,
+                                     char **text, size_t *len);
+/* `fgfa depth -b`, except that every entry is looked up by its own name (`fgfa depth --bed-paths FILE`): consecutive
+ * entries on one path are a group.  A name the graph does not have: FLATGFA_ERR_BOUNDS, and flatgfa_last_error names the
+ * entry's index.  No entries: FLATGFA_ERR_BOUNDS. */
+int flatgfa_bed_depth_paths_table(flatgfa_t gfa, const uint8_t *bed_text, size_t bed_len, char **text, size_t *len);
 /* format_float (ops/depth.rs:192-197); returns bytes written (no NUL). */
 int flatgfa_format_float(double x, int digits, char *out, int cap);
 

@@ -67,6 +67,9 @@ SIGNATURES = {
     "flatgfa_interval_depth": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p]),
     "flatgfa_window_depth_table": (c_int, [c_void_p, c_uint32, c_uint64, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_bed_depth_table": (c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_intervals_depth": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]),
+    "flatgfa_window_depth_paths_table": (c_int, [c_void_p, c_void_p, c_uint32, c_uint64, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_bed_depth_paths_table": (c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_pangenotype_matrix": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "flatgfa_pangenotype_table": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_gaf_count": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_uint64), POINTER(c_uint64)]),

@@ -33,6 +33,7 @@
 #include "gaf_lookup_device.hpp"
 #include "extract_device.hpp"
 #include "topology_device.hpp"
+#include "interval_device.hpp"
 
 using fgfa_dev::set_error;
 
@@ -895,6 +896,126 @@ int flatgfa_bed_depth_table(flatgfa_t gfa, const uint8_t *bed_text, size_t bed_l
     int64_t path = gfa->view.find_path(bed.name_data.data() + e0.name_start, e0.name_end - e0.name_start);
     if (path < 0) { set_error("BED: path not found in graph"); return FLATGFA_ERR_BOUNDS; }
     return bed_depth_common(gfa, (uint32_t)path, bed, text, len);
+}
+
+// ---- f2 on many paths: the interval walk on the device too (interval_device.hip) ----
+
+extern "C++" {
+namespace {
+// depth_out[k] for interval k on path ids[k], under the handle's op_mu.  Node depth goes into d_depth first unless the
+// caller has just left it there (depth_ready); it stays on the device, and only the n doubles come back.
+int intervals_depth_locked(CStore *gfa, DevScope *sc, const uint32_t *ids, const uint64_t *starts, const uint64_t *ends, uint64_t n,
+                           bool depth_ready, double *depth_out) {
+    if (!depth_ready)
+        if (int rc = run_seg_depth(gfa, false)) return rc;
+    CAPI_HIP(hipStreamSynchronize(gfa->stream));  // (the job runs on the scope's stream)
+    const fgfa::View &v = gfa->view;
+    fgfa_dev::IntervalGraph g;
+    g.steps = gfa->d_steps, g.n_steps = v.steps.len;
+    g.begin = gfa->h_path_begin.data(), g.end = gfa->h_path_end.data(), g.n_paths = (uint32_t)v.paths.len;
+    g.seg_len = gfa->d_seg_len, g.depth = gfa->d_depth, g.n_segs = (uint32_t)v.segs.len;
+    uint32_t *d_ids = nullptr;
+    uint64_t *d_starts = nullptr, *d_ends = nullptr;
+    double *d_out = nullptr;
+    CAPI_HIP(sc->upload(&d_ids, ids, n));
+    CAPI_HIP(sc->upload(&d_starts, starts, n));
+    CAPI_HIP(sc->upload(&d_ends, ends, n));
+    CAPI_HIP(sc->alloc(&d_out, n));
+    uint32_t cut = fgfa_dev::kIntervalLaneCut;
+    if (const char *h = test_hook("FLATGFA_INTERVAL_LANE_CUT")) cut = (uint32_t)strtoul(h, nullptr, 10);
+    fgfa_dev::IntervalJob *job = sc->hold<fgfa_dev::IntervalJob, fgfa_dev::interval_free>(fgfa_dev::interval_new(fgfa_dev::kIntervalScratchSteps, cut));
+    const fgfa_dev::IntervalList iv{d_ids, d_starts, d_ends, n};
+    if (int rc = fgfa_dev::interval_depth(job, g, iv, ids, sc->stream, d_out)) return rc;
+    CAPI_HIP(fgfa_dev::staged_copy(depth_out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
+    return FLATGFA_OK;
+}
+
+// the table of `bed`'s entries, entry k on path ids[k]
+int intervals_table_locked(CStore *gfa, DevScope *sc, const fgfa::Bed &bed, const std::vector<uint32_t> &ids, bool depth_ready, char **text,
+                           size_t *len) {
+    const size_t n = bed.entries.size();
+    std::vector<uint64_t> starts(n), ends(n);
+    for (size_t k = 0; k < n; ++k) starts[k] = bed.entries[k].start, ends[k] = bed.entries[k].end;
+    std::vector<double> out(n);
+    if (n)
+        if (int rc = intervals_depth_locked(gfa, sc, ids.data(), starts.data(), ends.data(), n, depth_ready, out.data())) return rc;
+    std::string s;
+    fgfa::emit_interval_depth(bed, out.data(), &s);
+    return give_text(s, text, len);
+}
+}  // namespace
+}  // extern "C++"
+
+int flatgfa_intervals_depth(flatgfa_t gfa, const uint32_t *path_ids, const uint64_t *starts, const uint64_t *ends, uint64_t n_intervals,
+                            double *depth_out) {
+    if (!gfa || (n_intervals && (!path_ids || !starts || !ends || !depth_out))) {
+        set_error("flatgfa_intervals_depth: NULL argument");
+        return FLATGFA_ERR_ARG;
+    }
+    if (!n_intervals) return FLATGFA_OK;
+    for (uint64_t k = 0; k < n_intervals; ++k)
+        if (path_ids[k] >= gfa->view.paths.len) { set_error("flatgfa_intervals_depth: path id out of range"); return FLATGFA_ERR_BOUNDS; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    DevScope sc;
+    if (int rc = open_scope(gfa, &sc, "interval depth")) return rc;
+    if (int rc = ensure_device(gfa, -1)) return rc;
+    return intervals_depth_locked(gfa, &sc, path_ids, starts, ends, n_intervals, false, depth_out);
+}
+
+int flatgfa_window_depth_paths_table(flatgfa_t gfa, const uint32_t *path_ids, uint32_t n_ids, uint64_t window, char **text, size_t *len) {
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (!gfa || !text) { set_error("flatgfa_window_depth_paths_table: NULL argument"); return FLATGFA_ERR_ARG; }
+    if (window == 0) { set_error("window depth: window size must be positive"); return FLATGFA_ERR_ARG; }
+    const size_t P = gfa->view.paths.len;
+    std::vector<uint32_t> all;
+    if (!path_ids) {
+        all.resize(P);
+        for (size_t i = 0; i < P; ++i) all[i] = (uint32_t)i;
+        path_ids = all.data();
+        n_ids = (uint32_t)P;
+    }
+    for (uint32_t k = 0; k < n_ids; ++k)
+        if (path_ids[k] >= P) { set_error("window depth: path not found"); return FLATGFA_ERR_BOUNDS; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    DevScope sc;
+    if (int rc = open_scope(gfa, &sc, "window depth")) return rc;
+    if (int rc = ensure_device(gfa, -1)) return rc;
+    fgfa::Bed bed;
+    std::vector<uint32_t> ids;
+    if (!n_ids) return intervals_table_locked(gfa, &sc, bed, ids, false, text, len);
+    // every path's length comes out of the pass that forms the node depth (flatgfa_path_depth's): one read of the steps for
+    // both, and d_depth is left where the interval job reads it
+    gfa->first_answer = false;  // (d_depth is written again)
+    int rc = flatgfa_dev_path_depth_all(gfa->plan, gfa->d_depth, gfa->d_sums, gfa->d_sums + P, gfa->stream);
+    if (!rc) rc = flatgfa_dev_status(gfa->plan, gfa->stream);
+    if (rc) return rc;
+    std::vector<uint64_t> plen(P), lens(n_ids);
+    CAPI_HIP(fgfa_dev::staged_copy(plen.data(), gfa->d_sums, P * 8, hipMemcpyDeviceToHost, gfa->stream));
+    for (uint32_t k = 0; k < n_ids; ++k) lens[k] = plen[path_ids[k]];
+    fgfa::make_paths_windows(gfa->view, path_ids, n_ids, lens.data(), window, &bed, &ids);
+    return intervals_table_locked(gfa, &sc, bed, ids, true, text, len);
+}
+
+int flatgfa_bed_depth_paths_table(flatgfa_t gfa, const uint8_t *bed_text, size_t bed_len, char **text, size_t *len) {
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (!gfa || !text || (bed_len && !bed_text)) { set_error("flatgfa_bed_depth_paths_table: NULL argument"); return FLATGFA_ERR_ARG; }
+    fgfa::Bed bed;
+    std::string err;
+    if (!fgfa::parse_bed(bed_text, bed_len, &bed, &err)) { set_error(err); return FLATGFA_ERR_BOUNDS; }
+    if (bed.entries.empty()) { set_error("BED: no intervals"); return FLATGFA_ERR_BOUNDS; }
+    std::vector<uint32_t> ids;
+    size_t bad = 0;
+    if (!fgfa::bed_entry_paths(gfa->view, bed, &ids, &bad)) {
+        set_error("BED: entry " + std::to_string(bad) + " names a path that is not in the graph");
+        return FLATGFA_ERR_BOUNDS;
+    }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    DevScope sc;
+    if (int rc = open_scope(gfa, &sc, "interval depth")) return rc;
+    if (int rc = ensure_device(gfa, -1)) return rc;
+    return intervals_table_locked(gfa, &sc, bed, ids, false, text, len);
 }
 
 // ---- f3: node depth over a subset of paths (odgi depth -d -s) ----

@@ -2,8 +2,8 @@
 // (cucapra/pollen flatgfa/src/cli/main.rs:9-55, cmds.rs:16-97,217-285), built on the C ABI:
 //
 //   fgfa [-i FILE.flatgfa | -I FILE.gfa] [-o OUT.flatgfa] [-O OUT.gfa] [COMMAND]
-//   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [-s PATHS]
-//            | window-depth PATH SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l]
+//   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [--bed-paths FILE.bed] [-s PATHS]
+//            | window-depth PATH SIZE | window-depth-all SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l]
 //            | extract -n NAME -c DIST [-d N] [-e N] | position -p PATH,OFFSET,+ | validate | degree
 //
 // With no -i/-I the GFA text is read from stdin; with no COMMAND the graph is written out
@@ -109,7 +109,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree";
+    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -275,11 +275,13 @@ int main(int argc, char **argv) {
         bool seg_depth = false;
         std::vector<std::string> names;
         const char *bed = nullptr, *subset = nullptr;
+        bool bed_paths = false;  // --bed-paths: every entry on the path it names (-b: all on the first entry's)
         for (; i < argc; ++i) {
             std::string a = argv[i];
             if (a == "-d" || a == "--graph-depth-table") seg_depth = true;
             else if (a == "-r" && i + 1 < argc) names.push_back(argv[++i]);
-            else if ((a == "-b" || a == "--bed-input") && i + 1 < argc) bed = argv[++i];
+            else if ((a == "-b" || a == "--bed-input") && i + 1 < argc) bed = argv[++i], bed_paths = false;
+            else if (a == "--bed-paths" && i + 1 < argc) bed = argv[++i], bed_paths = true;
             else if ((a == "-s" || a == "--subset-paths") && i + 1 < argc) subset = argv[++i];  // odgi depth -d -s
             else { fprintf(stderr, "fgfa: depth: unknown option %s\n", a.c_str()); flatgfa_free(g); return 2; }
         }
@@ -322,7 +324,8 @@ int main(int argc, char **argv) {
             size_t r;
             while ((r = fread(tmp, 1, sizeof tmp, bf)) > 0) btext.append(tmp, r);
             fclose(bf);
-            rc = flatgfa_bed_depth_table(g, (const uint8_t *)btext.data(), btext.size(), &text, &n);
+            rc = bed_paths ? flatgfa_bed_depth_paths_table(g, (const uint8_t *)btext.data(), btext.size(), &text, &n)
+                           : flatgfa_bed_depth_table(g, (const uint8_t *)btext.data(), btext.size(), &text, &n);
         } else if (names.empty()) {
             rc = flatgfa_path_depth_table(g, nullptr, 0, &text, &n);
         } else {
@@ -347,6 +350,15 @@ int main(int argc, char **argv) {
         size_t n = 0;
         if (id < 0) { fprintf(stderr, "fgfa: path not found\n"); rc = 1; }
         else if (flatgfa_window_depth_table(g, (uint32_t)id, strtoull(argv[i + 1], nullptr, 10), &text, &n)) rc = die("window-depth");
+        else write_all(text, n);
+        flatgfa_free_text(text);
+    } else if (cmd == "window-depth-all") {
+        // fgfa window-depth-all SIZE: what `window-depth P SIZE` prints, for every path in order (a name of its own, so that
+        // a path may be called anything)
+        if (i >= argc) { fprintf(stderr, "usage: fgfa window-depth-all SIZE\n"); flatgfa_free(g); return 2; }
+        char *text = nullptr;
+        size_t n = 0;
+        if (flatgfa_window_depth_paths_table(g, nullptr, 0, strtoull(argv[i], nullptr, 10), &text, &n)) rc = die("window-depth-all");
         else write_all(text, n);
         flatgfa_free_text(text);
     } else if (cmd == "overlap") {

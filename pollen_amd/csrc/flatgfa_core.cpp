@@ -1128,6 +1128,85 @@ void emit_interval_depth(const Bed &bed, const double *depths, std::string *out)
     }
 }
 
+void make_paths_windows(const View &v, const uint32_t *path_ids, size_t n_ids, const uint64_t *lengths, uint64_t size, Bed *out,
+                        std::vector<uint32_t> *entry_path) {
+    *out = Bed();
+    entry_path->clear();
+    for (size_t k = 0; k < n_ids; ++k) {
+        const Path &p = v.paths[path_ids[k]];
+        const uint32_t name_start = (uint32_t)out->name_data.size();
+        out->name_data.insert(out->name_data.end(), v.name_data.data + p.name.start, v.name_data.data + p.name.end);
+        const uint32_t name_end = (uint32_t)out->name_data.size();
+        for (uint64_t pos = 0; pos < lengths[k];) {  // window_depth.rs:41-51
+            const uint64_t e = size < lengths[k] - pos ? pos + size : lengths[k];  // (min(pos + size, end) without the wrap)
+            out->entries.push_back(BedEntry{name_start, name_end, pos, e});
+            entry_path->push_back(path_ids[k]);
+            pos = e;
+        }
+    }
+}
+
+bool bed_entry_paths(const View &v, const Bed &bed, std::vector<uint32_t> *entry_path, size_t *bad) {
+    entry_path->assign(bed.entries.size(), 0);
+    for (size_t k = 0; k < bed.entries.size(); ++k) {
+        const BedEntry &e = bed.entries[k];
+        const uint8_t *name = bed.name_data.data() + e.name_start;
+        const size_t n = e.name_end - e.name_start;
+        if (k) {  // (a BED lists a path's intervals together as a rule: the name of the entry before it is tried first)
+            const BedEntry &q = bed.entries[k - 1];
+            if (q.name_end - q.name_start == n && (n == 0 || memcmp(bed.name_data.data() + q.name_start, name, n) == 0)) {
+                (*entry_path)[k] = (*entry_path)[k - 1];
+                continue;
+            }
+        }
+        const int64_t p = v.find_path(name, n);
+        if (p < 0) {
+            *bad = k;
+            return false;
+        }
+        (*entry_path)[k] = (uint32_t)p;
+    }
+    return true;
+}
+
+bool plan_interval_batches(const uint32_t *path_ids, uint64_t n, const uint32_t *begin, const uint32_t *end, uint32_t n_paths, uint64_t n_steps,
+                           uint64_t budget, std::vector<uint32_t> *paths, std::vector<IntervalBatch> *batches, std::string *err) {
+    paths->clear();
+    batches->clear();
+    if (!n) return true;
+    std::vector<uint32_t> in_batch(n_paths, 0);  // the batch (counted from 1) that names the path
+    batches->emplace_back();
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t p = path_ids[i];
+        if (i && p == path_ids[i - 1]) continue;  // (inside a group)
+        if (p >= n_paths) {
+            *err = "path id out of range";
+            return false;
+        }
+        if (begin[p] > end[p] || end[p] > n_steps) {
+            *err = "path " + std::to_string(p) + " has a step span outside the steps pool";
+            return false;
+        }
+        if (in_batch[p] == batches->size()) continue;
+        const uint64_t len = end[p] - begin[p];
+        IntervalBatch *b = &batches->back();
+        if (b->s1 > b->s0 && b->n_steps + len > budget) {
+            b->i1 = i;
+            IntervalBatch next;
+            next.i0 = i;
+            next.s0 = next.s1 = paths->size();
+            batches->push_back(next);
+            b = &batches->back();
+        }
+        in_batch[p] = (uint32_t)batches->size();
+        paths->push_back(p);
+        b->s1 = paths->size();
+        b->n_steps += len;
+    }
+    batches->back().i1 = n;
+    return true;
+}
+
 void emit_overlap(const View &v, const uint32_t *query_ids, size_t n_q, const uint64_t *path_len, const uint8_t *touch,
                   std::string *out) {  // slow_odgi/overlap.py:17-32
     bool header = false;

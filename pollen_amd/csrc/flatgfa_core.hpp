@@ -261,6 +261,25 @@ uint64_t path_length(const View &v, uint32_t path);
 void interval_depth(const View &v, const uint64_t *seg_depth, uint32_t path, const BedEntry *win, size_t n_win, double *out);
 // IntervalDepth::emit, window_depth.rs:158-170
 void emit_interval_depth(const Bed &bed, const double *depths, std::string *out);
+// ---- intervals on many paths: the host side of flatgfa_intervals_depth and the two tables on it ----
+// The windows `fgfa window-depth P SIZE` makes (make_windows) for every listed path, one path's behind another's: `out` holds
+// every listed path's name once, entry_path[k] is the path entry k lies on.  lengths[k] is the length of path path_ids[k].
+void make_paths_windows(const View &v, const uint32_t *path_ids, size_t n_ids, const uint64_t *lengths, uint64_t size, Bed *out,
+                        std::vector<uint32_t> *entry_path);
+// The path every entry of a BED names, looked up by the entry's own name.  False, with *bad = the entry's index, at the first
+// name the graph does not have.
+bool bed_entry_paths(const View &v, const Bed &bed, std::vector<uint32_t> *entry_path, size_t *bad);
+// The batches an interval job runs (interval_device.hip).  A group is a maximal run of equal path ids; a batch is a run of
+// whole groups whose distinct paths hold at most `budget` steps together (one path that holds more is a batch of its own).
+// Batch b covers intervals [i0, i1) and names paths[s0 .. s1), each path once, in the order its first group comes.
+struct IntervalBatch {
+    uint64_t i0 = 0, i1 = 0;
+    size_t s0 = 0, s1 = 0;
+    uint64_t n_steps = 0;  // of its paths together
+};
+// False with *err for a path id >= n_paths or a span that is reversed or ends past n_steps.  No intervals: no batch.
+bool plan_interval_batches(const uint32_t *path_ids, uint64_t n, const uint32_t *begin, const uint32_t *end, uint32_t n_paths, uint64_t n_steps,
+                           uint64_t budget, std::vector<uint32_t> *paths, std::vector<IntervalBatch> *batches, std::string *err);
 // slow_odgi/slow_odgi/overlap.py:17-32
 void emit_overlap(const View &v, const uint32_t *query_ids, size_t n_q, const uint64_t *path_len, const uint8_t *touch,
                   std::string *out);

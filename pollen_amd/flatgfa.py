@@ -310,6 +310,37 @@ class FlatGFA:
                "bed_depth_table")
         return _take_text(p, n)
 
+    def intervals_depth(self, paths, starts, ends) -> np.ndarray:
+        """Interval k lies on paths[k] (names or ids); every maximal run of one path is one interval_depth of the reference
+        (ops/window_depth.rs:116-147).  The walk runs on the GPU; only the float64 results come back."""
+        ids = self._ids(paths)
+        st = np.ascontiguousarray(starts, dtype=np.uint64)
+        en = np.ascontiguousarray(ends, dtype=np.uint64)
+        if not len(ids) == len(st) == len(en):
+            raise FlatGFAError("intervals_depth: paths, starts and ends differ in length")
+        out = np.zeros(len(st), np.float64)
+        _check(_lib.lib().flatgfa_intervals_depth(self._h, ids.ctypes.data, st.ctypes.data, en.ctypes.data, len(st),
+                                                  out.ctypes.data), "intervals_depth")
+        return out
+
+    def window_depth_paths_table(self, window: int, paths=None) -> bytes:
+        """The bytes `fgfa window-depth-all SIZE` prints: `fgfa window-depth P SIZE` for every path (or the listed ones), in order."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        if paths is None:
+            rc = _lib.lib().flatgfa_window_depth_paths_table(self._h, None, 0, window, ctypes.byref(p), ctypes.byref(n))
+        else:
+            ids = self._ids(paths)
+            rc = _lib.lib().flatgfa_window_depth_paths_table(self._h, ids.ctypes.data, len(ids), window, ctypes.byref(p), ctypes.byref(n))
+        _check(rc, "window_depth_paths_table")
+        return _take_text(p, n)
+
+    def bed_depth_paths_table(self, bed: bytes) -> bytes:
+        """The bytes `fgfa depth --bed-paths FILE.bed` prints: every entry on the path it names."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(_lib.lib().flatgfa_bed_depth_paths_table(self._h, bed, len(bed), ctypes.byref(p), ctypes.byref(n)),
+               "bed_depth_paths_table")
+        return _take_text(p, n)
+
     def _gaf_call(self, gafs, call):
         """`call(ptrs, lens, n)` over GAF texts: file names are mapped (never read into Python), bytes-likes passed as they are."""
         maps, arrs = [], []
