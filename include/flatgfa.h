@@ -318,7 +318,8 @@ int flatgfa_bed_depth_table(flatgfa_t gfa, const uint8_t *bed, size_t bed_len, c
 int flatgfa_intervals_depth(flatgfa_t gfa, const uint32_t *path_ids, const uint64_t *starts, const uint64_t *ends,
                             uint64_t n_intervals, double *depth_out);
 /* The concatenation, in order, of what `fgfa window-depth P SIZE` prints for each listed path (`fgfa window-depth-all SIZE`);
- * path_ids == NULL: all paths.  window == 0: FLATGFA_ERR_ARG. */
+ * path_ids == NULL: all paths.  A path may be listed any number of times, in a row or apart: every listing is a table of its
+ * own (not one group of flatgfa_intervals_depth).  window == 0: FLATGFA_ERR_ARG. */
 int flatgfa_window_depth_paths_table(flatgfa_t gfa, const uint32_t *path_ids, uint32_t n_ids, uint64_t window,
                                      char **text, size_t *len);
 /* `fgfa depth -b`, except that every entry is looked up by its own name (`fgfa depth --bed-paths FILE`): consecutive

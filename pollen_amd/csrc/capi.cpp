@@ -930,15 +930,22 @@ int intervals_depth_locked(CStore *gfa, DevScope *sc, const uint32_t *ids, const
     return FLATGFA_OK;
 }
 
-// the table of `bed`'s entries, entry k on path ids[k]
+// the table of `bed`'s entries, entry k on path ids[k]: one job, or one per stretch of `cuts` (window_table_cuts), so that no
+// group reaches across a cut
 int intervals_table_locked(CStore *gfa, DevScope *sc, const fgfa::Bed &bed, const std::vector<uint32_t> &ids, bool depth_ready, char **text,
-                           size_t *len) {
+                           size_t *len, const std::vector<size_t> *cuts = nullptr) {
     const size_t n = bed.entries.size();
     std::vector<uint64_t> starts(n), ends(n);
     for (size_t k = 0; k < n; ++k) starts[k] = bed.entries[k].start, ends[k] = bed.entries[k].end;
     std::vector<double> out(n);
-    if (n)
-        if (int rc = intervals_depth_locked(gfa, sc, ids.data(), starts.data(), ends.data(), n, depth_ready, out.data())) return rc;
+    const std::vector<size_t> whole = {0, n};
+    if (!cuts) cuts = &whole;
+    for (size_t s = 0; s + 1 < cuts->size(); ++s) {
+        const size_t a = (*cuts)[s], b = (*cuts)[s + 1];
+        if (b <= a) continue;  // (no entries)
+        // (the first job leaves d_depth as it found or made it)
+        if (int rc = intervals_depth_locked(gfa, sc, ids.data() + a, starts.data() + a, ends.data() + a, b - a, depth_ready || s, out.data() + a)) return rc;
+    }
     std::string s;
     fgfa::emit_interval_depth(bed, out.data(), &s);
     return give_text(s, text, len);
@@ -993,8 +1000,12 @@ int flatgfa_window_depth_paths_table(flatgfa_t gfa, const uint32_t *path_ids, ui
     std::vector<uint64_t> plen(P), lens(n_ids);
     CAPI_HIP(fgfa_dev::staged_copy(plen.data(), gfa->d_sums, P * 8, hipMemcpyDeviceToHost, gfa->stream));
     for (uint32_t k = 0; k < n_ids; ++k) lens[k] = plen[path_ids[k]];
-    fgfa::make_paths_windows(gfa->view, path_ids, n_ids, lens.data(), window, &bed, &ids);
-    return intervals_table_locked(gfa, &sc, bed, ids, true, text, len);
+    // a path listed again behind itself (paths without windows in between or not) is a table of its own, not more intervals of
+    // one group: the job runs once per stretch without such a seam -- once, for a list that has none
+    std::vector<size_t> path_entry, cuts;
+    fgfa::make_paths_windows(gfa->view, path_ids, n_ids, lens.data(), window, &bed, &ids, &path_entry);
+    fgfa::window_table_cuts(path_ids, n_ids, path_entry, &cuts);
+    return intervals_table_locked(gfa, &sc, bed, ids, true, text, len, &cuts);
 }
 
 int flatgfa_bed_depth_paths_table(flatgfa_t gfa, const uint8_t *bed_text, size_t bed_len, char **text, size_t *len) {

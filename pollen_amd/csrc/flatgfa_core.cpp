@@ -1129,10 +1129,12 @@ void emit_interval_depth(const Bed &bed, const double *depths, std::string *out)
 }
 
 void make_paths_windows(const View &v, const uint32_t *path_ids, size_t n_ids, const uint64_t *lengths, uint64_t size, Bed *out,
-                        std::vector<uint32_t> *entry_path) {
+                        std::vector<uint32_t> *entry_path, std::vector<size_t> *path_entry) {
     *out = Bed();
     entry_path->clear();
+    if (path_entry) path_entry->assign(n_ids + 1, 0);
     for (size_t k = 0; k < n_ids; ++k) {
+        if (path_entry) (*path_entry)[k] = out->entries.size();
         const Path &p = v.paths[path_ids[k]];
         const uint32_t name_start = (uint32_t)out->name_data.size();
         out->name_data.insert(out->name_data.end(), v.name_data.data + p.name.start, v.name_data.data + p.name.end);
@@ -1144,6 +1146,19 @@ void make_paths_windows(const View &v, const uint32_t *path_ids, size_t n_ids, c
             pos = e;
         }
     }
+    if (path_entry) (*path_entry)[n_ids] = out->entries.size();
+}
+
+void window_table_cuts(const uint32_t *path_ids, size_t n_ids, const std::vector<size_t> &path_entry, std::vector<size_t> *cuts) {
+    cuts->assign(1, 0);
+    bool any = false;
+    uint32_t last = 0;  // the last listed path that has windows
+    for (size_t k = 0; k < n_ids; ++k) {
+        if (path_entry[k + 1] == path_entry[k]) continue;
+        if (any && last == path_ids[k]) cuts->push_back(path_entry[k]);
+        any = true, last = path_ids[k];
+    }
+    if (any) cuts->push_back(path_entry[n_ids]);
 }
 
 bool bed_entry_paths(const View &v, const Bed &bed, std::vector<uint32_t> *entry_path, size_t *bad) {

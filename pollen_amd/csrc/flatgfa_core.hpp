@@ -264,8 +264,14 @@ void emit_interval_depth(const Bed &bed, const double *depths, std::string *out)
 // ---- intervals on many paths: the host side of flatgfa_intervals_depth and the two tables on it ----
 // The windows `fgfa window-depth P SIZE` makes (make_windows) for every listed path, one path's behind another's: `out` holds
 // every listed path's name once, entry_path[k] is the path entry k lies on.  lengths[k] is the length of path path_ids[k].
+// path_entry (may be null) gets n_ids + 1 values: the entries of listed path k are [path_entry[k], path_entry[k + 1]).
 void make_paths_windows(const View &v, const uint32_t *path_ids, size_t n_ids, const uint64_t *lengths, uint64_t size, Bed *out,
-                        std::vector<uint32_t> *entry_path);
+                        std::vector<uint32_t> *entry_path, std::vector<size_t> *path_entry = nullptr);
+// Where a window table's entries must be cut so that no interval job sees two listed copies of one path as one group: the
+// job groups by runs of equal ids, and a path listed twice in a row -- or with only paths of no windows in between -- would
+// be such a run.  cuts = {0, ..., n_entries}, ascending, every stretch [cuts[s], cuts[s + 1]) non-empty; no entries: {0}.
+// path_entry as make_paths_windows leaves it.
+void window_table_cuts(const uint32_t *path_ids, size_t n_ids, const std::vector<size_t> &path_entry, std::vector<size_t> *cuts);
 // The path every entry of a BED names, looked up by the entry's own name.  False, with *bad = the entry's index, at the first
 // name the graph does not have.
 bool bed_entry_paths(const View &v, const Bed &bed, std::vector<uint32_t> *entry_path, size_t *bad);

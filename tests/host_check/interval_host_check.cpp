@@ -1,10 +1,11 @@
 // Drives the host side of interval depth over many paths (flatgfa_core.cpp: plan_interval_batches, make_paths_windows,
-// bed_entry_paths, with parse_bed and emit_interval_depth around them -- what flatgfa_intervals_depth and the two tables on
+// window_table_cuts, bed_entry_paths, with parse_bed and emit_interval_depth around them -- what flatgfa_intervals_depth and the two tables on
 // it do before and after the device's part) for the sanitizer build of pollen_amd/csrc/Makefile (interval_host_check,
 // interval_host_asan).  CPU only.
 //
 //   interval_host_check FILE.gfa ...   for every fixture: the windows of all paths at sizes 1, 4 and 2^64 - 1 (lengths from a host
-//                                      walk); a BED that names every path in shuffled blocks, and one with a name the graph does
+//                                      walk); where each listed path's windows begin, and the cuts of a window table between two
+//                                      listed copies of one path (window_table_cuts) against their definition; a BED that names every path in shuffled blocks, and one with a name the graph does
 //                                      not have; the batch plan of the BED's groups at budgets 0, 1, the longest path and no
 //                                      limit, checked here for what a plan must hold; path ids and spans out of range, which the
 //                                      plan must refuse without reading past anything.  Prints one line per fixture and a digest;
@@ -59,6 +60,35 @@ static void check_plan(const std::vector<uint32_t> &ids, const std::vector<uint3
     if (at != ids.size() || slot != paths.size()) fail("the batches do not cover the intervals", file);
 }
 
+// window_table_cuts against its definition, entry by entry: a cut lies exactly where two neighbouring entries belong to two
+// listed copies of one path.  Returns the number of such seams.
+static size_t check_cuts(const View &v, const std::vector<uint32_t> &list, const std::vector<uint64_t> &lens, uint64_t size, const char *file) {
+    Bed bed;
+    std::vector<uint32_t> entry_path;
+    std::vector<size_t> path_entry, cuts;
+    make_paths_windows(v, list.data(), list.size(), lens.data(), size, &bed, &entry_path, &path_entry);
+    const size_t n = bed.entries.size();
+    if (path_entry.size() != list.size() + 1 || path_entry[0] != 0 || path_entry.back() != n) fail("path_entry does not span the entries", file);
+    std::vector<size_t> owner(n);
+    for (size_t k = 0; k < list.size(); ++k) {
+        if (path_entry[k + 1] < path_entry[k]) fail("path_entry goes back", file);
+        if ((path_entry[k + 1] > path_entry[k]) != (lens[k] > 0)) fail("a path's windows are not where path_entry says", file);
+        for (size_t e = path_entry[k]; e < path_entry[k + 1]; ++e) {
+            owner[e] = k;
+            if (entry_path[e] != list[k] || (e == path_entry[k] ? bed.entries[e].start != 0 : bed.entries[e].start != bed.entries[e - 1].end))
+                fail("an entry is not its path's next window", file);
+        }
+        if (path_entry[k + 1] > path_entry[k] && bed.entries[path_entry[k + 1] - 1].end != lens[k]) fail("a path's windows stop short", file);
+    }
+    std::vector<size_t> want(1, 0);
+    for (size_t e = 1; e < n; ++e)
+        if (owner[e] != owner[e - 1] && list[owner[e]] == list[owner[e - 1]]) want.push_back(e);
+    if (n) want.push_back(n);
+    window_table_cuts(list.data(), list.size(), path_entry, &cuts);
+    if (cuts != want) fail("the cuts are not the seams between copies of one path", file);
+    return want.size() - (n ? 2 : 1);
+}
+
 int main(int argc, char **argv) {
     uint64_t all = 1469598103934665603ull;
     for (int k = 1; k < argc; ++k) {
@@ -87,10 +117,13 @@ int main(int argc, char **argv) {
         for (uint64_t size : {(uint64_t)1, (uint64_t)4, ~(uint64_t)0}) {
             Bed bed;
             std::vector<uint32_t> entry_path;
-            make_paths_windows(v, all_ids.data(), P, lens.data(), size, &bed, &entry_path);
+            std::vector<size_t> path_entry;
+            make_paths_windows(v, all_ids.data(), P, lens.data(), size, &bed, &entry_path, &path_entry);
+            if (path_entry.size() != P + 1) fail("path_entry has not one value per listed path and one more", argv[k]);
             if (entry_path.size() != bed.entries.size()) fail("windows without a path", argv[k]);
             size_t at = 0;
             for (size_t p = 0; p < P; ++p) {  // the same entries as one make_windows per path
+                if (path_entry[p] != at) fail("a path's entries begin elsewhere", argv[k]);
                 const Path &path = v.paths[p];
                 Bed one;
                 make_windows(v.name_data.data + path.name.start, path.name.len(), 0, lens[p], size, &one);
@@ -103,12 +136,34 @@ int main(int argc, char **argv) {
                     ++at;
                 }
             }
-            if (at != bed.entries.size()) fail("too many windows", argv[k]);
+            if (at != bed.entries.size() || path_entry[P] != at) fail("too many windows", argv[k]);
             n_windows += at;
             std::vector<double> depths(bed.entries.size(), 1.5);
             std::string table;
             emit_interval_depth(bed, depths.data(), &table);
             all = fnv(all, table.data(), table.size());
+        }
+        // ---- lists that name a path again: no seam (all paths, and none), every path twice in a row, thrice, the first path
+        // again behind all the others -- as they are, and with the others' lengths taken as 0 -- and a lone path of no length ----
+        size_t n_seams = 0;
+        for (uint64_t size : {(uint64_t)1, (uint64_t)4, ~(uint64_t)0}) {
+            n_seams += check_cuts(v, all_ids, lens, size, argv[k]);
+            n_seams += check_cuts(v, {}, {}, size, argv[k]);
+            for (size_t times : {2, 3}) {
+                std::vector<uint32_t> list;
+                std::vector<uint64_t> ll;
+                for (size_t p = 0; p < P; ++p) list.insert(list.end(), times, (uint32_t)p), ll.insert(ll.end(), times, lens[p]);
+                n_seams += check_cuts(v, list, ll, size, argv[k]);
+            }
+            if (P) {
+                std::vector<uint32_t> list = all_ids;
+                std::vector<uint64_t> ll = lens;
+                list.push_back(0), ll.push_back(lens[0]);
+                n_seams += check_cuts(v, list, ll, size, argv[k]);
+                std::fill(ll.begin() + 1, ll.end() - 1, 0);
+                n_seams += check_cuts(v, list, ll, size, argv[k]);
+                n_seams += check_cuts(v, {0, 0}, {0, 0}, size, argv[k]);
+            }
         }
         // ---- a BED that names every path in shuffled blocks ----
         std::string text = "#name\tstart\tend\n";
@@ -160,7 +215,8 @@ int main(int argc, char **argv) {
             refusals += plan_interval_batches(&zero, 1, b2.data(), end.data(), (uint32_t)P, v.steps.len, 8, &paths, &plan, &err) ? 0 : 1;
             refusals += plan_interval_batches(nullptr, 0, begin.data(), end.data(), (uint32_t)P, v.steps.len, 8, &paths, &plan, &err) && plan.empty() ? 1 : 0;
         }
-        printf("%s windows=%zu bed=%zu refused=%d batches=%zu refusals=%d\n", argv[k], n_windows, ids.size(), (int)refused, n_batches, refusals);
+        printf("%s windows=%zu seams=%zu bed=%zu refused=%d batches=%zu refusals=%d\n", argv[k], n_windows, n_seams, ids.size(), (int)refused, n_batches,
+               refusals);
         all = fnv(all, ids.data(), ids.size() * 4);
     }
     printf("all %016llx\n", (unsigned long long)all);

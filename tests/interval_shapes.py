@@ -10,6 +10,10 @@ and at the end of an interval; a path with no steps; sorted-disjoint, sorted-ove
 M drops terms); A,B,A with one interval per group; more groups of long intervals than k_long has waves; spans that overlap
 and leave gaps in the steps pool; positions beyond 2^32.  budget_cases() lowers the batch budget, for the stand-alone program.
 
+And at the seams of what the kernels tile over: long_groups (one group across the max-scan's tiles, k_spine's second round and
+k_intervals' stride; heads on the tile seams), many_paths (three thousand slots, runs of stepless paths on a tile seam and at
+a batch's ends), cut_edges (7, 8 and 9 walked steps; paths of 64 and 128), big_products (u64 -> f64 rounding; raw arrays).
+
 Test infrastructure only."""
 import functools
 from dataclasses import dataclass, field
@@ -30,6 +34,9 @@ class Shape:
     name: str
     pools: fo.Pools
     lists: Dict[str, Tuple[np.ndarray, np.ndarray, np.ndarray]] = field(default_factory=dict)
+    seams: Dict[str, List[int]] = field(default_factory=dict)  # per list: indices inside a group that M must be carried across
+    heads: Dict[str, List[int]] = field(default_factory=dict)  # per list: group heads at which M must restart
+    notes: Dict[str, object] = field(default_factory=dict)    # what a shape's tests need to know of its geometry
 
     def add(self, label, ids, starts, ends):
         assert label not in self.lists, label
@@ -196,7 +203,200 @@ def long_positions() -> Shape:
     return s
 
 
-SHAPES = [basic, zeros, tiles, many_groups, long_positions]
+SPINE_ROUND = 256 * TILE    # k_spine takes 256 tile aggregates a round: its second round begins at this interval
+STRIDE = 2048 * 256         # kMaxGrid * kThreads: k_intervals strides over the intervals from here upwards
+WIDE = 1 << 24
+
+
+def step_ends_within(r1, a, b) -> int:
+    """How many steps end in (a, b]."""
+    return int(np.searchsorted(r1, b, "right") - np.searchsorted(r1, a, "right"))
+
+
+def ascending(L: int, n: int):
+    """n windows of width L // n + 3, window i from i * (L // n): sorted, each reaching 3 bases into the next, so M is the end
+    of the window before and drops next to nothing.  (Unsorted random lists come out almost all 0.0 in long groups: the cursor
+    is past them.)"""
+    g = L // n
+    st = np.arange(n, dtype=np.uint64) * np.uint64(g)
+    return st, st + np.uint64(g + 3)
+
+
+def long_groups() -> Shape:
+    """Groups of thousands of intervals on the pools of long_positions: M carried across the max-scan's tile seams, through
+    k_spine and into its second round, across k_intervals' stride; M restarting at heads on and around the tile seams; a
+    tile whose own ends all lie below the M it must hand on."""
+    lp = long_positions()
+    s = Shape("long_groups", lp.pools)
+    r1 = [np.array(ends_of(s.pools, p), np.uint64) for p in range(2)]
+    L = [int(r[-1]) for r in r1]
+    assert min(L) > 1 << 32
+
+    def carried(label, n, seams, step_ends=3):
+        st, en = ascending(L[0], n)
+        assert n > max(seams) + 2 and int(en[-1]) <= L[0] + 3
+        for q in seams:  # the interval two before the seam reaches far past the ones behind the seam
+            a = int(st[q - 2])
+            en[q - 2] = a + WIDE
+            assert (q - 2) // TILE == q // TILE - 1 and q % TILE == 0
+            assert step_ends_within(r1[0], a, a + WIDE) >= step_ends
+            assert step_ends == 3 or (a + WIDE > L[0] and step_ends_within(r1[0], a, L[0]) == step_ends)
+            assert int(en[q + 1]) < a + WIDE  # (the seam's interval and the one behind it end below that M)
+        s.add(label, 0, st, en)
+        s.seams[label] = list(seams)
+
+    carried("tile_seams", 3 * TILE + 5, [TILE, 2 * TILE, 3 * TILE])
+    carried("spine_round", SPINE_ROUND + TILE + 3, [SPINE_ROUND])
+    # (257 windows from the path's end only two steps are left to end, 2^24 bases reach past the path, and that M drops every
+    # term of every interval behind the seam)
+    carried("stride", STRIDE + 257, [STRIDE], step_ends=2)
+
+    # heads on and around the tile seams: the group in front of each ends on an interval that reaches its path's end
+    heads = [TILE - 1, TILE, TILE + 1, 2 * TILE - 1, 2 * TILE]
+    n = 2 * TILE + 100
+    ids = np.zeros(n, np.uint32)
+    for k, h in enumerate(heads):
+        ids[h:] = (k + 1) & 1
+    st, en = ascending(min(L), n)
+    for h in heads:
+        en[h - 1] = L[int(ids[h - 1])]
+        assert ids[h] != ids[h - 1] and int(st[h - 1]) < L[int(ids[h - 1])]
+    s.add("heads", ids, st, en)
+    s.heads["heads"] = heads
+
+    # tile 1's ends all lie below the M that tile 0 sets; tile 2 begins below it and leaves it
+    n = 3 * TILE + 7
+    st, en = ascending(L[0], n)
+    big = int(st[2 * TILE + 20]) + 5
+    en[TILE - 24] = big
+    assert int(en[TILE:2 * TILE].max()) < big and int(en[:TILE - 24].max()) < big
+    assert int(en[2 * TILE]) < big < int(st[2 * TILE + 40])
+    assert step_ends_within(r1[0], int(st[2 * TILE]), big) >= 3
+    s.add("through_a_tile", 0, st, en)
+    s.seams["through_a_tile"] = [2 * TILE]
+    return s
+
+
+def many_paths() -> Shape:
+    """About 3000 paths of 0 to 5 steps over segments of 0 to 6 bases; the list names them in a shuffled order, which is the
+    batch's slot order.  In that order: three stepless paths at the front, three at the end, three where the batch's step 1024
+    lies (so one path ends at 1024 and one starts there), and one stepless path between a path that ends at step 2048 and one
+    that starts there."""
+    rng = np.random.default_rng(21)
+    S = 40
+    lens = rng.integers(0, 7, S)
+    lens[:6] = [0, 0, 3, 6, 1, 0]
+    counts = [0, 0, 0, 3]
+
+    def fill_to(total):
+        while sum(counts) < total:
+            c = min(int(rng.integers(0, 6)), total - sum(counts))
+            if sum(counts) + c == total and c < 2:  # the path that ends there has two steps or more
+                counts.append(0)
+                continue
+            if 0 < total - sum(counts) - c < 2:
+                c -= 1
+            counts.append(c)
+
+    fill_to(TILE)
+    at_tile = len(counts)
+    counts.extend([0, 0, 0, 4])
+    fill_to(2 * TILE)
+    at_two = len(counts)
+    counts.extend([0, 2])
+    while len(counts) < 2990:
+        counts.append(int(rng.integers(0, 6)))
+    counts.extend([5, 0, 0, 0])
+    counts = np.array(counts)
+    P = len(counts)
+    order = rng.permutation(P)           # slot k holds path order[k]
+    per_path = np.zeros(P, np.int64)
+    per_path[order] = counts
+    begin = np.concatenate([[0], np.cumsum(per_path)])
+    steps = chop_shapes.handles(rng, rng.integers(0, S, int(begin[-1])))
+    s = Shape("many_paths", make_pools(lens, steps, np.stack([begin[:-1], begin[1:]], axis=1)))
+    # ---- the geometry, in slot order ----
+    pstart = np.concatenate([[0], np.cumsum(counts)])
+    assert (lens == 0).any() and 2900 < P < 3100 and counts.max() == 5 and counts.min() == 0
+    assert (counts[:3] == 0).all() and counts[3] > 0 and (counts[-3:] == 0).all() and counts[-4] >= 2
+    assert pstart[at_tile] == TILE and (counts[at_tile:at_tile + 3] == 0).all() and counts[at_tile - 1] >= 2 and counts[at_tile + 3] > 0
+    assert pstart[at_two] == 2 * TILE and counts[at_two] == 0 and counts[at_two - 1] >= 2 and counts[at_two + 1] > 0
+    assert pstart[-1] > 7 * TILE
+    s.notes.update(order=order, counts=counts, at_tile=at_tile, at_two=at_two)
+
+    def listed(slots, whole_first=False):
+        ids, st, en = [], [], []
+        for k in slots:
+            L = (ends_of(s.pools, int(order[k])) or [0])[-1]
+            w = [(a, min(a + 3, L)) for a in range(0, L, 3)]
+            # (behind its windows M leaves the whole path its last steps only; in front of them it would leave them nothing)
+            rows = [(0, L), (L, L + 4)] if whole_first else w + [(0, L), (L, L + 4)]
+            ids += [int(order[k])] * len(rows)
+            st += [r[0] for r in rows]
+            en += [r[1] for r in rows]
+        return ids, st, en
+
+    s.add("slot_order", *listed(range(P)))
+    # every path again, backwards, its whole length first in its group: groups on paths the batch already holds
+    there, back = listed(range(P)), listed(range(P - 2, -1, -1), True)
+    s.add("there_and_back", *[a + b for a, b in zip(there, back)])
+    # the runs of stepless paths with five slots either side, for budgets below a path's steps (run_budget_cases)
+    near = sorted(set(range(0, 9)) | set(range(at_tile - 5, at_tile + 9)) | set(range(at_two - 5, at_two + 7)) | set(range(P - 9, P)))
+    s.add("around_the_runs", *listed(near))
+    s.notes["near"] = near
+    return s
+
+
+def walked_steps(pools, pid: int, ws: int, we: int, m: int = 0):
+    """(how many steps k_intervals walks for [ws, we) with M = m -- the steps from the first that ends at or past
+    max(ws + 1, m) on, as long as they begin below we -- and how many of those have no length)"""
+    r1 = ends_of(pools, pid)
+    r0 = [0] + r1[:-1]
+    if we <= ws:
+        return 0, 0
+    first = next((j for j, e in enumerate(r1) if e >= max(ws + 1, m)), len(r1))
+    js = [j for j in range(first, len(r1)) if r0[j] < we]
+    assert js == list(range(first, first + len(js)))
+    return len(js), sum(1 for j in js if r1[j] == r0[j])
+
+
+def cut_edges() -> Shape:
+    """The lane / wave cut and k_long's rounds, aimed at: intervals that walk exactly 7, 8 and 9 steps (LANE_CUT - 1, LANE_CUT,
+    LANE_CUT + 1), from a step seam and from inside a step, ending one base into their last step and at its end, with 0, 2 and 3
+    of the walked steps of no length; paths of exactly 64 and 128 steps taken whole, from their second base and past their
+    end, so that a wave's round ends on the path's last step."""
+    rng = np.random.default_rng(22)
+    lens = np.array([0, 3, 4, 2, 1, 5, 2], np.int64)
+    segs = np.concatenate([rng.integers(0, 7, 500), [2], rng.integers(0, 7, 63), [5], rng.integers(0, 7, 127)])
+    s = Shape("cut_edges", make_pools(lens, np.asarray(segs << 1, np.uint32), [(0, 500), (500, 564), (564, 692), (692, 692)]))
+    r1 = ends_of(s.pools, 0)
+    r0 = [0] + r1[:-1]
+    n = len(r1)
+    for k in (LANE_CUT - 1, LANE_CUT, LANE_CUT + 1):
+        for z in (0, 2, 3):
+            for inside in (0, 1):
+                # steps a .. a + k - 1, a and the last of them with a length, z of them without
+                a = next(a for a in range(1, n - k) if r1[a] - r0[a] > inside and r1[a + k - 1] > r0[a + k - 1]
+                         and sum(1 for j in range(a, a + k) if r1[j] == r0[j]) == z)
+                ws = r0[a] + inside
+                ends = sorted({r0[a + k - 1] + 1, r1[a + k - 1]})
+                for we in ends:
+                    assert walked_steps(s.pools, 0, ws, we) == (k, z), (k, z, inside)
+                # every interval its own group (a stepless path in between): M is 0, and the count is the one asserted
+                s.add("walk%d_zeros%d_%s" % (k, z, "inside" if inside else "seam"), [0, 3] * len(ends),
+                      [x for we in ends for x in (ws, 0)], [x for we in ends for x in (we, 1)])
+    for pid, count in ((1, 64), (2, 128)):
+        e = ends_of(s.pools, pid)
+        L = e[-1]
+        assert len(e) == count and e[0] >= 2
+        for label, (ws, we) in (("whole", (0, L)), ("from1", (1, L)), ("past", (0, L + 5))):
+            assert walked_steps(s.pools, pid, ws, we)[0] == count
+            s.add("p%d_%s" % (pid, label), pid, [ws], [we])
+        s.add("p%d_all" % pid, [pid, 3, pid, 3, pid], [0, 0, 1, 0, 0], [L, 1, L, 1, L + 5])
+    return s
+
+
+SHAPES = [basic, zeros, tiles, many_groups, long_positions, long_groups, many_paths, cut_edges]
 
 
 @functools.lru_cache(maxsize=None)
@@ -239,3 +439,65 @@ def plan_batches(groups, lengths, budget) -> int:
         held.add(p)
         steps += lengths[p]
     return batches
+
+
+def plan_slots(groups, lengths, budget):
+    """The batches' slots (plan_interval_batches, restated as plan_batches restates it): a list of path lists."""
+    out, steps = [[]], 0
+    for k, p in enumerate(groups):
+        if (k and groups[k - 1] == p) or p in out[-1]:
+            continue
+        if out[-1] and steps + lengths[p] > budget:
+            out.append([])
+            steps = 0
+        out[-1].append(p)
+        steps += lengths[p]
+    return out
+
+
+def run_budget_cases():
+    """(label, list of many_paths, budget, batches) where a batch cut meets a run of stepless paths.  A path of no steps never
+    makes the plan cut (it adds nothing to the batch's steps), so a cut touches a run in two ways only.  Budget 1, on the
+    list around the runs: a path of two steps or more is over the budget alone, the stepless path behind it starts a batch of
+    no steps, and the path of two steps or more behind the run cuts again: the run is a whole batch, cut at both its ends.
+    Budget 1024 or 2048, on the whole list: the first batch fills exactly, takes the run in behind its last step -- it ends
+    on a tile seam in stepless slots -- and the path that starts at that step begins the next batch."""
+    s = shape("many_paths")
+    lengths = [int(p["steps_end"]) - int(p["steps_start"]) for p in s.pools.paths]
+    out = []
+    for label, name, budget in (("runs-budget1", "around_the_runs", 1), ("budget1024", "slot_order", TILE), ("budget2048", "there_and_back", 2 * TILE)):
+        ids = s.lists[name][0]
+        groups = [int(ids[k]) for k in np.flatnonzero(np.concatenate([[True], np.diff(ids.astype(np.int64)) != 0]))]
+        out.append((label, name, budget, len(plan_slots(groups, lengths, budget))))
+    return out
+
+
+def big_products():
+    """(pools, depth, ids, starts, ends) of raw arrays no handle loads: segment lengths and depths up to 2^32 - 1, so that
+    (double)(depth * len) rounds (the product has up to 64 bits), and intervals whose (double)(end - start) rounds."""
+    top = (1 << 32) - 1
+    lens = np.array([top, (1 << 31) + 1, 3, 0, top - 2, 123456789, 1, (1 << 32) - 5], np.int64)
+    depth = np.array([top, top - 2, 7, 5, (1 << 31) + 3, 987654321, top, (1 << 30) + 1], np.uint64)
+    segs = np.array([0, 1, 2, 3, 4, 5, 6, 7, 0, 3, 3, 4, 1, 7, 6, 5, 2, 0, 4, 7], np.int64)
+    pools = chop_shapes.make_pools(lens, np.asarray(segs << 1, np.uint32), [(0, 20), (3, 20)], seq=False)
+    rows = [(0, 0, (1 << 64) - 1), (1, 0, (1 << 64) - 1), (0, 1, (1 << 63) + 1), (1, 1, (1 << 63) + 1)]
+    for pid in (0, 1):
+        r1 = ends_of(pools, pid)
+        r0 = [0] + r1[:-1]
+        L = r1[-1]
+        assert L > 1 << 35
+        rows += [(pid, 0, L), (pid, 1, L + (1 << 60) + 1), (pid, 0, (1 << 53) + 1)]
+        for j in range(len(r1)):
+            if r1[j] - r0[j] > 8:   # inside one step
+                rows += [(pid, r0[j] + 5, r0[j] + 7), (pid, r0[j] + 1, r1[j] - 1), (pid, r0[j], r1[j])]
+    assert any(int(depth[x]) * int(lens[x]) > 1 << 63 for x in range(len(lens)))
+    ids, st, en = [], [], []
+    for k, (pid, a, b) in enumerate(rows):  # every row alone in its group: a row on the other path in front of it
+        ids += [1 - pid, pid]
+        st += [3, a]
+        en += [3, b]
+    # and groups of several: M from a huge end, and from a small one
+    ids += [0, 0, 0, 1, 1, 1]
+    st += [5, 1, 0, 0, 2, 1]
+    en += [1 << 33, (1 << 63) + 1, (1 << 64) - 1, 7, (1 << 64) - 1, (1 << 63) + 1]
+    return pools, depth, np.array(ids, np.uint32), np.array(st, np.uint64), np.array(en, np.uint64)

@@ -4,7 +4,8 @@ flatgfa_bed_depth_paths_table; `fgfa window-depth-all`, `fgfa depth --bed-paths`
 The vectors are compared with the model (tests/interval_model.py: the oracle's interval_depth, group by group) by
 .tobytes(): no tolerance.  Every shape of tests/interval_shapes.py goes through the Python method with the lane / wave cut as
 it ships, with every interval on the wave kernel and with every interval on one lane; the stand-alone program
-(tests/device_check/interval_check.hip, built with the library) runs the job with the batch budget lowered.  Run with -m gpu."""
+(tests/device_check/interval_check.hip, built with the library) runs the job with the batch budget lowered, and on raw arrays
+whose products and widths no f64 holds (big_products: the closed form in Python integers is the reference).  Run with -m gpu."""
 import functools
 import os
 import struct
@@ -105,6 +106,28 @@ def job_cases():
     for budget in (2 * ish.TILE + 1, 3 * ish.TILE):  # every path alone; two or three paths a batch, the scan restarting inside tiles
         out.append(("tiles-%d" % budget, case_bytes(t.pools, ids, st, en, budget, ish.LANE_CUT), len(ids), want("tiles")["all_paths"], 0,
                     ish.plan_batches(groups, lengths, budget)))
+    # three thousand slots: a batch cut at both ends of a run of stepless paths, batches of a tile that end in such a run
+    m = ish.shape("many_paths")
+    lengths = [int(p["steps_end"]) - int(p["steps_start"]) for p in m.pools.paths]
+    for label, name, budget, _ in ish.run_budget_cases():
+        ids, st, en = m.lists[name]
+        groups = [int(ids[a]) for a, _ in im.runs(ids)]
+        out.append(("many_paths-" + label, case_bytes(m.pools, ids, st, en, budget, ish.LANE_CUT), len(ids), want("many_paths")[name], 0,
+                    ish.plan_batches(groups, lengths, budget)))
+    # one long group, and groups with heads on the tile seams, a batch per new path: M comes from one scan over all batches
+    lg = ish.shape("long_groups")
+    lengths = [int(p["steps_end"]) - int(p["steps_start"]) for p in lg.pools.paths]
+    for name in ("tile_seams", "heads"):
+        ids, st, en = lg.lists[name]
+        groups = [int(ids[a]) for a, _ in im.runs(ids)]
+        out.append(("long_groups-%s-budget1" % name, case_bytes(lg.pools, ids, st, en, 1, ish.LANE_CUT), len(ids), want("long_groups")[name], 0,
+                    ish.plan_batches(groups, lengths, 1)))
+    # lengths and depths up to 2^32 - 1, widths up to 2^64 - 1: where u64 -> f64 rounds.  Raw arrays (no handle loads such
+    # segments); the closed form in Python integers is the reference
+    pools, depth, ids, st, en = ish.big_products()
+    model = im.closed_form(pools, ids, st, en, depth).tobytes()
+    for cut in (ish.LANE_CUT, 0):
+        out.append(("big_products-cut%d" % cut, case_bytes(pools, ids, st, en, 1 << 27, cut, depth), len(ids), model, 0, 1))
     # a step that names no segment: FLATGFA_ERR_BOUNDS, whatever the intervals
     bad = fo.Pools(**{n: getattr(b.pools, n) for n in fo.POOL_ORDER})
     bad.steps = b.pools.steps.copy()
@@ -134,7 +157,9 @@ def job_outputs(tmp_path_factory):
 
 
 JOB_IDS = ["%s-cut%d" % (c[0], cut) for c in ish.budget_cases() for cut in (ish.LANE_CUT, 0)] + \
-    ["tiles-%d" % (2 * ish.TILE + 1), "tiles-%d" % (3 * ish.TILE), "bad_step", "bad_path_id", "no_intervals"]
+    ["tiles-%d" % (2 * ish.TILE + 1), "tiles-%d" % (3 * ish.TILE)] + \
+    ["many_paths-runs-budget1", "many_paths-budget1024", "many_paths-budget2048", "long_groups-tile_seams-budget1", "long_groups-heads-budget1",
+     "big_products-cut%d" % ish.LANE_CUT, "big_products-cut0", "bad_step", "bad_path_id", "no_intervals"]
 
 
 @pytest.mark.parametrize("case", JOB_IDS)
@@ -205,6 +230,41 @@ def test_golden_tables(gfa, tmp_path, monkeypatch):
             assert out.returncode == 0 and out.stdout == got, out.stderr
         out = subprocess.run([FGFA, "-I", gfa, "window-depth-all", "4"], capture_output=True, timeout=120)
         assert out.returncode == 0 and out.stdout == g.window_depth_paths_table(4), out.stderr
+    finally:
+        g.close()
+
+
+REPEATED = [[0, 0], [0, 2, 0], [1, 1, 3], [3, 3, 3]]
+
+
+@pytest.mark.parametrize("graph", ["basic", "edge_names_loops.gfa"])
+def test_a_path_listed_again_gets_its_own_table(images, graph, monkeypatch):
+    """The window table is the per-path tables one behind another, whatever the list: a path listed twice in a row, or with
+    only paths of no windows in between (path 2 of `basic` has no steps), is not one group of both copies' windows."""
+    monkeypatch.delenv(CUT_HOOK, raising=False)
+    if graph == "basic":
+        pools = ish.shape("basic").pools
+        g = pa.load(images["basic"])
+    else:
+        pools = fo.parse_gfa(read(os.path.join(GOLDEN, graph)))
+        g = pa.parse(os.path.join(GOLDEN, graph))
+    try:
+        P = len(pools.paths)
+        assert P >= 4 and len({pools.path_name(i) for i in range(P)}) == P
+        lens, _ = fo.path_depth(pools)
+        for w in (1, 50, int(max(lens)) + 1):
+            one = [g.window_depth_table(i, w) for i in range(P)]
+            for ids in REPEATED + [[p for p in range(P) for _ in (0, 1)]]:
+                got = g.window_depth_paths_table(w, ids)
+                assert got == b"".join(one[i] for i in ids), (graph, w, ids, "the one-path route, path by path")
+                assert got == im.window_depth_paths_table(pools, w, ids), (graph, w, ids, "the oracle")
+            assert g.window_depth_paths_table(w) == b"".join(one), (graph, w, "all paths: no seam")
+        if graph == "basic":
+            ids, st, en = ish.shape("basic").lists["aba"]
+            assert g.intervals_depth(ids, st, en).tobytes() == want("basic")["aba"]
+        else:
+            st, en = np.zeros(P, np.uint64), lens.astype(np.uint64)
+            assert g.intervals_depth(list(range(P)), st, en).tobytes() == im.intervals_depth(pools, list(range(P)), st, en).tobytes()
     finally:
         g.close()
 

@@ -58,6 +58,11 @@ def test_interval_host_code_is_clean_and_agrees(binaries):
         n_windows = sum(len(im.windows(int(n), w)) for n in lens for w in (1, 4, 2 ** 64 - 1))
         fields = dict(f.split("=") for f in by_file[path].split(" ")[1:])
         assert int(fields["windows"]) == n_windows, path
+        # seams between two listed copies of one path: every path twice (one each that has windows) and thrice (two each); the
+        # first path again behind all the others, as they are and with the others taken as windowless; at each of three sizes
+        live = [int(n) > 0 for n in lens]
+        seams = 3 * sum(live) + (int(live[0] and not any(live[1:])) + int(live[0]) if live else 0)
+        assert int(fields["seams"]) == 3 * seams, path
         if len(p.paths):
             assert fields["refused"] == "1" and fields["refusals"] == "4", by_file[path]
     assert seen >= 5
