@@ -326,6 +326,34 @@ int flatgfa_window_depth_paths_table(flatgfa_t gfa, const uint32_t *path_ids, ui
  * entries on one path are a group.  A name the graph does not have: FLATGFA_ERR_BOUNDS, and flatgfa_last_error names the
  * entry's index.  No entries: FLATGFA_ERR_BOUNDS. */
 int flatgfa_bed_depth_paths_table(flatgfa_t gfa, const uint8_t *bed_text, size_t bed_len, char **text, size_t *len);
+/* flatten (slow_odgi/slow_odgi/flatten.py:5-57; `fgfa flatten [-n NAME] [-f FASTA] [-b BED]`, `odgi flatten -f -b`,
+ * tests/turnt.toml:46-49): the graph in linear coordinates.  `name` is name_len bytes of the caller's (not NUL-terminated).
+ * The FASTA (flatten.py:51-55): ">" name "\n", then the bases of every segment in pool order -- segment s is
+ * seq_data[seq.start, seq.end), gathered: the spans need not be in order, disjoint or contiguous -- with a newline after every
+ * 80 of them (insert_newlines, flatten.py:44-46) and one at the end (print's); with no bases the body is that one newline.
+ * The BED (flatten.py:23-41): "#name\tstart\tend\tpath.name\tstrand\tstep.rank\n", then for every path in pool order and
+ * every step of its span in order (rank i from 0) "{name}\t{start}\t{end}\t{path name}\t{+|-}\t{i}\n": start is the legend
+ * (flatten.py:13-19) of the step's segment -- the lengths of the segments before it in pool order -- and end = start + its
+ * length, '+' a forward handle; plain decimal, offsets 64-bit.  Path spans may overlap, alias or be empty, and paths of one
+ * name are emitted as often as they occur.
+ * The legend is an exclusive scan on the GPU, made on the first flatten call and kept with the handle (freed by
+ * flatgfa_free); both texts are formed on the GPU by tile of output bytes -- the BED a fixed number of lines at a time, so
+ * device memory beyond the graph does not grow with the step count -- and leave through the process's pinned staging while
+ * the next piece is formed.  The device `gfa` is resident on, else device 0; a resident graph's steps are read in place, and
+ * `gfa` is not made resident (its sequence pool is kept on the device with the handle, as for the GAF lookup, once a FASTA is
+ * asked for).  A step naming a segment out of range, or a span that leaves its pool: FLATGFA_ERR_BOUNDS, nothing delivered.
+ * Without a device: FLATGFA_ERR_NO_DEVICE.  NULL arguments, name == NULL with name_len != 0: FLATGFA_ERR_ARG. */
+/* flatten.py:13-19: offset_out[s] = the bases before segment s; offset_out[segment_count] = all bases. */
+int flatgfa_flatten_legend(flatgfa_t gfa, uint64_t *offset_out /* [segment_count + 1] */);
+/* flatten.py:51-55 and :23-41, each into a malloc'd buffer (release with flatgfa_free_text): the stream below into memory. */
+int flatgfa_flatten_fasta(flatgfa_t gfa, const char *name, size_t name_len, char **text, size_t *len);
+int flatgfa_flatten_bed(flatgfa_t gfa, const char *name, size_t name_len, char **text, size_t *len);
+/* flatten.py:49-57 as a stream: the bytes in order, in pieces of whatever size the chunks give, each handed to `sink` (the
+ * pointer is the library's and holds until the sink returns).  what: 1 the FASTA, 2 the BED, 3 both, the FASTA first (what
+ * `slow_odgi flatten` prints, __main__.py:178); anything else, or a NULL sink: FLATGFA_ERR_ARG.  A sink that returns nonzero
+ * ends the call with FLATGFA_ERR_IO, and nothing more is delivered. */
+typedef int (*flatgfa_sink_t)(void *ctx, const char *bytes, size_t n); /* nonzero: stop */
+int flatgfa_flatten_stream(flatgfa_t gfa, const char *name, size_t name_len, int what, flatgfa_sink_t sink, void *ctx);
 /* format_float (ops/depth.rs:192-197); returns bytes written (no NUL). */
 int flatgfa_format_float(double x, int digits, char *out, int cap);
 
@@ -538,6 +566,11 @@ int flatgfa_dev_chop_count(const flatgfa_dev_graph_t *g, uint64_t max_size, uint
 int flatgfa_dev_chop_fill(flatgfa_dev_chop_t *job, uint32_t *steps, uint32_t *path_begin, uint32_t *path_end, uint32_t *seg_len,
                           void *stream);
 void flatgfa_dev_chop_free(flatgfa_dev_chop_t *job);
+/* The legend of flatten (flatten.py:13-19; flatgfa_flatten_legend) of a graph image in device memory: d_offset_out[s] = the
+ * sum of g->seg_len before s, d_offset_out[n_segs] = the sum of all, in 64 bits (g->seg_len is required: FLATGFA_ERR_ARG when
+ * NULL; the steps and spans are not read).  Enqueued on `stream`, which is waited for: the scan's scratch goes before the
+ * call returns. */
+int flatgfa_dev_flatten_legend(const flatgfa_dev_graph_t *g, uint64_t *d_offset_out /* device, [n_segs + 1] */, void *stream);
 /* Synchronizes `stream`, then returns FLATGFA_OK, or FLATGFA_ERR_BOUNDS if any kernel since the
  * last call saw a segment id >= n_segs or a path id >= n_paths.  Plans size their scratch for the
  * graph when they are created; should a node-depth call nevertheless have run out of scratch room

@@ -27,6 +27,9 @@ class flatgfa_dev_graph_t(ctypes.Structure):
                 ("n_paths", c_uint32), ("n_segs", c_uint32), ("seg_len", c_void_p)]
 
 
+# flatgfa_sink_t: int (*)(void *ctx, const char *bytes, size_t n)
+SINK_T = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t)
+
 # name -> (restype, argtypes); this table is also what tests/test_capi_symbols.py checks
 # against include/flatgfa.h.
 SIGNATURES = {
@@ -87,6 +90,10 @@ SIGNATURES = {
     "flatgfa_validate_table": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_degree": (c_int, [c_void_p, c_void_p]),
     "flatgfa_degree_table": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_flatten_legend": (c_int, [c_void_p, c_void_p]),
+    "flatgfa_flatten_fasta": (c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_flatten_bed": (c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_flatten_stream": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_void_p, c_void_p]),
     "flatgfa_sharded_create": (c_void_p, [c_void_p, c_void_p, c_int, ctypes.c_uint]),
     "flatgfa_sharded_free": (None, [c_void_p]),
     "flatgfa_sharded_layout": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint32),
@@ -126,6 +133,7 @@ SIGNATURES = {
                                        POINTER(c_uint64), POINTER(c_uint64)]),
     "flatgfa_dev_chop_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "flatgfa_dev_chop_free": (None, [c_void_p]),
+    "flatgfa_dev_flatten_legend": (c_int, [POINTER(flatgfa_dev_graph_t), c_void_p, c_void_p]),
     "flatgfa_dev_status": (c_int, [c_void_p, c_void_p]),
     "flatgfa_dev_profile_enable": (None, [c_int]),
     "flatgfa_dev_profile_read": (c_int, [POINTER(c_char_p), POINTER(c_float), c_int]),

@@ -1,7 +1,7 @@
 // extern "C" surface of libflatgfa.so: the flatgfa-c drop-in (Part 1 of include/flatgfa.h)
 // plus the additive loaders, the depth queries and the host routes of the other features (Part 2).  The kernels live in the
 // .hip files -- depth_device.hip and its kin for depth, gaf_device.hip, gaf_lookup_device.hip, chop_device.hip,
-// extract_device.hip, topology_device.hip for the rest -- and are reached through their headers; this file uses the HIP runtime
+// extract_device.hip, topology_device.hip, flatten_device.hip for the rest -- and are reached through their headers; this file uses the HIP runtime
 // API only.  Every host route that is not a depth query holds what it has on the device in one DevScope (below).
 #include <hip/hip_runtime_api.h>
 
@@ -34,6 +34,7 @@
 #include "extract_device.hpp"
 #include "topology_device.hpp"
 #include "interval_device.hpp"
+#include "flatten_device.hpp"
 
 using fgfa_dev::set_error;
 
@@ -114,6 +115,10 @@ struct CStore {
     // validate, degree: the link index on one device (made on the first validate or degree call, never for a graph that is not asked)
     int topo_device = -1;
     fgfa_dev::TopoIndex topo;
+    // flatten: the legend on one device (made on the first flatten call), and the bases it adds up to
+    int flat_device = -1;
+    uint64_t *d_flat_legend = nullptr;
+    uint64_t flat_total = 0;
 
     ~CStore() {
         if (plan) flatgfa_dev_plan_destroy(plan);
@@ -127,6 +132,7 @@ struct CStore {
         if (gaf_ev) (void)hipEventDestroy(gaf_ev);
         if (d_gaf_seg_seq) (void)hipFree(d_gaf_seg_seq);
         fgfa_dev::topo_index_free(&topo);
+        if (d_flat_legend) (void)hipFree(d_flat_legend);
         stream_release(device, stream);
     }
 };
@@ -156,7 +162,7 @@ int count_devices(const std::string &who, int *ndev) {
     return FLATGFA_OK;
 }
 
-// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree -- holds on the device,
+// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree, flatten -- holds on the device,
 // given back on every way out: the work stream is waited for, then the job, the events and the memory go, then the streams
 // return to the pool.  A thread that still copies on one of the streams is joined first: its joiner is declared after the scope.
 struct DevScope {
@@ -2032,6 +2038,188 @@ int flatgfa_degree_table(flatgfa_t gfa, char **text, size_t *len) {
     std::string out;
     fgfa::emit_degree(gfa->view, deg.data(), &out);
     return give_text(out, text, len);
+}
+
+// ---- flatten (slow_odgi/flatten.py) ----
+
+extern "C++" {
+namespace {
+// How many BED lines a chunk holds: kFlatChunkLines, or what the tests ask for.
+uint64_t flatten_chunk_lines() {
+    if (const char *h = test_hook("FLATGFA_FLATTEN_CHUNK_LINES")) return std::max<uint64_t>(1, strtoull(h, nullptr, 10));
+    return fgfa_dev::kFlatChunkLines;
+}
+
+// The handle's legend on `device` (the current device), made once from the segments' spans.  A span that leaves seq_data,
+// where the reference could not have read the segment, is refused here.
+int ensure_flat_legend(CStore *cs, DevScope *sc) {
+    if (cs->flat_device == sc->device) return FLATGFA_OK;
+    const fgfa::View &v = cs->view;
+    const size_t S = v.segs.len;
+    if (S > 0x80000000ull) { set_error("flatten: graph too large for 32-bit ids"); return FLATGFA_ERR_TOO_LARGE; }
+    std::vector<uint32_t> len(S);
+    for (size_t i = 0; i < S; ++i) {
+        const fgfa::Span sp = v.segs[i].seq;
+        if (sp.start > sp.end || sp.end > v.seq_data.len) {
+            set_error("flatten: segment " + std::to_string(i) + " has a sequence span outside seq_data");
+            return FLATGFA_ERR_BOUNDS;
+        }
+        len[i] = sp.end - sp.start;
+    }
+    uint32_t *d_len = nullptr;
+    uint64_t *d_legend = nullptr;
+    CAPI_HIP(sc->upload(&d_len, len.data(), S));
+    CAPI_HIP(hipMalloc((void **)&d_legend, (S + 1) * 8));
+    int rc = fgfa_dev::flatten_legend(d_len, (uint32_t)S, d_legend, sc->stream);
+    uint64_t total = 0;
+    if (!rc && hipMemcpy(&total, d_legend + S, 8, hipMemcpyDeviceToHost) != hipSuccess) {
+        set_error("flatten: reading the legend's total failed");
+        rc = FLATGFA_ERR_HIP;
+    }
+    (void)sc->release(d_len);
+    if (rc) {
+        (void)hipFree(d_legend);
+        return rc;
+    }
+    if (cs->d_flat_legend) (void)hipFree(cs->d_flat_legend);  // (the handle moved to another device)
+    cs->d_flat_legend = d_legend;
+    cs->flat_total = total;
+    cs->flat_device = sc->device;
+    return FLATGFA_OK;
+}
+
+// One flatten call between its two halves: everything is checked and counted (open) before a byte is delivered (emit).
+struct FlatCall {
+    DevScope sc;
+    fgfa_dev::FlatJob *job = nullptr;
+    fgfa_dev::FlatSeqs seqs;
+    const uint8_t *name = nullptr;
+    size_t name_len = 0;
+    int what = 0;
+    uint64_t fasta_bytes = 0, bed_bytes = 0;
+};
+
+int flat_open(CStore *gfa, FlatCall *c, const char *name, size_t name_len, int what) {
+    c->name = (const uint8_t *)name, c->name_len = name_len, c->what = what;
+    const fgfa::View &v = gfa->view;
+    const size_t N = v.steps.len, P = v.paths.len;
+    // the paths' steps numbered one behind another, whatever their spans do in the pool (they may overlap, alias or be empty)
+    std::vector<uint64_t> pstart;
+    std::vector<uint32_t> prec;
+    if (what & 2) {
+        if (N > 0xFFFFFFFFull || P > 0xFFFFFFFEull) { set_error("flatten: graph too large for 32-bit ids"); return FLATGFA_ERR_TOO_LARGE; }
+        pstart.assign(P + 1, 0), prec.assign(3 * P, 0);
+        for (size_t p = 0; p < P; ++p) {
+            const fgfa::Span sp = v.paths[p].steps, nm = v.paths[p].name;
+            if (sp.start > sp.end || sp.end > N) { set_error("flatten: a path has a step span outside the steps pool"); return FLATGFA_ERR_BOUNDS; }
+            if (nm.start > nm.end || nm.end > v.name_data.len) { set_error("flatten: a path has a name span outside name_data"); return FLATGFA_ERR_BOUNDS; }
+            prec[3 * p] = sp.start, prec[3 * p + 1] = nm.start, prec[3 * p + 2] = nm.len();
+            pstart[p + 1] = pstart[p] + sp.len();
+        }
+    }
+    DevScope &sc = c->sc;
+    if (int rc = open_scope(gfa, &sc, "flatten")) return rc;
+    if (int rc = ensure_flat_legend(gfa, &sc)) return rc;
+    c->job = sc.hold<fgfa_dev::FlatJob, fgfa_dev::flatten_free>(fgfa_dev::flatten_new(flatten_chunk_lines()));
+    if (what & 1) {
+        if (int rc = ensure_gaf_seqs(gfa, sc.device)) return rc;  // (starts and bases, kept with the handle)
+        c->seqs.legend = gfa->d_flat_legend, c->seqs.seg_seq = gfa->d_gaf_seg_seq, c->seqs.seq_data = gfa->d_gaf_seq_data;
+        c->seqs.n_segs = (uint32_t)v.segs.len, c->seqs.total = gfa->flat_total;
+        c->fasta_bytes = fgfa_dev::flatten_fasta_bytes(gfa->flat_total, name_len);
+    }
+    if (what & 2) {
+        fgfa_dev::FlatPaths g;
+        uint64_t *d_pstart = nullptr;
+        uint32_t *d_prec = nullptr, *d_steps = nullptr;
+        uint8_t *d_names = nullptr;
+        CAPI_HIP(sc.upload(&d_pstart, pstart.data(), P + 1));
+        CAPI_HIP(sc.upload(&d_prec, prec.data(), 3 * P));
+        CAPI_HIP(sc.upload(&d_names, v.name_data.data, v.name_data.len));
+        if (sc.resident) d_steps = gfa->d_steps;  // (read in place)
+        else CAPI_HIP(sc.upload(&d_steps, v.steps.data, N));
+        g.legend = gfa->d_flat_legend, g.n_segs = (uint32_t)v.segs.len, g.steps = d_steps, g.pstart = d_pstart, g.prec = d_prec;
+        g.name_data = d_names, g.n_paths = (uint32_t)P, g.n_lines = pstart[P];
+        if (int rc = fgfa_dev::flatten_bed_begin(c->job, g, c->name, name_len, sc.stream, &c->bed_bytes)) return rc;
+    }
+    return FLATGFA_OK;
+}
+
+int flat_emit(FlatCall *c, flatgfa_sink_t sink, void *ctx) {
+    if (c->what & 1)
+        if (int rc = fgfa_dev::flatten_fasta(c->job, c->seqs, c->name, c->name_len, c->sc.stream, sink, ctx)) return rc;
+    if (c->what & 2)
+        if (int rc = fgfa_dev::flatten_bed_emit(c->job, sink, ctx)) return rc;
+    return FLATGFA_OK;
+}
+
+int flat_args(const char *who, flatgfa_t gfa, const char *name, size_t name_len, const void *a, const void *b) {
+    if (gfa && a && b && (name || !name_len)) return FLATGFA_OK;
+    set_error(std::string(who) + ": NULL argument");
+    return FLATGFA_ERR_ARG;
+}
+
+// the stream into a malloc'd buffer of the size flat_open counted
+struct TextSink {
+    char *buf;
+    size_t cap, at;
+    static int take(void *ctx, const char *bytes, size_t n) {
+        TextSink *t = static_cast<TextSink *>(ctx);
+        if (n > t->cap - t->at) return 1;
+        memcpy(t->buf + t->at, bytes, n);
+        t->at += n;
+        return 0;
+    }
+};
+
+int flat_text(const char *who, flatgfa_t gfa, const char *name, size_t name_len, int what, char **text, size_t *len) {
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (int rc = flat_args(who, gfa, name, name_len, text, len)) return rc;
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    FlatCall c;
+    if (int rc = flat_open(gfa, &c, name, name_len, what)) return rc;
+    TextSink t{nullptr, (size_t)(c.fasta_bytes + c.bed_bytes), 0};
+    t.buf = (char *)malloc(t.cap + 1);
+    if (!t.buf) { set_error(std::string(who) + ": out of memory"); return FLATGFA_ERR_IO; }
+    int rc = flat_emit(&c, TextSink::take, &t);
+    if (!rc && t.at != t.cap) { set_error(std::string(who) + ": internal: the text is not as long as it was counted"); rc = FLATGFA_ERR_HIP; }
+    if (rc) {
+        free(t.buf);
+        return rc;
+    }
+    t.buf[t.cap] = 0;
+    *text = t.buf;
+    *len = t.cap;
+    return FLATGFA_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int flatgfa_flatten_legend(flatgfa_t gfa, uint64_t *offset_out) {
+    if (!gfa || !offset_out) { set_error("flatgfa_flatten_legend: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    DevScope sc;
+    if (int rc = open_scope(gfa, &sc, "flatten")) return rc;
+    if (int rc = ensure_flat_legend(gfa, &sc)) return rc;
+    CAPI_HIP(fgfa_dev::staged_copy(offset_out, gfa->d_flat_legend, (gfa->view.segs.len + 1) * 8, hipMemcpyDeviceToHost, sc.stream));
+    return FLATGFA_OK;
+}
+
+int flatgfa_flatten_fasta(flatgfa_t gfa, const char *name, size_t name_len, char **text, size_t *len) {
+    return flat_text("flatgfa_flatten_fasta", gfa, name, name_len, 1, text, len);
+}
+
+int flatgfa_flatten_bed(flatgfa_t gfa, const char *name, size_t name_len, char **text, size_t *len) {
+    return flat_text("flatgfa_flatten_bed", gfa, name, name_len, 2, text, len);
+}
+
+int flatgfa_flatten_stream(flatgfa_t gfa, const char *name, size_t name_len, int what, flatgfa_sink_t sink, void *ctx) {
+    if (int rc = flat_args("flatgfa_flatten_stream", gfa, name, name_len, (const void *)sink, (const void *)sink)) return rc;
+    if (what < 1 || what > 3) { set_error("flatgfa_flatten_stream: `what` is 1 (FASTA), 2 (BED) or 3 (both)"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    FlatCall c;
+    if (int rc = flat_open(gfa, &c, name, name_len, what)) return rc;
+    return flat_emit(&c, sink, ctx);
 }
 
 }  // extern "C"

@@ -5,12 +5,13 @@
 //   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [--bed-paths FILE.bed] [-s PATHS]
 //            | window-depth PATH SIZE | window-depth-all SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l]
 //            | extract -n NAME -c DIST [-d N] [-e N] | position -p PATH,OFFSET,+ | validate | degree
+//            | flatten [-n NAME] [-f FASTA] [-b BED]
 //
 // With no -i/-I the GFA text is read from stdin; with no COMMAND the graph is written out
 // (-o binary, -O text, otherwise text on stdout).  `depth` output is byte-identical to the
 // reference's and is computed on the GPU, as are `matrix` (cmds.rs:453-475), `position` (cmds.rs:105-152), and `chop`
 // (cli/main.rs:139-159) and `extract` (cmds.rs:174-215), whose graph is written out as the input graph would be; `validate` and `degree` print what slow_odgi's validate.py and
-// degree.py print.  Everything else in the reference CLI is out of scope.
+// degree.py print, `flatten` what its flatten.py prints (or, with -f / -b, what `odgi flatten` writes to those files).  Everything else in the reference CLI is out of scope.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -49,6 +50,17 @@ static bool read_names(const char *file, std::vector<std::string> *out) {
     if (!cur.empty()) out->push_back(cur);
     fclose(f);
     return true;
+}
+
+// flatgfa_sink_t over a file descriptor (ctx: the int); a short or failed write stops the call
+static int write_fd(void *ctx, const char *p, size_t n) {
+    while (n) {
+        const ssize_t w = write(*static_cast<int *>(ctx), p, n);
+        if (w <= 0) return 1;
+        p += w;
+        n -= (size_t)w;
+    }
+    return 0;
 }
 
 static void write_all(const char *p, size_t n) {
@@ -109,7 +121,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree";
+    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -248,6 +260,41 @@ int main(int argc, char **argv) {
         if (cmd == "validate" ? flatgfa_validate_table(g, &text, &n) : flatgfa_degree_table(g, &text, &n)) rc = die(cmd.c_str());
         else write_all(text, n);
         flatgfa_free_text(text);
+    } else if (cmd == "flatten") {
+        // slow_odgi flatten (flatten.py:49-57, __main__.py:178): FASTA then BED on stdout; with -f / -b each goes to its file and
+        // nothing to stdout, as `odgi flatten -f -b` (tests/turnt.toml:46-49).  Written as it streams, never held whole.
+        const char *name = nullptr, *fasta = nullptr, *bed = nullptr;
+        bool bad = false;
+        for (; i < argc; ++i) {
+            const std::string a = argv[i];
+            const char **dst = a == "-n" ? &name : a == "-f" ? &fasta : a == "-b" ? &bed : nullptr;
+            if (!dst || i + 1 >= argc) { bad = true; break; }
+            *dst = argv[++i];
+        }
+        if (bad) {
+            fprintf(stderr, "usage: fgfa flatten [-n NAME] [-f FASTA] [-b BED]\n");
+            flatgfa_free(g);
+            return 2;
+        }
+        // the default name: the input's file name with its last extension cut and ".og" in its place (for x.gfa the
+        // reference's G[:-4] + ".og")
+        std::string nm = name ? name : "";
+        if (!name) {
+            nm = in_flat ? in_flat : in_gfa ? in_gfa : "-";
+            const size_t dot = nm.rfind('.'), slash = nm.rfind('/');
+            if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) nm.resize(dot);
+            nm += ".og";
+        }
+        const auto to = [&](const char *file, int what) -> int {
+            int fd = STDOUT_FILENO;
+            if (file && (fd = open(file, O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0) { fprintf(stderr, "fgfa: cannot write %s\n", file); return 1; }
+            const int r = flatgfa_flatten_stream(g, nm.data(), nm.size(), what, write_fd, &fd) ? die("flatten") : 0;
+            if (file && close(fd) && !r) { fprintf(stderr, "fgfa: cannot write %s\n", file); return 1; }
+            return r;
+        };
+        if (!fasta && !bed) rc = to(nullptr, 3);
+        if (fasta) rc = to(fasta, 1);
+        if (bed && !rc) rc = to(bed, 2);
     } else if (cmd == "toc") {
         bool bytes = i < argc && !strcmp(argv[i], "-b");
         static const char *names[11] = {"header", "segs", "paths", "links", "steps", "seq_data",

@@ -522,8 +522,51 @@ class FlatGFA:
         _check(_lib.lib().flatgfa_degree_table(self._h, ctypes.byref(p), ctypes.byref(n)), "degree")
         return _take_text(p, n)
 
+    # ---- flatten (slow_odgi/flatten.py) ----
+    def flatten_legend(self) -> np.ndarray:
+        """slow_odgi/flatten.py:13-19 -> uint64[segment_count + 1]: the bases before each segment in pool order, then all of
+        them; segment s lies at [legend[s], legend[s + 1]) of the FASTA's bases."""
+        out = np.zeros(self.segment_count + 1, np.uint64)
+        _check(_lib.lib().flatgfa_flatten_legend(self._h, out.ctypes.data), "flatten_legend")
+        return out
 
-MISSING_LINK_DT = np.dtype([("path", "<u4"), ("step", "<u4"), ("src", "<u4"), ("dst", "<u4")])  # flatgfa_missing_link_t
+    def flatten_fasta(self, name: bytes) -> bytes:
+        """The FASTA record `slow_odgi flatten` prints (flatten.py:51-55): `>name`, then every segment's bases, 80 to a line."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(_lib.lib().flatgfa_flatten_fasta(self._h, name, len(name), ctypes.byref(p), ctypes.byref(n)), "flatten_fasta")
+        return _take_text(p, n)
+
+    def flatten_bed(self, name: bytes) -> bytes:
+        """The BED table `slow_odgi flatten` prints (flatten.py:23-41): per path step where its segment lies in the FASTA."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(_lib.lib().flatgfa_flatten_bed(self._h, name, len(name), ctypes.byref(p), ctypes.byref(n)), "flatten_bed")
+        return _take_text(p, n)
+
+    def flatten_stream(self, name: bytes, what: int, write) -> None:
+        """flatgfa_flatten_stream: `write(bytes)` receives the text in order, a piece at a time (what: 1 the FASTA, 2 the BED,
+        3 both, the FASTA first).  A `write` that raises, or returns something true, stops the call."""
+        raised = []
+
+        def sink(_ctx, ptr, n):
+            try:
+                return 1 if write(ctypes.string_at(ptr, n)) else 0  # (a piece is a few megabytes: within string_at's C int)
+            except BaseException as e:  # noqa: BLE001  (must not unwind through the C caller)
+                raised.append(e)
+                return 1
+        rc = _lib.lib().flatgfa_flatten_stream(self._h, name, len(name), int(what), _lib.SINK_T(sink), None)
+        if raised:
+            raise raised[0]
+        _check(rc, "flatten_stream")
+
+    def flatten_to(self, name: bytes, fasta_file=None, bed_file=None) -> None:
+        """`odgi flatten -f FASTA -b BED`: the FASTA and the BED into open binary files, written as they stream from the
+        device (either may be None)."""
+        for f, what in ((fasta_file, 1), (bed_file, 2)):
+            if f is not None:
+                self.flatten_stream(name, what, lambda b, f=f: f.write(b) and None)
+
+
+MISSING_LINK_DT =np.dtype([("path", "<u4"), ("step", "<u4"), ("src", "<u4"), ("dst", "<u4")])  # flatgfa_missing_link_t
 
 SHARD_WHOLE_PATHS = 1  # FLATGFA_SHARD_WHOLE_PATHS
 SHARD_NO_RCCL = 2      # FLATGFA_SHARD_NO_RCCL
