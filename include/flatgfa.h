@@ -258,6 +258,29 @@ void flatgfa_gaf_events_free(flatgfa_gaf_events_t *ev);
  * FLATGFA_ERR_ARG; a span, step or link naming something out of range: FLATGFA_ERR_BOUNDS; 2^31 or more new
  * segments, or more than 2^32 - 1 new steps or links: FLATGFA_ERR_TOO_LARGE, found before any output is allocated. */
 int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out);
+/* inject (slow_odgi/inject.py, `odgi inject`; `fgfa inject -b BED [-l]`): line l -- bases [starts[l], ends[l]) of path
+ * path_ids[l], to be called names[l] (name_lens[l] bytes) -- cuts the segments under its two ends so that both fall on
+ * segment seams and adds a path that walks exactly the interval.  All lines are handled in one pass, which gives what the
+ * reference gives line by line: a segment with k distinct cuts becomes k + 1 segments, numbered in old-segment order and by
+ * position and named id + 1 (seq spans into the old seq_data, no optional fields); an old path keeps its name, loses its
+ * overlaps, and walks the pieces of its steps (reversed, all backward, for a backward step); the new paths follow the old
+ * ones in line order, each the steps of its path after cutting from the first that starts at or after `start` up to, but not
+ * including, the first that ends after `end` (none when start >= end or start is at or past the path's end).  links as
+ * flatgfa_chop's.  *out is a new heap handle that owns its pools.  The work runs on the GPU (the device `gfa` is resident
+ * on, else device 0); `gfa` is not made resident, and a resident one is only read.
+ * Refused with FLATGFA_ERR_ARG before any device work, flatgfa_last_error naming the line, where the reference's
+ * line-by-line dictionary update does what one pass cannot: a new name that is a path of `gfa` already (the reference
+ * replaces that path), a new name an earlier line gave (the later wins there), and -- flatgfa_inject_bed only -- a line on a
+ * path that `gfa` lacks but an earlier line injects.  A path id, span, step or link out of range: FLATGFA_ERR_BOUNDS; 2^31
+ * or more new segments, or more than 2^32 - 1 new steps, links or paths: FLATGFA_ERR_TOO_LARGE, found before any output is
+ * allocated.  n == 0: a copy of the graph with no cuts.
+ * flatgfa_inject_bed reads BED text: "path<TAB>start<TAB>end<TAB>new_name" lines ('#' lines and empty lines skipped; a line
+ * with fewer than four columns, with an empty new name, or without a number in the second or third: FLATGFA_ERR_ARG; a number
+ * past 2^64 - 1 wraps, as the --bed-paths reader's does); a line whose path `gfa` does not have is skipped silently, as the
+ * reference does.  The line a message names is counted from 1 over every line of the text, comments and empty lines too. */
+int flatgfa_inject(flatgfa_t gfa, const uint32_t *path_ids, const uint64_t *starts, const uint64_t *ends, const char *const *names,
+                   const size_t *name_lens, uint64_t n, int links, flatgfa_t *out);
+int flatgfa_inject_bed(flatgfa_t gfa, const char *bed, size_t bed_len, int links, flatgfa_t *out);
 /* extract (flatgfa/src/ops/extract.rs; `fgfa extract -n NAME -c DIST [-d N] [-e N]`, cli/cmds.rs:174-215): the subgraph
  * around one segment.  flatgfa_find_seg is FlatGFA::find_seg (flatgfa.rs:380-384): the id of the first segment with that
  * name, or -1.  The new graph holds the old header; the origin as segment 0 and every segment within link_distance links
@@ -566,6 +589,22 @@ int flatgfa_dev_chop_count(const flatgfa_dev_graph_t *g, uint64_t max_size, uint
 int flatgfa_dev_chop_fill(flatgfa_dev_chop_t *job, uint32_t *steps, uint32_t *path_begin, uint32_t *path_end, uint32_t *seg_len,
                           void *stream);
 void flatgfa_dev_chop_free(flatgfa_dev_chop_t *job);
+/* inject (flatgfa_inject, without links or names) of a graph image in device memory, in two stream-ordered calls modelled on
+ * the chop pair.  d_path_id u32[n], d_start / d_end u64[n] are the lines, in device memory.  flatgfa_dev_inject_count
+ * checks the image (g->seg_len is required) and the lines, builds the cut table, waits for `stream` once to read the totals
+ * -- *n_segs_out new segments, *n_steps_out new steps, *n_paths_out = g->n_paths + n paths -- and, when they fit 32-bit
+ * ids, enqueues seg_first u32[n_segs + 1] and returns a job; errors as flatgfa_inject's, with no job.
+ * flatgfa_dev_inject_fill enqueues the new image into caller memory: steps u32[*n_steps_out], path_begin / path_end
+ * u32[*n_paths_out] (the old paths, then one per line) and seg_len u32[*n_segs_out] -- a flatgfa_dev_graph_t that
+ * flatgfa_dev_plan_create takes.  g's arrays, the lines and seg_first must stay as they are until the fill is done; nothing is
+ * held per call outside the job.  flatgfa_dev_inject_free waits for the job's stream and releases its scratch. */
+typedef struct flatgfa_dev_inject flatgfa_dev_inject_t;
+int flatgfa_dev_inject_count(const flatgfa_dev_graph_t *g, const uint32_t *d_path_id, const uint64_t *d_start, const uint64_t *d_end, uint64_t n,
+                             uint32_t *seg_first, void *stream, flatgfa_dev_inject_t **job, uint64_t *n_segs_out, uint64_t *n_steps_out,
+                             uint64_t *n_paths_out);
+int flatgfa_dev_inject_fill(flatgfa_dev_inject_t *job, uint32_t *steps, uint32_t *path_begin, uint32_t *path_end, uint32_t *seg_len,
+                            void *stream);
+void flatgfa_dev_inject_free(flatgfa_dev_inject_t *job);
 /* The legend of flatten (flatten.py:13-19; flatgfa_flatten_legend) of a graph image in device memory: d_offset_out[s] = the
  * sum of g->seg_len before s, d_offset_out[n_segs] = the sum of all, in 64 bits (g->seg_len is required: FLATGFA_ERR_ARG when
  * NULL; the steps and spans are not read).  Enqueued on `stream`, which is waited for: the scan's scratch goes before the

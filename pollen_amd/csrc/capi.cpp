@@ -16,6 +16,8 @@
 #include <chrono>
 #include <mutex>
 #include <thread>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include <malloc.h>
@@ -30,6 +32,7 @@
 #include "flatgfa_core.hpp"
 #include "gaf_device.hpp"
 #include "chop_device.hpp"
+#include "inject_device.hpp"
 #include "gaf_lookup_device.hpp"
 #include "extract_device.hpp"
 #include "topology_device.hpp"
@@ -1588,21 +1591,12 @@ void flatgfa_dev_gaf_free(flatgfa_dev_gaf_t *job) { delete job; }
 
 // ---- chop (ops/chop.rs) ----
 
-int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
-    if (out) *out = nullptr;
-    if (!gfa || !out) { set_error("flatgfa_chop: NULL argument"); return FLATGFA_ERR_ARG; }
-    if (max_size == 0) { set_error("flatgfa_chop: the maximum segment size must be at least 1"); return FLATGFA_ERR_ARG; }
-    std::lock_guard<std::mutex> op(gfa->op_mu);
+// What chop and inject read of `gfa` on the scope's device: the steps, spans and lengths (the resident image's, when there is
+// one), the seq starts, the links when they are wanted; and room for seg_first.
+static int upload_chop_input(CStore *gfa, DevScope &sc, bool links, fgfa_dev::ChopIn *in_out, uint32_t **seg_first_out) {
     const fgfa::View &v = gfa->view;
     const size_t N = v.steps.len, P = v.paths.len, S = v.segs.len, L = links ? v.links.len : 0;
-    if (N > 0xFFFFFFFFull || S > 0x80000000ull || P > 0xFFFFFFFFull || L > 0xFFFFFFFFull) {
-        set_error("flatgfa_chop: graph too large for 32-bit ids");
-        return FLATGFA_ERR_TOO_LARGE;
-    }
-    DevScope sc;
-    if (int rc = open_scope(gfa, &sc, "chop")) return rc;
     const bool resident = sc.resident;  // (its image is read in place)
-    hipStream_t st = sc.stream;
     // (an array of no elements stays NULL below, which chop_fill reads as "not wanted": sc.alloc would make it one element long)
     // what chop reads: the steps, spans and lengths (the resident image's, when there is one), the seq starts, the links
     const size_t Pa = (P + 63) & ~(size_t)63, Sa = (S + 63) & ~(size_t)63;
@@ -1644,6 +1638,29 @@ int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
         CAPI_HIP(fgfa_dev::staged_copy(d_links, v.links.data, L * 16, hipMemcpyHostToDevice, nullptr));
         in.links = d_links;
     }
+    *in_out = in;
+    *seg_first_out = d_seg_first;
+    return FLATGFA_OK;
+}
+
+int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
+    if (out) *out = nullptr;
+    if (!gfa || !out) { set_error("flatgfa_chop: NULL argument"); return FLATGFA_ERR_ARG; }
+    if (max_size == 0) { set_error("flatgfa_chop: the maximum segment size must be at least 1"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    const fgfa::View &v = gfa->view;
+    const size_t N = v.steps.len, P = v.paths.len, S = v.segs.len, L = links ? v.links.len : 0;
+    if (N > 0xFFFFFFFFull || S > 0x80000000ull || P > 0xFFFFFFFFull || L > 0xFFFFFFFFull) {
+        set_error("flatgfa_chop: graph too large for 32-bit ids");
+        return FLATGFA_ERR_TOO_LARGE;
+    }
+    DevScope sc;
+    if (int rc = open_scope(gfa, &sc, "chop")) return rc;
+    hipStream_t st = sc.stream;
+    fgfa_dev::ChopIn in;
+    uint32_t *d_seg_first = nullptr;
+    if (int rc = upload_chop_input(gfa, sc, links != 0, &in, &d_seg_first)) return rc;
+    const size_t Pa = (P + 63) & ~(size_t)63;
     fgfa_dev::ChopJob *job = sc.hold<fgfa_dev::ChopJob, fgfa_dev::chop_free>(fgfa_dev::chop_new());
     uint64_t S2 = 0, N2 = 0, L2 = 0;
     int rc = fgfa_dev::chop_count(job, in, max_size, links != 0, d_seg_first, st, &S2, &N2, &L2);
@@ -1678,6 +1695,164 @@ int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
     cs->view = h.view();
     *out = cs.release();
     return FLATGFA_OK;
+}
+
+// ---- inject (slow_odgi/inject.py) ----
+
+namespace {
+// The three cases a batch refuses (the reference updates its path dictionary in place, line by line): new name l equals a path
+// name of the graph, or an earlier line's new name.  `by_name` holds the graph's path names; line_no[l] is what line l is called
+// in the message (the line of the BED text, counted from 1), l + 1 when there is none.
+int inject_check_names(const std::unordered_map<std::string, uint32_t> &by_name, const char *const *names, const size_t *name_lens, uint64_t n,
+                       const size_t *line_no) {
+    std::unordered_set<std::string> fresh;
+    for (uint64_t l = 0; l < n; ++l) {
+        std::string nm(names[l] ? names[l] : "", name_lens[l]);
+        const std::string where = "inject: line " + std::to_string(line_no ? line_no[l] : l + 1);
+        if (by_name.count(nm)) {
+            set_error(where + ": the new name '" + nm + "' is a path of the graph already");
+            return FLATGFA_ERR_ARG;
+        }
+        if (!fresh.insert(std::move(nm)).second) {
+            set_error(where + ": the new name was given by an earlier line");
+            return FLATGFA_ERR_ARG;
+        }
+    }
+    return FLATGFA_OK;
+}
+
+void path_names(const fgfa::View &v, std::unordered_map<std::string, uint32_t> *out) {
+    std::unordered_map<std::string, uint32_t> &m = *out;
+    m.reserve(v.paths.len);
+    for (size_t i = 0; i < v.paths.len; ++i) {  // (the first path of a name, as View::find_path)
+        const fgfa::Span s = v.paths[i].name;
+        m.emplace(std::string((const char *)v.name_data.data + s.start, s.len()), (uint32_t)i);
+    }
+}
+
+// chop's route with the lines beside the graph; the names were checked
+int inject_locked(CStore *gfa, const uint32_t *path_ids, const uint64_t *starts, const uint64_t *ends, const char *const *names,
+                  const size_t *name_lens, uint64_t n, int links, flatgfa_t *out) {
+    const fgfa::View &v = gfa->view;
+    const size_t N = v.steps.len, P = v.paths.len, S = v.segs.len, L = links ? v.links.len : 0;
+    size_t name_bytes = v.name_data.len;
+    for (uint64_t l = 0; l < n; ++l) name_bytes += name_lens[l];
+    if (N > 0xFFFFFFFFull || S > 0x80000000ull || P + n > 0xFFFFFFFFull || n >= 0x7FFFFFFFull || L > 0xFFFFFFFFull || name_bytes > 0xFFFFFFFFull) {
+        set_error("flatgfa_inject: graph too large for 32-bit ids");
+        return FLATGFA_ERR_TOO_LARGE;
+    }
+    DevScope sc;
+    if (int rc = open_scope(gfa, &sc, "inject")) return rc;
+    hipStream_t st = sc.stream;
+    fgfa_dev::ChopIn in;
+    uint32_t *d_seg_first = nullptr;
+    if (int rc = upload_chop_input(gfa, sc, links != 0, &in, &d_seg_first)) return rc;
+    fgfa_dev::InjectLines ln;
+    ln.n = n;
+    if (n) {
+        uint32_t *d_ids = nullptr;
+        uint64_t *d_lo = nullptr, *d_hi = nullptr;
+        CAPI_HIP(sc.upload(&d_ids, path_ids, n));
+        CAPI_HIP(sc.upload(&d_lo, starts, n));
+        CAPI_HIP(sc.upload(&d_hi, ends, n));
+        ln.path_id = d_ids;
+        ln.start = d_lo;
+        ln.end = d_hi;
+    }
+    fgfa_dev::InjectJob *job = sc.hold<fgfa_dev::InjectJob, fgfa_dev::inject_free>(fgfa_dev::inject_new());
+    uint64_t S2 = 0, N2 = 0, L2 = 0;
+    int rc = fgfa_dev::inject_count(job, in, ln, links != 0, d_seg_first, st, &S2, &N2, &L2);
+    if (rc) return rc;
+    // the outputs, now that their sizes are known to fit
+    const size_t P2 = P + n, Pa = (P2 + 63) & ~(size_t)63;
+    fgfa_dev::ChopOut o;
+    if (N2) CAPI_HIP(sc.alloc(&o.steps, N2));
+    if (Pa) CAPI_HIP(sc.alloc(&o.path_begin, 2 * Pa));
+    o.path_end = o.path_begin ? o.path_begin + Pa : nullptr;
+    if (S2) CAPI_HIP(sc.alloc(&o.seg_recs, S2 * 6));
+    if (L2) CAPI_HIP(sc.alloc(&o.links, L2 * 4));
+    rc = fgfa_dev::inject_fill(job, o, st);
+    if (rc) return rc;
+    auto cs = std::make_unique<CStore>();
+    fgfa::Store &h = cs->heap;
+    std::thread alloc([&] { h.steps.resize(N2); });
+    Joiner joiner{alloc};
+    h.header.assign(v.header.begin(), v.header.end());
+    h.seq_data.assign(v.seq_data.begin(), v.seq_data.end());
+    h.name_data.reserve(name_bytes);
+    h.name_data.assign(v.name_data.begin(), v.name_data.end());
+    h.segs.resize(S2);
+    h.links.resize(L2);
+    std::vector<uint32_t> spans(2 * Pa);
+    CAPI_HIP(fgfa_dev::staged_copy(h.segs.data(), o.seg_recs, S2 * 24, hipMemcpyDeviceToHost, st));
+    CAPI_HIP(fgfa_dev::staged_copy(h.links.data(), o.links, L2 * 16, hipMemcpyDeviceToHost, st));
+    CAPI_HIP(fgfa_dev::staged_copy(spans.data(), o.path_begin, 2 * Pa * 4, hipMemcpyDeviceToHost, st));
+    alloc.join();
+    CAPI_HIP(fgfa_dev::staged_copy(h.steps.data(), o.steps, N2 * 4, hipMemcpyDeviceToHost, st));
+    h.paths.resize(P2);
+    for (size_t i = 0; i < P; ++i) h.paths[i] = fgfa::Path{v.paths[i].name, fgfa::Span{spans[i], spans[Pa + i]}, fgfa::Span{0, 0}};  // chop.py:56
+    for (size_t l = 0; l < n; ++l) {  // inject.py:91-92
+        const uint32_t at = (uint32_t)h.name_data.size();
+        h.name_data.insert(h.name_data.end(), (const uint8_t *)names[l], (const uint8_t *)names[l] + name_lens[l]);
+        h.paths[P + l] = fgfa::Path{fgfa::Span{at, (uint32_t)h.name_data.size()}, fgfa::Span{spans[P + l], spans[Pa + P + l]}, fgfa::Span{0, 0}};
+    }
+    cs->view = h.view();
+    *out = cs.release();
+    return FLATGFA_OK;
+}
+}  // namespace
+
+int flatgfa_inject(flatgfa_t gfa, const uint32_t *path_ids, const uint64_t *starts, const uint64_t *ends, const char *const *names,
+                   const size_t *name_lens, uint64_t n, int links, flatgfa_t *out) {
+    if (out) *out = nullptr;
+    if (!gfa || !out || (n && (!path_ids || !starts || !ends || !names || !name_lens))) { set_error("flatgfa_inject: NULL argument"); return FLATGFA_ERR_ARG; }
+    for (uint64_t l = 0; l < n; ++l) {
+        if (!names[l] && name_lens[l]) { set_error("flatgfa_inject: NULL argument"); return FLATGFA_ERR_ARG; }
+        if (!name_lens[l]) { set_error("inject: line " + std::to_string(l + 1) + ": the new name is empty"); return FLATGFA_ERR_ARG; }
+    }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    std::unordered_map<std::string, uint32_t> by_name;
+    path_names(gfa->view, &by_name);
+    if (int rc = inject_check_names(by_name, names, name_lens, n, nullptr)) return rc;
+    return inject_locked(gfa, path_ids, starts, ends, names, name_lens, n, links, out);
+}
+
+int flatgfa_inject_bed(flatgfa_t gfa, const char *bed, size_t bed_len, int links, flatgfa_t *out) {
+    if (out) *out = nullptr;
+    if (!gfa || !out || (bed_len && !bed)) { set_error("flatgfa_inject_bed: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::vector<fgfa::InjectBedLine> lines;
+    std::string err;
+    if (!fgfa::parse_inject_bed((const uint8_t *)bed, bed_len, &lines, &err)) { set_error(err); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    std::unordered_map<std::string, uint32_t> by_name;
+    path_names(gfa->view, &by_name);
+    // inject.py:87: a line whose path the graph does not have is skipped -- unless an earlier line made a path of that name
+    std::vector<uint32_t> ids;
+    std::vector<uint64_t> lo, hi;
+    std::vector<const char *> names;
+    std::vector<size_t> name_lens, line_no;
+    std::unordered_set<std::string> fresh;
+    for (size_t l = 0; l < lines.size(); ++l) {
+        const fgfa::InjectBedLine &b = lines[l];
+        const std::string path(bed + b.path_off, b.path_len);
+        const auto it = by_name.find(path);
+        if (it == by_name.end()) {
+            if (fresh.count(path)) {
+                set_error("inject: line " + std::to_string(b.line) + " names the path '" + path + "' that an earlier line injects");
+                return FLATGFA_ERR_ARG;
+            }
+            continue;
+        }
+        fresh.emplace(bed + b.name_off, b.name_len);
+        ids.push_back(it->second);
+        lo.push_back(b.start);
+        hi.push_back(b.end);
+        names.push_back(bed + b.name_off);
+        name_lens.push_back(b.name_len);
+        line_no.push_back(b.line);
+    }
+    if (int rc = inject_check_names(by_name, names.data(), name_lens.data(), ids.size(), line_no.data())) return rc;
+    return inject_locked(gfa, ids.data(), lo.data(), hi.data(), names.data(), name_lens.data(), ids.size(), links, out);
 }
 
 // ---- extract (ops/extract.rs) and position (ops/position.rs) ----

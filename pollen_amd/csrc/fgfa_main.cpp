@@ -3,7 +3,7 @@
 //
 //   fgfa [-i FILE.flatgfa | -I FILE.gfa] [-o OUT.flatgfa] [-O OUT.gfa] [COMMAND]
 //   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [--bed-paths FILE.bed] [-s PATHS]
-//            | window-depth PATH SIZE | window-depth-all SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l]
+//            | window-depth PATH SIZE | window-depth-all SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l] | inject -b BED [-l]
 //            | extract -n NAME -c DIST [-d N] [-e N] | position -p PATH,OFFSET,+ | validate | degree
 //            | flatten [-n NAME] [-f FASTA] [-b BED]
 //
@@ -121,7 +121,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten";
+    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -207,6 +207,35 @@ int main(int argc, char **argv) {
         flatgfa_t chopped = nullptr;
         if (flatgfa_chop(g, count, links ? 1 : 0, &chopped)) rc = die("chop");
         else rc = dump(chopped);
+    } else if (cmd == "inject") {
+        // slow_odgi inject --bed BED (`odgi inject -b`): fgfa inject -b BED [-l]
+        const char *bed_path = nullptr;
+        bool links = false, bad = false;
+        for (; i < argc; ++i) {
+            std::string a = argv[i];
+            if ((a == "-b" || a == "--bed") && i + 1 < argc) bed_path = argv[++i];
+            else if (a == "-l" || a == "--links") links = true;
+            else bad = true;
+        }
+        if (bad || !bed_path) {
+            fprintf(stderr, "usage: fgfa inject -b BED [-l]   (BED: path<TAB>start<TAB>end<TAB>new_name lines)\n");
+            flatgfa_free(g);
+            return 2;
+        }
+        std::string bed;
+        if (FILE *f = fopen(bed_path, "rb")) {
+            char tmp[1 << 16];
+            size_t r;
+            while ((r = fread(tmp, 1, sizeof tmp, f)) > 0) bed.append(tmp, r);
+            fclose(f);
+        } else {
+            fprintf(stderr, "fgfa: cannot open %s\n", bed_path);
+            flatgfa_free(g);
+            return 1;
+        }
+        flatgfa_t injected = nullptr;
+        if (flatgfa_inject_bed(g, bed.data(), bed.size(), links ? 1 : 0, &injected)) rc = die("inject");
+        else rc = dump(injected);
     } else if (cmd == "extract") {
         // cli/cmds.rs:174-215: fgfa extract -n NAME -c DIST [-d N] [-e N]
         uint64_t name = 0, dist = 0, max_dist = 300000, iters = 6;

@@ -1073,6 +1073,43 @@ bool parse_bed(const uint8_t *buf, size_t n, Bed *out, std::string *err) {
     return true;
 }
 
+bool parse_inject_bed(const uint8_t *buf, size_t n, std::vector<InjectBedLine> *out, std::string *err) {
+    out->clear();
+    size_t pos = 0, line_no = 0;
+    while (pos < n) {
+        const uint8_t *nl = (const uint8_t *)memchr(buf + pos, '\n', n - pos);
+        const uint8_t *p = buf + pos, *e = nl ? nl : buf + n;
+        pos = (size_t)(e - buf) + 1;
+        ++line_no;
+        if (e > p && e[-1] == '\r') --e;
+        if (p == e || *p == '#') continue;
+        const auto fail = [&](const char *what) {
+            *err = "inject BED: line " + std::to_string(line_no) + ": " + what;
+            return false;
+        };
+        const uint8_t *col[4], *col_end[4];
+        const uint8_t *q = p;
+        for (int c = 0; c < 4; ++c) {
+            col[c] = q;
+            const uint8_t *t = c < 3 ? (const uint8_t *)memchr(q, '\t', (size_t)(e - q)) : nullptr;
+            if (c < 3 && !t) return fail("fewer than four tab-separated columns");
+            if (c == 3) t = (const uint8_t *)memchr(q, '\t', (size_t)(e - q));  // (further columns are ignored)
+            col_end[c] = t ? t : e;
+            q = t ? t + 1 : e;
+        }
+        uint64_t num[2] = {0, 0};
+        for (int c = 1; c <= 2; ++c) {
+            const uint8_t *s = col[c];
+            while (s < col_end[c] && *s >= '0' && *s <= '9') num[c - 1] = num[c - 1] * 10 + (uint64_t)(*s++ - '0');
+            if (s == col[c] || s != col_end[c]) return fail("expected number");
+        }
+        if (col_end[3] == col[3]) return fail("the new name is empty");
+        out->push_back(InjectBedLine{(size_t)(col[0] - buf), (size_t)(col_end[0] - col[0]), (size_t)(col[3] - buf), (size_t)(col_end[3] - col[3]), num[0],
+                                     num[1], line_no});
+    }
+    return true;
+}
+
 void make_windows(const uint8_t *name, size_t name_len, uint64_t start, uint64_t end, uint64_t size, Bed *out) {
     *out = Bed();
     out->name_data.assign(name, name + name_len);

@@ -253,6 +253,17 @@ struct Bed {
     std::vector<BedEntry> entries;
 };
 bool parse_bed(const uint8_t *buf, size_t n, Bed *out, std::string *err);
+// The BED of inject (slow_odgi/inject.py, mygfa.Bed): "path<TAB>start<TAB>end<TAB>new_name" lines, `#` lines skipped, numbers as
+// parse_bed reads them.  The names are offsets into the text.  Unlike parse_bed an unterminated last line counts, a '\r' before
+// the newline does not belong to the name, and an empty line is skipped.  A line with fewer than four columns, with an empty
+// new name or without a number where one belongs: false, and *err names the line (counted from 1 over every line of the text,
+// comments and empty lines too; `line` of an entry is the same number).  A number past 2^64 - 1 wraps, as parse_bed's does.
+struct InjectBedLine {
+    size_t path_off, path_len, name_off, name_len;
+    uint64_t start, end;
+    size_t line;
+};
+bool parse_inject_bed(const uint8_t *buf, size_t n, std::vector<InjectBedLine> *out, std::string *err);
 // Windows{name, start, end, size}.as_bed(), window_depth.rs:22-57
 void make_windows(const uint8_t *name, size_t name_len, uint64_t start, uint64_t end, uint64_t size, Bed *out);
 // window_depth.rs:69-77

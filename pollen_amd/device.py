@@ -350,6 +350,45 @@ def chop(graph: DeviceGraph, max_size: int, stream=None) -> Tuple[DeviceGraph, o
         return DeviceGraph.from_tensors(steps, pb, pe, n_segs.value, seg_len), seg_first
 
 
+def inject(graph: DeviceGraph, path_ids, starts, ends, stream=None) -> Tuple[DeviceGraph, object]:
+    """inject (slow_odgi/inject.py, without links or names) of a resident graph image, on the device: line l is bases
+    [starts[l], ends[l]) of path path_ids[l] (int32 / int64 / int64 CUDA tensors of one length).  Returns the new image as a
+    DeviceGraph -- the old paths, cut, then one new path per line; a valid input to DepthPlan -- and seg_first
+    (int32[n_segs + 1]: old segment s became the new segments [seg_first[s], seg_first[s + 1])).  Needs graph.seg_len.  Waits
+    for the stream once, to learn the sizes (flatgfa_dev_inject_count); the rest is enqueued on it (torch's current stream by
+    default)."""
+    torch = _torch()
+    if graph.seg_len is None:
+        raise FlatGFAError("inject: the graph has no seg_len", -1)
+    n = int(path_ids.numel())
+    assert path_ids.dtype == torch.int32 and starts.dtype == torch.int64 and ends.dtype == torch.int64
+    assert starts.numel() == n and ends.numel() == n
+    assert all(t.is_cuda and t.is_contiguous() for t in (path_ids, starts, ends))
+    with torch.cuda.device(graph.device):
+        st = stream if stream is not None else torch.cuda.current_stream(graph.device)
+        g = graph.c_struct()
+        seg_first = torch.empty(graph.n_segs + 1, dtype=torch.int32, device=graph.device)
+        job = ctypes.c_void_p()
+        n_segs, n_steps, n_paths = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        L = _lib.lib()
+
+        def ptr(t):
+            return t.data_ptr() if t.numel() else None
+        _check(L.flatgfa_dev_inject_count(ctypes.byref(g), ptr(path_ids), ptr(starts), ptr(ends), n, seg_first.data_ptr(),
+                                          ctypes.c_void_p(st.cuda_stream), ctypes.byref(job), ctypes.byref(n_segs), ctypes.byref(n_steps),
+                                          ctypes.byref(n_paths)), "dev_inject_count")
+        try:
+            steps = torch.empty(n_steps.value, dtype=torch.int32, device=graph.device)
+            pb = torch.empty(n_paths.value, dtype=torch.int32, device=graph.device)
+            pe = torch.empty(n_paths.value, dtype=torch.int32, device=graph.device)
+            seg_len = torch.empty(n_segs.value, dtype=torch.int32, device=graph.device)
+            _check(L.flatgfa_dev_inject_fill(job, ptr(steps), ptr(pb), ptr(pe), ptr(seg_len), ctypes.c_void_p(st.cuda_stream)),
+                   "dev_inject_fill")
+        finally:
+            L.flatgfa_dev_inject_free(job)  # (waits for the fill)
+        return DeviceGraph.from_tensors(steps, pb, pe, n_segs.value, seg_len), seg_first
+
+
 def profile_enable(on: bool) -> None:
     _lib.lib().flatgfa_dev_profile_enable(1 if on else 0)
 

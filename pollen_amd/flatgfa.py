@@ -447,6 +447,44 @@ class FlatGFA:
         _check(_lib.lib().flatgfa_chop(self._h, int(max_size), 1 if links else 0, ctypes.byref(h)), "chop")
         return FlatGFA(h.value)
 
+    # ---- inject (slow_odgi/inject.py) ----
+    def inject(self, bed, links: bool = False) -> "FlatGFA":
+        """`fgfa inject -b BED [-l]`: a new graph in which every BED line "path start end new_name" is a path of its own:
+        the segments under the interval's two ends are cut so that both fall on seams, and the new path walks exactly the
+        interval (slow_odgi/inject.py, `odgi inject`), computed on the GPU.  `bed` is the BED text (bytes or str) or a list
+        of (path, start, end, new_name) with path a name or a path id.  A line of BED text whose path the graph lacks is
+        skipped; in a list it is a KeyError.  The result owns its pools and outlives this graph."""
+        h = ctypes.c_void_p()
+        L = _lib.lib()
+        if isinstance(bed, str):
+            bed = bed.encode()
+        if isinstance(bed, (bytes, bytearray, memoryview)):
+            text = bytes(bed)
+            _check(L.flatgfa_inject_bed(self._h, text, len(text), 1 if links else 0, ctypes.byref(h)), "inject")
+            return FlatGFA(h.value)
+        lines = list(bed)
+        n = len(lines)
+        ids = np.empty(n, np.uint32)
+        lo = np.empty(n, np.uint64)
+        hi = np.empty(n, np.uint64)
+        names = []
+        for k, (path, start, end, new) in enumerate(lines):
+            if isinstance(path, (int, np.integer)):
+                ids[k] = int(path)
+            else:
+                raw = path.encode() if isinstance(path, str) else bytes(path)
+                p = L.flatgfa_find_path(self._h, raw, len(raw))
+                if p < 0:
+                    raise KeyError(f"path not found: {path!r}")
+                ids[k] = p
+            lo[k], hi[k] = int(start), int(end)
+            names.append(new.encode() if isinstance(new, str) else bytes(new))
+        c_names = (ctypes.c_char_p * max(n, 1))(*names)
+        c_lens = (ctypes.c_size_t * max(n, 1))(*[len(x) for x in names])
+        _check(L.flatgfa_inject(self._h, ids.ctypes.data, lo.ctypes.data, hi.ctypes.data, c_names, c_lens, n, 1 if links else 0,
+                                ctypes.byref(h)), "inject")
+        return FlatGFA(h.value)
+
     # ---- extract (ops/extract.rs) and position (ops/position.rs) ----
     def find_seg(self, name: int) -> Optional[int]:
         """The id of the first segment called `name` (FlatGFA::find_seg), or None."""
