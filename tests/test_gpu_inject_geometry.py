@@ -42,7 +42,8 @@ def check(im: sh.Image, stream=None):
     return want
 
 
-@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 1023, 1024, 1025, (1 << 20) + 5])
+# (511 and 512 lines: the distinct scan over M + 1 = 2 n + 1 elements ends one short of a scan tile and begins the next)
+@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 511, 512, 1023, 1024, 1025, (1 << 20) + 5])
 def test_line_counts(n):
     check(sh.line_counts(n))
 
@@ -65,9 +66,31 @@ def test_long_segment_cut_in_the_middle():
     assert want.seg_len.tolist() == [1 << 31, (1 << 31) - 1, 1, 3, 1]
 
 
-@pytest.mark.parametrize("S", [255, 256, 257, 4095, 4096, 4097])
+# (1023 .. 1025: the row scan over S + 1 elements on its tile seam; 524288 and 524289: k_sort_short's second grid-stride round)
+@pytest.mark.parametrize("S", [255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, sh.MAX_GRID * 256, sh.MAX_GRID * 256 + 1])
 def test_many_segments(S):
     check(sh.many_segments(S))
+
+
+@pytest.mark.parametrize("R", [sh.MAX_GRID, sh.MAX_GRID + 1, 2 * sh.MAX_GRID + 1])
+def test_long_rows_past_one_round_of_workgroups(R):
+    # row 2048 is the first of k_sort_long's second round, row 4096 the first of its third
+    want = check(sh.long_rows(R))
+    assert len(want.seg_len) == 18 * R
+
+
+def test_row_lengths_around_powers_of_two():
+    check(sh.row_lengths())
+
+
+@pytest.mark.parametrize("N", [sh.SCAN_TILE - 2, sh.SCAN_TILE - 1, sh.SCAN_TILE])
+def test_pool_steps_at_the_scan_tile(N):
+    # pre[N] and noff[N], one past the steps, as the last element of a scan tile and as the first of the next
+    check(sh.pool_steps(N))
+
+
+def test_many_paths_take_the_per_path_route_twice_round():
+    check(sh.many_paths_non_tiling())
 
 
 @pytest.mark.parametrize("total", [sh.OUT_TILE * 3 - 1, sh.OUT_TILE * 3, sh.OUT_TILE * 3 + 1])

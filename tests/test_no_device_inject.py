@@ -77,6 +77,36 @@ def test_refusals_and_parse_errors_need_no_device(what):
         g.close()
 
 
+def test_a_repeated_name_behind_65536_lines_is_named_by_its_line_in_the_text():
+    # more lines than 16 bits count, comments and empty lines among them: the refusal counts lines as the text has them
+    rows, names = [], 0
+    for i in range(66000):
+        if i % 1000 == 7:
+            rows.append(b"# a comment")
+        elif i % 777 == 5:
+            rows.append(b"")
+        elif i % 501 == 3:
+            rows.append(b"nope\t1\t2\tskipped%d" % i)
+        else:
+            rows.append(b"%s\t1\t5\tx%d" % (b"pq"[i % 2:i % 2 + 1], names))
+            names += 1
+    rows.append(b"q\t0\t3\tx40000")
+    assert names > 65536 and len(rows) == 66001
+    g = pa.parse_bytes(TEXT)
+    try:
+        with pytest.raises(pa.FlatGFAError) as e:
+            g.inject(b"\n".join(rows) + b"\n")
+        assert e.value.code == -1
+        assert _lib.last_error() == "inject: line 66001: the new name was given by an earlier line"
+        # and the same lines as a list, which has no text to count in: the line's index, from 1
+        lines = [(f[0].decode(), int(f[1]), int(f[2]), f[3]) for f in (r.split(b"\t") for r in rows) if len(f) == 4 and f[0] != b"nope"]
+        with pytest.raises(pa.FlatGFAError) as e:
+            g.inject(lines)
+        assert e.value.code == -1 and _lib.last_error() == "inject: line %d: the new name was given by an earlier line" % len(lines)
+    finally:
+        g.close()
+
+
 def test_list_refusals_and_argument_errors_need_no_device():
     lib = _lib.lib()
     g = pa.parse_bytes(TEXT)
