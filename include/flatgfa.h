@@ -281,6 +281,18 @@ int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out);
 int flatgfa_inject(flatgfa_t gfa, const uint32_t *path_ids, const uint64_t *starts, const uint64_t *ends, const char *const *names,
                    const size_t *name_lens, uint64_t n, int links, flatgfa_t *out);
 int flatgfa_inject_bed(flatgfa_t gfa, const char *bed, size_t bed_len, int links, flatgfa_t *out);
+/* crush (slow_odgi/crush.py, `odgi crush`; `fgfa crush`): within each segment's sequence every maximal run of the byte 'N'
+ * (0x4E, and no other: 'n' and '*' are ordinary bytes) becomes a single N; runs never join across segments.  *out is a new
+ * heap handle that owns its pools and outlives `gfa`: seq_data is the crushed segments one behind another in segment order,
+ * whatever the input spans were (they may be out of order, overlap, alias or be empty), and every segment's span points into
+ * it -- an empty segment's at the place where the next segment begins; segments keep their names and lose their optional
+ * fields, paths keep their names and steps and lose their overlaps; header, steps, links, alignment and name_data are copies
+ * of the input's; overlaps, optional_data and line_order are empty (the text comes out in normalized order).  The steps are
+ * neither read nor checked.  The count, the scans and the compaction run on the GPU (the device `gfa` is resident on, else
+ * device 0), on the sequence pool the handle keeps there when it has one, else on a copy made for the call; `gfa` is only
+ * read.  A segment span that leaves seq_data: FLATGFA_ERR_BOUNDS, before any device work; more than 2^32 - 1 kept bytes:
+ * FLATGFA_ERR_TOO_LARGE, found before any output is allocated. */
+int flatgfa_crush(flatgfa_t gfa, flatgfa_t *out);
 /* extract (flatgfa/src/ops/extract.rs; `fgfa extract -n NAME -c DIST [-d N] [-e N]`, cli/cmds.rs:174-215): the subgraph
  * around one segment.  flatgfa_find_seg is FlatGFA::find_seg (flatgfa.rs:380-384): the id of the first segment with that
  * name, or -1.  The new graph holds the old header; the origin as segment 0 and every segment within link_distance links
@@ -605,6 +617,22 @@ int flatgfa_dev_inject_count(const flatgfa_dev_graph_t *g, const uint32_t *d_pat
 int flatgfa_dev_inject_fill(flatgfa_dev_inject_t *job, uint32_t *steps, uint32_t *path_begin, uint32_t *path_end, uint32_t *seg_len,
                             void *stream);
 void flatgfa_dev_inject_free(flatgfa_dev_inject_t *job);
+/* crush (flatgfa_crush) of a sequence pool in device memory, in two stream-ordered calls modelled on the chop pair.  seg_seq
+ * u32[2 * n_segs] holds each segment's start in seq_data and its length, as the GAF lookup keeps them; seq_data u8[seq_len].
+ * n_segs == 0 and seq_len == 0 are valid (the pointers may then be NULL).  flatgfa_dev_crush_count checks the spans, counts
+ * what is kept, waits for `stream` once to read the totals -- *bytes_out kept bytes, *dropped_out dropped ones -- and, when
+ * the kept bytes fit a 32-bit span, enqueues seg_len_out u32[n_segs] (the new lengths: put in place of a
+ * flatgfa_dev_graph_t's seg_len they give the crushed graph's image, the steps and path spans shared) and returns a job in
+ * *job; a span that leaves seq_data: FLATGFA_ERR_BOUNDS, more than 2^32 - 1 kept bytes: FLATGFA_ERR_TOO_LARGE, both with no
+ * job and nothing written.  flatgfa_dev_crush_fill enqueues on `stream` the new pool into seq_out u8[*bytes_out] (at any
+ * alignment) and the new spans into seg_seq_out u32[2 * n_segs] (start, length; segment s starts at the sum of the new
+ * lengths before s, empty or not), and does not wait.  seg_seq and seq_data must stay as they are until the fill is done.
+ * flatgfa_dev_crush_free waits for the job's stream and releases its scratch. */
+typedef struct flatgfa_dev_crush flatgfa_dev_crush_t;
+int flatgfa_dev_crush_count(const uint32_t *seg_seq, const uint8_t *seq_data, uint64_t seq_len, uint32_t n_segs, uint32_t *seg_len_out,
+                            void *stream, flatgfa_dev_crush_t **job, uint64_t *bytes_out, uint64_t *dropped_out);
+int flatgfa_dev_crush_fill(flatgfa_dev_crush_t *job, uint8_t *seq_out, uint32_t *seg_seq_out, void *stream);
+void flatgfa_dev_crush_free(flatgfa_dev_crush_t *job);
 /* The legend of flatten (flatten.py:13-19; flatgfa_flatten_legend) of a graph image in device memory: d_offset_out[s] = the
  * sum of g->seg_len before s, d_offset_out[n_segs] = the sum of all, in 64 bits (g->seg_len is required: FLATGFA_ERR_ARG when
  * NULL; the steps and spans are not read).  Enqueued on `stream`, which is waited for: the scan's scratch goes before the

@@ -84,6 +84,7 @@ SIGNATURES = {
     "flatgfa_inject": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_char_p), POINTER(c_size_t), c_uint64, c_int,
                                POINTER(c_void_p)]),
     "flatgfa_inject_bed": (c_int, [c_void_p, c_char_p, c_size_t, c_int, POINTER(c_void_p)]),
+    "flatgfa_crush": (c_int, [c_void_p, POINTER(c_void_p)]),
     "flatgfa_find_seg": (c_int64, [c_void_p, c_uint64]),
     "flatgfa_extract": (c_int, [c_void_p, c_uint32, c_uint64, c_uint64, c_uint64, POINTER(c_void_p)]),
     "flatgfa_position": (c_int, [c_void_p, c_uint32, c_uint64, POINTER(c_uint32), POINTER(c_uint64), POINTER(c_int)]),
@@ -140,6 +141,10 @@ SIGNATURES = {
                                          POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     "flatgfa_dev_inject_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "flatgfa_dev_inject_free": (None, [c_void_p]),
+    "flatgfa_dev_crush_count": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, POINTER(c_void_p),
+                                        POINTER(c_uint64), POINTER(c_uint64)]),
+    "flatgfa_dev_crush_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "flatgfa_dev_crush_free": (None, [c_void_p]),
     "flatgfa_dev_flatten_legend": (c_int, [POINTER(flatgfa_dev_graph_t), c_void_p, c_void_p]),
     "flatgfa_dev_status": (c_int, [c_void_p, c_void_p]),
     "flatgfa_dev_profile_enable": (None, [c_int]),

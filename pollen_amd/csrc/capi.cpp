@@ -1,7 +1,7 @@
 // extern "C" surface of libflatgfa.so: the flatgfa-c drop-in (Part 1 of include/flatgfa.h)
 // plus the additive loaders, the depth queries and the host routes of the other features (Part 2).  The kernels live in the
 // .hip files -- depth_device.hip and its kin for depth, gaf_device.hip, gaf_lookup_device.hip, chop_device.hip,
-// extract_device.hip, topology_device.hip, flatten_device.hip for the rest -- and are reached through their headers; this file uses the HIP runtime
+// extract_device.hip, topology_device.hip, flatten_device.hip, crush_device.hip for the rest -- and are reached through their headers; this file uses the HIP runtime
 // API only.  Every host route that is not a depth query holds what it has on the device in one DevScope (below).
 #include <hip/hip_runtime_api.h>
 
@@ -38,6 +38,7 @@
 #include "topology_device.hpp"
 #include "interval_device.hpp"
 #include "flatten_device.hpp"
+#include "crush_device.hpp"
 
 using fgfa_dev::set_error;
 
@@ -165,7 +166,7 @@ int count_devices(const std::string &who, int *ndev) {
     return FLATGFA_OK;
 }
 
-// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree, flatten -- holds on the device,
+// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree, flatten, crush -- holds on the device,
 // given back on every way out: the work stream is waited for, then the job, the events and the memory go, then the streams
 // return to the pool.  A thread that still copies on one of the streams is joined first: its joiner is declared after the scope.
 struct DevScope {
@@ -1853,6 +1854,74 @@ int flatgfa_inject_bed(flatgfa_t gfa, const char *bed, size_t bed_len, int links
     }
     if (int rc = inject_check_names(by_name, names.data(), name_lens.data(), ids.size(), line_no.data())) return rc;
     return inject_locked(gfa, ids.data(), lo.data(), hi.data(), names.data(), name_lens.data(), ids.size(), links, out);
+}
+
+// ---- crush (slow_odgi/crush.py) ----
+
+int flatgfa_crush(flatgfa_t gfa, flatgfa_t *out) {
+    if (out) *out = nullptr;
+    if (!gfa || !out) { set_error("flatgfa_crush: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    const fgfa::View &v = gfa->view;
+    const size_t S = v.segs.len, n_seq = v.seq_data.len;
+    if (S > 0x80000000ull) { set_error("flatgfa_crush: graph too large for 32-bit ids"); return FLATGFA_ERR_TOO_LARGE; }
+    // (before any device work: the kernels check the spans again, as the device-level entry needs them to)
+    std::vector<uint32_t> seg_seq(2 * S);
+    for (size_t i = 0; i < S; ++i) {
+        const fgfa::Span sp = v.segs[i].seq;
+        if (sp.start > sp.end || sp.end > n_seq) {
+            set_error("crush: segment " + std::to_string(i) + " has a sequence span outside seq_data");
+            return FLATGFA_ERR_BOUNDS;
+        }
+        seg_seq[2 * i] = sp.start;
+        seg_seq[2 * i + 1] = sp.end - sp.start;
+    }
+    DevScope sc;
+    if (int rc = open_scope(gfa, &sc, "crush")) return rc;
+    hipStream_t st = sc.stream;
+    fgfa_dev::CrushIn in;
+    in.seq_len = n_seq;
+    in.n_segs = (uint32_t)S;
+    if (gfa->gaf_seq_device == sc.device) {  // the pool the handle keeps on this device, read in place
+        in.seg_seq = gfa->d_gaf_seg_seq;
+        in.seq_data = gfa->d_gaf_seq_data;
+    } else {
+        uint32_t *d_seg_seq = nullptr;
+        uint8_t *d_seq = nullptr;
+        CAPI_HIP(sc.upload(&d_seg_seq, seg_seq.data(), 2 * S));
+        CAPI_HIP(sc.upload(&d_seq, v.seq_data.data, n_seq));
+        in.seg_seq = d_seg_seq;
+        in.seq_data = d_seq;
+    }
+    uint32_t *d_out = nullptr;  // the new lengths, then the new spans
+    CAPI_HIP(sc.alloc(&d_out, 3 * S));
+    fgfa_dev::CrushJob *job = sc.hold<fgfa_dev::CrushJob, fgfa_dev::crush_free>(fgfa_dev::crush_new());
+    uint64_t kept = 0, dropped = 0;
+    if (int rc = fgfa_dev::crush_count(job, in, d_out, st, &kept, &dropped)) return rc;
+    // the new pool, now that its size is known to fit
+    uint8_t *d_seq_out = nullptr;
+    CAPI_HIP(sc.alloc(&d_seq_out, kept));
+    if (int rc = fgfa_dev::crush_fill(job, d_seq_out, d_out + S, st)) return rc;
+    auto cs = std::make_unique<CStore>();
+    fgfa::Store &h = cs->heap;
+    // (the host pools are made beside the kernels)
+    h.header.assign(v.header.begin(), v.header.end());
+    h.name_data.assign(v.name_data.begin(), v.name_data.end());
+    h.steps.assign(v.steps.begin(), v.steps.end());
+    h.links.assign(v.links.begin(), v.links.end());
+    h.alignment.resize(v.alignment.len);
+    if (v.alignment.len) memcpy(h.alignment.data(), v.alignment.data, v.alignment.len * 4);
+    h.seq_data.resize(kept);
+    std::vector<uint32_t> spans(2 * S);
+    CAPI_HIP(fgfa_dev::staged_copy(spans.data(), d_out + S, 2 * S * 4, hipMemcpyDeviceToHost, st));
+    CAPI_HIP(fgfa_dev::staged_copy(h.seq_data.data(), d_seq_out, kept, hipMemcpyDeviceToHost, st));
+    h.segs.resize(S);
+    for (size_t i = 0; i < S; ++i) h.segs[i] = fgfa::Segment{v.segs[i].name, fgfa::Span{spans[2 * i], spans[2 * i] + spans[2 * i + 1]}, fgfa::Span{0, 0}};
+    h.paths.resize(v.paths.len);
+    for (size_t i = 0; i < v.paths.len; ++i) h.paths[i] = fgfa::Path{v.paths[i].name, v.paths[i].steps, fgfa::Span{0, 0}};  // crush.py:27
+    cs->view = h.view();
+    *out = cs.release();
+    return FLATGFA_OK;
 }
 
 // ---- extract (ops/extract.rs) and position (ops/position.rs) ----

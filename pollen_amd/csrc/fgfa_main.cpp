@@ -3,7 +3,7 @@
 //
 //   fgfa [-i FILE.flatgfa | -I FILE.gfa] [-o OUT.flatgfa] [-O OUT.gfa] [COMMAND]
 //   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [--bed-paths FILE.bed] [-s PATHS]
-//            | window-depth PATH SIZE | window-depth-all SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l] | inject -b BED [-l]
+//            | window-depth PATH SIZE | window-depth-all SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l] | inject -b BED [-l] | crush
 //            | extract -n NAME -c DIST [-d N] [-e N] | position -p PATH,OFFSET,+ | validate | degree
 //            | flatten [-n NAME] [-f FASTA] [-b BED]
 //
@@ -11,7 +11,7 @@
 // (-o binary, -O text, otherwise text on stdout).  `depth` output is byte-identical to the
 // reference's and is computed on the GPU, as are `matrix` (cmds.rs:453-475), `position` (cmds.rs:105-152), and `chop`
 // (cli/main.rs:139-159) and `extract` (cmds.rs:174-215), whose graph is written out as the input graph would be; `validate` and `degree` print what slow_odgi's validate.py and
-// degree.py print, `flatten` what its flatten.py prints (or, with -f / -b, what `odgi flatten` writes to those files).  Everything else in the reference CLI is out of scope.
+// degree.py print, `crush` writes out the graph of its crush.py, `flatten` what its flatten.py prints (or, with -f / -b, what `odgi flatten` writes to those files).  Everything else in the reference CLI is out of scope.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -121,7 +121,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten";
+    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "crush" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -236,6 +236,16 @@ int main(int argc, char **argv) {
         flatgfa_t injected = nullptr;
         if (flatgfa_inject_bed(g, bed.data(), bed.size(), links ? 1 : 0, &injected)) rc = die("inject");
         else rc = dump(injected);
+    } else if (cmd == "crush") {
+        // slow_odgi crush (`odgi crush`): every run of N in a segment becomes one N; the graph is written out as chop's is
+        if (i != argc) {
+            fprintf(stderr, "usage: fgfa crush\n");
+            flatgfa_free(g);
+            return 2;
+        }
+        flatgfa_t crushed = nullptr;
+        if (flatgfa_crush(g, &crushed)) rc = die("crush");
+        else rc = dump(crushed);
     } else if (cmd == "extract") {
         // cli/cmds.rs:174-215: fgfa extract -n NAME -c DIST [-d N] [-e N]
         uint64_t name = 0, dist = 0, max_dist = 300000, iters = 6;

@@ -389,6 +389,40 @@ def inject(graph: DeviceGraph, path_ids, starts, ends, stream=None) -> Tuple[Dev
         return DeviceGraph.from_tensors(steps, pb, pe, n_segs.value, seg_len), seg_first
 
 
+def crush(graph: DeviceGraph, seg_seq, seq_data, stream=None):
+    """crush (slow_odgi/crush.py) of a resident graph image and its sequence pool, on the device: seg_seq is int32[2 * n_segs]
+    (each segment's start in seq_data and its length, as the GAF lookup keeps them), seq_data the pool (uint8), both CUDA
+    tensors.  Returns (the crushed image, seq_out, seg_seq_out): a DeviceGraph that shares graph's step and span tensors and
+    has the new lengths as seg_len (a valid input to DepthPlan), the new pool (uint8: the crushed segments in segment order)
+    and the new spans (int32[2 * n_segs]).  Waits for the stream once, to learn the sizes (flatgfa_dev_crush_count); the rest
+    is enqueued on it (torch's current stream by default)."""
+    torch = _torch()
+    S = graph.n_segs
+    assert seg_seq.dtype == torch.int32 and seg_seq.is_cuda and seg_seq.is_contiguous() and seg_seq.numel() == 2 * S
+    assert seq_data.dtype == torch.uint8 and seq_data.is_cuda and seq_data.is_contiguous()
+    with torch.cuda.device(graph.device):
+        st = stream if stream is not None else torch.cuda.current_stream(graph.device)
+        seg_len = torch.empty(S, dtype=torch.int32, device=graph.device)
+        job = ctypes.c_void_p()
+        kept, dropped = ctypes.c_uint64(), ctypes.c_uint64()
+        L = _lib.lib()
+
+        def ptr(t):
+            return t.data_ptr() if t.numel() else None
+        with torch.cuda.stream(st):  # (the outputs are the stream's: torch's allocator may hand their memory on behind it)
+            _check(L.flatgfa_dev_crush_count(ptr(seg_seq), ptr(seq_data), int(seq_data.numel()), S, ptr(seg_len),
+                                             ctypes.c_void_p(st.cuda_stream), ctypes.byref(job), ctypes.byref(kept), ctypes.byref(dropped)),
+                   "dev_crush_count")
+            try:
+                seq_out = torch.empty(kept.value, dtype=torch.uint8, device=graph.device)
+                seg_seq_out = torch.empty(2 * S, dtype=torch.int32, device=graph.device)
+                _check(L.flatgfa_dev_crush_fill(job, ptr(seq_out), ptr(seg_seq_out), ctypes.c_void_p(st.cuda_stream)), "dev_crush_fill")
+            finally:
+                L.flatgfa_dev_crush_free(job)  # (waits for the fill, on this stream only)
+        new = DeviceGraph.from_tensors(graph.steps, graph.path_begin, graph.path_end, S, seg_len, graph.h_path_begin, graph.h_path_end)
+        return new, seq_out, seg_seq_out
+
+
 def profile_enable(on: bool) -> None:
     _lib.lib().flatgfa_dev_profile_enable(1 if on else 0)
 

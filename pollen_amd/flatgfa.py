@@ -447,6 +447,15 @@ class FlatGFA:
         _check(_lib.lib().flatgfa_chop(self._h, int(max_size), 1 if links else 0, ctypes.byref(h)), "chop")
         return FlatGFA(h.value)
 
+    # ---- crush (slow_odgi/crush.py) ----
+    def crush(self) -> "FlatGFA":
+        """`fgfa crush`: a new graph in which every run of N inside a segment's sequence is a single N (slow_odgi/crush.py,
+        `odgi crush`), computed on the GPU.  Segments lose their optional fields and paths their overlaps; the sequence pool
+        is laid out again in segment order.  The result owns its pools and outlives this graph."""
+        h = ctypes.c_void_p()
+        _check(_lib.lib().flatgfa_crush(self._h, ctypes.byref(h)), "crush")
+        return FlatGFA(h.value)
+
     # ---- inject (slow_odgi/inject.py) ----
     def inject(self, bed, links: bool = False) -> "FlatGFA":
         """`fgfa inject -b BED [-l]`: a new graph in which every BED line "path start end new_name" is a path of its own:
