@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
@@ -1599,7 +1600,6 @@ static int upload_chop_input(CStore *gfa, DevScope &sc, bool links, fgfa_dev::Ch
     const size_t N = v.steps.len, P = v.paths.len, S = v.segs.len, L = links ? v.links.len : 0;
     const bool resident = sc.resident;  // (its image is read in place)
     // (an array of no elements stays NULL below, which chop_fill reads as "not wanted": sc.alloc would make it one element long)
-    // what chop reads: the steps, spans and lengths (the resident image's, when there is one), the seq starts, the links
     const size_t Pa = (P + 63) & ~(size_t)63, Sa = (S + 63) & ~(size_t)63;
     std::vector<uint32_t> host((resident ? 0 : 2 * Pa + Sa) + Sa + 1);
     uint32_t *h_start = host.data();
@@ -1644,28 +1644,20 @@ static int upload_chop_input(CStore *gfa, DevScope &sc, bool links, fgfa_dev::Ch
     return FLATGFA_OK;
 }
 
-int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
-    if (out) *out = nullptr;
-    if (!gfa || !out) { set_error("flatgfa_chop: NULL argument"); return FLATGFA_ERR_ARG; }
-    if (max_size == 0) { set_error("flatgfa_chop: the maximum segment size must be at least 1"); return FLATGFA_ERR_ARG; }
-    std::lock_guard<std::mutex> op(gfa->op_mu);
+// the pools that chop and inject number in u32 (`links`: whether the links are read at all)
+static bool chop_input_too_large(const fgfa::View &v, bool links) {
+    return v.steps.len > 0xFFFFFFFFull || v.segs.len > 0x80000000ull || v.paths.len > 0xFFFFFFFFull || (links && v.links.len > 0xFFFFFFFFull);
+}
+
+// What chop and inject do once the count has the sizes (S2 segments, N2 steps, L2 links, P2 >= P paths): the image is
+// allocated on the device, filled (the feature's fill on the scope's stream) and downloaded into a new CStore: the header,
+// seq_data and name_data (with room for name_bytes) copied, the old P path records made from the new spans.  *spans_out holds
+// the P2 spans, begins in its first half and ends in its second, for the paths the caller adds behind the old ones.
+static int download_expanded(CStore *gfa, DevScope &sc, const std::function<int(const fgfa_dev::ChopOut &)> &fill, size_t P2, uint64_t S2, uint64_t N2,
+                             uint64_t L2, size_t name_bytes, std::unique_ptr<CStore> *cs_out, std::vector<uint32_t> *spans_out) {
     const fgfa::View &v = gfa->view;
-    const size_t N = v.steps.len, P = v.paths.len, S = v.segs.len, L = links ? v.links.len : 0;
-    if (N > 0xFFFFFFFFull || S > 0x80000000ull || P > 0xFFFFFFFFull || L > 0xFFFFFFFFull) {
-        set_error("flatgfa_chop: graph too large for 32-bit ids");
-        return FLATGFA_ERR_TOO_LARGE;
-    }
-    DevScope sc;
-    if (int rc = open_scope(gfa, &sc, "chop")) return rc;
+    const size_t P = v.paths.len, Pa = (P2 + 63) & ~(size_t)63;
     hipStream_t st = sc.stream;
-    fgfa_dev::ChopIn in;
-    uint32_t *d_seg_first = nullptr;
-    if (int rc = upload_chop_input(gfa, sc, links != 0, &in, &d_seg_first)) return rc;
-    const size_t Pa = (P + 63) & ~(size_t)63;
-    fgfa_dev::ChopJob *job = sc.hold<fgfa_dev::ChopJob, fgfa_dev::chop_free>(fgfa_dev::chop_new());
-    uint64_t S2 = 0, N2 = 0, L2 = 0;
-    int rc = fgfa_dev::chop_count(job, in, max_size, links != 0, d_seg_first, st, &S2, &N2, &L2);
-    if (rc) return rc;
     // the outputs, now that their sizes are known to fit
     fgfa_dev::ChopOut o;
     if (N2) CAPI_HIP(sc.alloc(&o.steps, N2));
@@ -1673,8 +1665,7 @@ int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
     o.path_end = o.path_begin ? o.path_begin + Pa : nullptr;
     if (S2) CAPI_HIP(sc.alloc(&o.seg_recs, S2 * 6));
     if (L2) CAPI_HIP(sc.alloc(&o.links, L2 * 4));
-    rc = fgfa_dev::chop_fill(job, o, st);
-    if (rc) return rc;
+    if (int rc = fill(o)) return rc;
     auto cs = std::make_unique<CStore>();
     fgfa::Store &h = cs->heap;
     // (the host pools are allocated beside the kernels; the largest, the steps, on a thread of its own)
@@ -1682,18 +1673,43 @@ int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
     Joiner joiner{alloc};
     h.header.assign(v.header.begin(), v.header.end());
     h.seq_data.assign(v.seq_data.begin(), v.seq_data.end());
+    h.name_data.reserve(name_bytes);
     h.name_data.assign(v.name_data.begin(), v.name_data.end());
     h.segs.resize(S2);
     h.links.resize(L2);
-    std::vector<uint32_t> spans(2 * Pa);
+    std::vector<uint32_t> &spans = *spans_out;
+    spans.resize(2 * Pa);
     CAPI_HIP(fgfa_dev::staged_copy(h.segs.data(), o.seg_recs, S2 * 24, hipMemcpyDeviceToHost, st));
     CAPI_HIP(fgfa_dev::staged_copy(h.links.data(), o.links, L2 * 16, hipMemcpyDeviceToHost, st));
     CAPI_HIP(fgfa_dev::staged_copy(spans.data(), o.path_begin, 2 * Pa * 4, hipMemcpyDeviceToHost, st));
     alloc.join();
     CAPI_HIP(fgfa_dev::staged_copy(h.steps.data(), o.steps, N2 * 4, hipMemcpyDeviceToHost, st));
-    h.paths.resize(P);
-    for (size_t i = 0; i < P; ++i) h.paths[i] = fgfa::Path{v.paths[i].name, fgfa::Span{spans[i], spans[Pa + i]}, fgfa::Span{0, 0}};  // chop.rs:104
-    cs->view = h.view();
+    h.paths.resize(P2);
+    for (size_t i = 0; i < P; ++i) h.paths[i] = fgfa::Path{v.paths[i].name, fgfa::Span{spans[i], spans[Pa + i]}, fgfa::Span{0, 0}};  // chop.rs:104, chop.py:56
+    *cs_out = std::move(cs);
+    return FLATGFA_OK;
+}
+
+int flatgfa_chop(flatgfa_t gfa, uint64_t max_size, int links, flatgfa_t *out) {
+    if (out) *out = nullptr;
+    if (!gfa || !out) { set_error("flatgfa_chop: NULL argument"); return FLATGFA_ERR_ARG; }
+    if (max_size == 0) { set_error("flatgfa_chop: the maximum segment size must be at least 1"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    const fgfa::View &v = gfa->view;
+    if (chop_input_too_large(v, links != 0)) { set_error("flatgfa_chop: graph too large for 32-bit ids"); return FLATGFA_ERR_TOO_LARGE; }
+    DevScope sc;
+    if (int rc = open_scope(gfa, &sc, "chop")) return rc;
+    fgfa_dev::ChopIn in;
+    uint32_t *d_seg_first = nullptr;
+    if (int rc = upload_chop_input(gfa, sc, links != 0, &in, &d_seg_first)) return rc;
+    fgfa_dev::ChopJob *job = sc.hold<fgfa_dev::ChopJob, fgfa_dev::chop_free>(fgfa_dev::chop_new());
+    uint64_t S2 = 0, N2 = 0, L2 = 0;
+    if (int rc = fgfa_dev::chop_count(job, in, max_size, links != 0, d_seg_first, sc.stream, &S2, &N2, &L2)) return rc;
+    std::unique_ptr<CStore> cs;
+    std::vector<uint32_t> spans;
+    const auto fill = [&](const fgfa_dev::ChopOut &o) { return fgfa_dev::chop_fill(job, o, sc.stream); };
+    if (int rc = download_expanded(gfa, sc, fill, v.paths.len, S2, N2, L2, v.name_data.len, &cs, &spans)) return rc;
+    cs->view = cs->heap.view();
     *out = cs.release();
     return FLATGFA_OK;
 }
@@ -1735,16 +1751,15 @@ void path_names(const fgfa::View &v, std::unordered_map<std::string, uint32_t> *
 int inject_locked(CStore *gfa, const uint32_t *path_ids, const uint64_t *starts, const uint64_t *ends, const char *const *names,
                   const size_t *name_lens, uint64_t n, int links, flatgfa_t *out) {
     const fgfa::View &v = gfa->view;
-    const size_t N = v.steps.len, P = v.paths.len, S = v.segs.len, L = links ? v.links.len : 0;
+    const size_t P = v.paths.len;
     size_t name_bytes = v.name_data.len;
     for (uint64_t l = 0; l < n; ++l) name_bytes += name_lens[l];
-    if (N > 0xFFFFFFFFull || S > 0x80000000ull || P + n > 0xFFFFFFFFull || n >= 0x7FFFFFFFull || L > 0xFFFFFFFFull || name_bytes > 0xFFFFFFFFull) {
+    if (chop_input_too_large(v, links != 0) || P + n > 0xFFFFFFFFull || n >= 0x7FFFFFFFull || name_bytes > 0xFFFFFFFFull) {
         set_error("flatgfa_inject: graph too large for 32-bit ids");
         return FLATGFA_ERR_TOO_LARGE;
     }
     DevScope sc;
     if (int rc = open_scope(gfa, &sc, "inject")) return rc;
-    hipStream_t st = sc.stream;
     fgfa_dev::ChopIn in;
     uint32_t *d_seg_first = nullptr;
     if (int rc = upload_chop_input(gfa, sc, links != 0, &in, &d_seg_first)) return rc;
@@ -1762,36 +1777,13 @@ int inject_locked(CStore *gfa, const uint32_t *path_ids, const uint64_t *starts,
     }
     fgfa_dev::InjectJob *job = sc.hold<fgfa_dev::InjectJob, fgfa_dev::inject_free>(fgfa_dev::inject_new());
     uint64_t S2 = 0, N2 = 0, L2 = 0;
-    int rc = fgfa_dev::inject_count(job, in, ln, links != 0, d_seg_first, st, &S2, &N2, &L2);
-    if (rc) return rc;
-    // the outputs, now that their sizes are known to fit
-    const size_t P2 = P + n, Pa = (P2 + 63) & ~(size_t)63;
-    fgfa_dev::ChopOut o;
-    if (N2) CAPI_HIP(sc.alloc(&o.steps, N2));
-    if (Pa) CAPI_HIP(sc.alloc(&o.path_begin, 2 * Pa));
-    o.path_end = o.path_begin ? o.path_begin + Pa : nullptr;
-    if (S2) CAPI_HIP(sc.alloc(&o.seg_recs, S2 * 6));
-    if (L2) CAPI_HIP(sc.alloc(&o.links, L2 * 4));
-    rc = fgfa_dev::inject_fill(job, o, st);
-    if (rc) return rc;
-    auto cs = std::make_unique<CStore>();
+    if (int rc = fgfa_dev::inject_count(job, in, ln, links != 0, d_seg_first, sc.stream, &S2, &N2, &L2)) return rc;
+    std::unique_ptr<CStore> cs;
+    std::vector<uint32_t> spans;
+    const auto fill = [&](const fgfa_dev::ChopOut &o) { return fgfa_dev::inject_fill(job, o, sc.stream); };
+    if (int rc = download_expanded(gfa, sc, fill, P + n, S2, N2, L2, name_bytes, &cs, &spans)) return rc;
     fgfa::Store &h = cs->heap;
-    std::thread alloc([&] { h.steps.resize(N2); });
-    Joiner joiner{alloc};
-    h.header.assign(v.header.begin(), v.header.end());
-    h.seq_data.assign(v.seq_data.begin(), v.seq_data.end());
-    h.name_data.reserve(name_bytes);
-    h.name_data.assign(v.name_data.begin(), v.name_data.end());
-    h.segs.resize(S2);
-    h.links.resize(L2);
-    std::vector<uint32_t> spans(2 * Pa);
-    CAPI_HIP(fgfa_dev::staged_copy(h.segs.data(), o.seg_recs, S2 * 24, hipMemcpyDeviceToHost, st));
-    CAPI_HIP(fgfa_dev::staged_copy(h.links.data(), o.links, L2 * 16, hipMemcpyDeviceToHost, st));
-    CAPI_HIP(fgfa_dev::staged_copy(spans.data(), o.path_begin, 2 * Pa * 4, hipMemcpyDeviceToHost, st));
-    alloc.join();
-    CAPI_HIP(fgfa_dev::staged_copy(h.steps.data(), o.steps, N2 * 4, hipMemcpyDeviceToHost, st));
-    h.paths.resize(P2);
-    for (size_t i = 0; i < P; ++i) h.paths[i] = fgfa::Path{v.paths[i].name, fgfa::Span{spans[i], spans[Pa + i]}, fgfa::Span{0, 0}};  // chop.py:56
+    const size_t Pa = spans.size() / 2;
     for (size_t l = 0; l < n; ++l) {  // inject.py:91-92
         const uint32_t at = (uint32_t)h.name_data.size();
         h.name_data.insert(h.name_data.end(), (const uint8_t *)names[l], (const uint8_t *)names[l] + name_lens[l]);

@@ -33,13 +33,13 @@ struct ChopOut {
 
 // One chop: count() checks the graph, scans the piece counts, waits for the totals (its one host synchronization), checks
 // them and enqueues the write of seg_first; fill() enqueues the rest.  Both return FLATGFA_* codes (flatgfa_last_error).
+// The job is an Expansion (expand_kernels.hpp, the driver chop and inject share) and c; chop_free waits for the last stream
+// the job was used on, then frees its scratch.
 struct ChopJob;
 ChopJob *chop_new();
 void chop_free(ChopJob *j);
 int chop_count(ChopJob *j, const ChopIn &in, uint64_t max_size, bool links, uint32_t *seg_first, hipStream_t stream,
                uint64_t *n_new_segs, uint64_t *n_new_steps, uint64_t *n_new_links);
 int chop_fill(ChopJob *j, const ChopOut &out, hipStream_t stream);
-// The graph the job was counted on.
-const ChopIn &chop_input(const ChopJob *j);
 
 }  // namespace fgfa_dev

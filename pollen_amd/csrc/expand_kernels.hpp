@@ -13,7 +13,15 @@
 //                emits 8 consecutive items, and the tile goes out through LDS in coalesced rows.
 //   k_path_spans a wave per path: the new span [O(begin), O(end)) where O(v) = prefix of v's tile + the pieces of the at most
 //                255 steps before v in it.
-//   k_path_lens, k_expand_paths   the per-path route for spans that do not tile the steps pool in order.
+//   k_path_lens, k_expand_paths   the per-path route for spans that do not tile the steps pool in order (the types allow any
+//                spans, overlapping ones included): k_path_lens sums each path's pieces, k_offsets lays the paths out,
+//                k_expand_paths writes each path with one workgroup (all its lanes on a long step).
+//
+// The host code that drives them is here too, once ("the expansion driver", below the kernels): the Expansion that a job of
+// either feature holds and the functions that check the arguments, lay out the scratch, launch the reduces, read the totals
+// (the host reads them -- new segments, new steps -- checks them against the u32 id space, and only then is anything written)
+// and fill; templated on Pc and on the pair Load / Emit that makes the new segments' records.  A feature's .hip file says
+// what is its own and calls them in order.
 //
 // Everything is in an unnamed namespace: each .hip file that includes this gets its own kernels.
 #pragma once
@@ -21,7 +29,9 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <string>
 
+#include "chop_device.hpp"
 #include "device_common.hpp"
 #include "device_scan.hpp"
 #include "prof.hpp"
@@ -37,7 +47,7 @@ constexpr uint32_t kOutTile = kThreads * kItems;
 constexpr uint32_t kRMax = kOutTile / kTile + 2;  // source tiles that can cover one output tile
 
 // flag word bits
-constexpr uint32_t kNonTiling = 1, kBadSpan = 2, kBadStep = 4, kBadLink = 8;
+constexpr uint32_t kNonTiling = 1, kBadSpan = 2, kBadStep = 4, kBadLink = 8, kBadPath = 16;  // (kBadPath: inject's lines)
 
 // ---- piece counts ----
 template <class Pc>
@@ -436,6 +446,209 @@ void launch_prefix(const ScanBuf &sb, hipStream_t st) {
 void launch_map(const ScanBuf &sb, hipStream_t st) {
     if (!sb.n_out_tiles) return;
     hipLaunchKernelGGL(k_map, dim3((uint32_t)blocks(sb.n_out_tiles, kThreads)), dim3(kThreads), 0, st, sb.prefix, sb.n_tiles, sb.n_out_tiles, sb.map);
+}
+
+// ---- the expansion driver ----
+// What a feature is called in its messages and in the profile (literals: ProfRec keeps the pointers).
+struct ExpandNames {
+    const char *prefix, *noun;  // "chop: ", "chopped graph"
+    const char *reduce_segs, *reduce_steps, *reduce_paths, *expand_steps, *expand_paths, *expand_segs;
+};
+
+// One count-and-fill job over a graph: what chop and inject both hold.  A feature's count calls expand_check_args,
+// expand_begin, expand_check_graph, expand_reduce<Pc> and expand_totals<Pc> in this order, and its fill calls
+// expand_fill<Load, Emit>, with the launches of its own between them (inject: the cut table before the reduces, the lines'
+// lengths behind them, the new paths behind the fill).  The count waits for its stream once, in expand_totals; nothing else
+// waits.  Kernels never trap: a bad span, step, link or path id raises a bit of the flag word that expand_totals reads.
+struct Expansion {
+    ChopIn in;
+    bool links = false, counted = false, tiling = true;
+    uint32_t *seg_first = nullptr;
+    uint64_t S2 = 0, N_old2 = 0, N_add = 0, L2 = 0;  // new segments, the old paths' new steps, the added paths' steps, new links
+    DeviceMem dm;                                    // (waits for the last stream used, then frees)
+    uint64_t *hdr = nullptr;  // [0] flags, [1] new segments, [2] old paths' new steps (tiling), [3] (per path), [4] the added paths' steps
+    uint64_t *plen = nullptr;
+    uint32_t *maps = nullptr;
+    ScanBuf seg, step, path;
+    uint64_t N2() const { return N_old2 + N_add; }
+};
+
+inline int expand_refuse(const ExpandNames &nm, const char *what, int code) {
+    set_error(std::string(nm.prefix) + what);
+    return code;
+}
+
+// `own_null`: an argument of the feature's own is missing
+int expand_check_args(const ExpandNames &nm, const ChopIn &in, bool links, const uint32_t *seg_first, bool own_null) {
+    if ((in.n_segs && (!in.seg_len || !seg_first)) || (in.n_steps && !in.steps) || (in.n_paths && (!in.path_begin || !in.path_end)) ||
+        (links && in.n_links && !in.links) || own_null)
+        return expand_refuse(nm, "NULL argument", FLATGFA_ERR_ARG);
+    if (in.n_steps > 0xFFFFFFFFull || in.n_segs > 0x80000000u) return expand_refuse(nm, "graph too large for 32-bit ids", FLATGFA_ERR_TOO_LARGE);
+    return FLATGFA_OK;
+}
+
+// One zeroed allocation for the scans' scratch: header, segments, steps, paths, per-path lengths, then `extra_words` of the
+// feature's own, at *extra.
+int expand_begin(Expansion &x, const ExpandNames &nm, const ChopIn &in, bool links, uint32_t *seg_first, hipStream_t st, size_t extra_words = 0,
+                 uint64_t **extra = nullptr) {
+    if (x.counted) return expand_refuse(nm, "this job was counted already", FLATGFA_ERR_ARG);
+    x.in = in;
+    x.links = links;
+    x.seg_first = seg_first;
+    x.dm.st = st;
+    const size_t words = 8 + ScanBuf::words_for(in.n_segs) + ScanBuf::words_for(in.n_steps) + ScanBuf::words_for(in.n_paths) + in.n_paths + extra_words;
+    uint64_t *p = nullptr;
+    FGFA_HIP(nm.prefix, x.dm.alloc(&p, words));
+    FGFA_HIP(nm.prefix, hipMemsetAsync(p, 0, words * 8, st));
+    x.hdr = p;
+    p += 8;
+    x.seg.place(in.n_segs, p);
+    x.step.place(in.n_steps, p);
+    x.path.place(in.n_paths, p);
+    x.plen = p;
+    if (extra) *extra = p + in.n_paths;
+    return FLATGFA_OK;
+}
+
+// the spans and the links
+int expand_check_graph(Expansion &x, const ExpandNames &nm, hipStream_t st) {
+    const ChopIn &in = x.in;
+    uint32_t *flags = reinterpret_cast<uint32_t *>(x.hdr);
+    if (in.n_paths == 0) FGFA_HIP(nm.prefix, hipMemsetAsync(flags, kNonTiling, 1, st));  // (no path: the pool is not walked)
+    if (in.n_paths)
+        hipLaunchKernelGGL(k_check_spans, dim3((uint32_t)blocks(in.n_paths, kThreads)), dim3(kThreads), 0, st, in.path_begin, in.path_end, in.n_paths,
+                           in.n_steps, flags);
+    if (x.links && in.n_links)
+        hipLaunchKernelGGL(k_check_links<kThreads>, dim3((uint32_t)blocks(in.n_links, kThreads)), dim3(kThreads), 0, st, in.links, in.n_links, in.n_segs,
+                           flags, kBadLink);
+    return FLATGFA_OK;
+}
+
+// the piece counts of the segments, of the steps pool and (for spans that do not tile it) of each path
+template <class Pc>
+void expand_reduce(Expansion &x, const ExpandNames &nm, const Pc &pc, hipStream_t st) {
+    const ChopIn &in = x.in;
+    uint32_t *flags = reinterpret_cast<uint32_t *>(x.hdr);
+    launch_reduce(x.seg, SegCountT<Pc>{pc}, x.hdr + 1, st, nm.reduce_segs);
+    launch_reduce(x.step, StepCountT<Pc>{in.steps, in.n_segs, pc, flags}, x.hdr + 2, st, nm.reduce_steps);
+    if (in.n_paths) {
+        hipLaunchKernelGGL(k_path_lens<Pc>, dim3(std::min<uint32_t>(in.n_paths, 4096)), dim3(kThreads), 0, st, in.steps, in.path_begin, in.path_end,
+                           in.n_paths, in.n_steps, pc, in.n_segs, flags, x.plen);
+        launch_reduce(x.path, ArrCount{x.plen}, x.hdr + 3, st, nm.reduce_paths);
+    }
+}
+
+// Waits for the totals (the count's one host synchronization), checks the flags and then the totals against the u32 id
+// space, and only then allocates the tile maps of the two expansions and enqueues the write of seg_first.
+template <class Pc>
+int expand_totals(Expansion &x, const ExpandNames &nm, const Pc &pc, hipStream_t st, uint64_t *n_new_segs, uint64_t *n_new_steps,
+                  uint64_t *n_new_links) {
+    const ChopIn &in = x.in;
+    FGFA_HIP(nm.prefix, hipGetLastError());
+    uint64_t h[5];
+    FGFA_HIP(nm.prefix, hipMemcpyAsync(h, x.hdr, sizeof h, hipMemcpyDeviceToHost, st));
+    FGFA_HIP(nm.prefix, hipStreamSynchronize(st));
+    const uint32_t f = (uint32_t)h[0];
+    if (f & kBadSpan) return expand_refuse(nm, "a path has a step span outside the steps pool", FLATGFA_ERR_BOUNDS);
+    if (f & kBadPath) return expand_refuse(nm, "a line names a path id that is out of range", FLATGFA_ERR_BOUNDS);
+    if (f & kBadStep) return expand_refuse(nm, "a step refers to a segment id that is out of range", FLATGFA_ERR_BOUNDS);
+    if (f & kBadLink) return expand_refuse(nm, "a link refers to a segment id that is out of range", FLATGFA_ERR_BOUNDS);
+    x.tiling = !(f & kNonTiling);
+    x.S2 = h[1];
+    x.N_old2 = x.tiling ? h[2] : h[3];
+    x.N_add = h[4];
+    x.L2 = x.links ? x.S2 - in.n_segs + in.n_links : 0;
+    // a handle is seg << 1 | orient in a u32; steps and links are counted in u32 (chop.rs through pool.rs Id)
+    if (x.S2 >= 0x80000000ull || x.N_old2 > 0xFFFFFFFFull || x.N2() > 0xFFFFFFFFull || x.L2 > 0xFFFFFFFFull) {
+        set_error(std::string(nm.prefix) + "the " + nm.noun + " would have " + std::to_string(x.S2) + " segments, " + std::to_string(x.N2()) +
+                  " steps and " + std::to_string(x.L2) + " links: more than 32-bit ids hold");
+        return FLATGFA_ERR_TOO_LARGE;
+    }
+    x.seg.n_out_tiles = (x.S2 + kOutTile - 1) / kOutTile;
+    x.step.n_out_tiles = x.tiling ? (x.N_old2 + kOutTile - 1) / kOutTile : 0;
+    const uint64_t mw = x.seg.n_out_tiles + x.step.n_out_tiles;
+    if (mw) {
+        FGFA_HIP(nm.prefix, x.dm.alloc(&x.maps, mw));
+        x.seg.map = x.maps;
+        x.step.map = x.maps + x.seg.n_out_tiles;
+    }
+    // seg_first, now that it fits
+    if (in.n_segs) {
+        launch_prefix(x.seg, st);
+        hipLaunchKernelGGL((k_offsets<SegCountT<Pc>, SegFirstWriter>), dim3((uint32_t)x.seg.n_tiles), dim3(kThreads), 0, st, SegCountT<Pc>{pc},
+                           (uint64_t)in.n_segs, x.seg.prefix, SegFirstWriter{x.seg_first});
+    } else if (x.seg_first) {
+        FGFA_HIP(nm.prefix, hipMemsetAsync(x.seg_first, 0, 4, st));
+    }
+    FGFA_HIP(nm.prefix, hipGetLastError());
+    x.counted = true;
+    *n_new_segs = x.S2;
+    *n_new_steps = x.N2();
+    if (n_new_links) *n_new_links = x.L2;
+    return FLATGFA_OK;
+}
+
+// The old paths' steps and spans (by output tile when the spans tile the pool, per path when they do not), the new segments
+// through the feature's Load / Emit pair, and the old links remapped.  `n_added`: the paths the feature writes behind the old.
+template <class Load, class Emit>
+int expand_fill(Expansion &x, const ExpandNames &nm, const Load &ld, const Emit &em, const ChopOut &out, uint64_t n_added, hipStream_t st) {
+    if (!x.counted) return expand_refuse(nm, "fill before a successful count", FLATGFA_ERR_ARG);
+    const ChopIn &in = x.in;
+    if ((x.N2() && !out.steps) || ((in.n_paths || n_added) && (!out.path_begin || !out.path_end)) || (x.links && x.L2 && !out.links))
+        return expand_refuse(nm, "NULL output", FLATGFA_ERR_ARG);
+    x.dm.st = st;
+    if (x.tiling) {
+        launch_prefix(x.step, st);
+        launch_map(x.step, st);
+        if (x.N_old2) {
+            ProfScope ps(nm.expand_steps, st);
+            hipLaunchKernelGGL((k_expand<StepLoad, StepEmit>), dim3((uint32_t)x.step.n_out_tiles), dim3(kThreads), 0, st,
+                               StepLoad{in.steps, x.seg_first, in.n_segs}, StepEmit{}, in.n_steps, x.step.prefix, x.step.n_tiles, x.step.map, x.N_old2,
+                               out.steps);
+        }
+        if (in.n_paths)
+            hipLaunchKernelGGL(k_path_spans, dim3((uint32_t)blocks(in.n_paths, kThreads / 64)), dim3(kThreads), 0, st, in.steps, in.path_begin, in.path_end,
+                               in.n_paths, in.n_steps, x.seg_first, in.n_segs, x.step.prefix, out.path_begin, out.path_end);
+    } else if (in.n_paths) {
+        launch_prefix(x.path, st);
+        hipLaunchKernelGGL((k_offsets<ArrCount, PathWriter>), dim3((uint32_t)x.path.n_tiles), dim3(kThreads), 0, st, ArrCount{x.plen},
+                           (uint64_t)in.n_paths, x.path.prefix, PathWriter{out.path_begin, out.path_end});
+        ProfScope ps(nm.expand_paths, st);
+        hipLaunchKernelGGL(k_expand_paths, dim3(std::min<uint32_t>(in.n_paths, 4096)), dim3(kThreads), 0, st, in.steps, in.path_begin, in.path_end,
+                           in.n_paths, in.n_steps, x.seg_first, in.n_segs, out.path_begin, out.steps);
+    }
+    if (x.S2) {
+        launch_map(x.seg, st);
+        ProfScope ps(nm.expand_segs, st);
+        hipLaunchKernelGGL((k_expand<Load, Emit>), dim3((uint32_t)x.seg.n_out_tiles), dim3(kThreads), 0, st, ld, em, (uint64_t)in.n_segs, x.seg.prefix,
+                           x.seg.n_tiles, x.seg.map, x.S2, out.seg_len);
+    }
+    if (x.links && in.n_links)
+        hipLaunchKernelGGL(k_links, dim3((uint32_t)blocks(in.n_links, kThreads)), dim3(kThreads), 0, st, in.links, in.n_links, x.seg_first, in.n_segs,
+                           out.links + (x.S2 - in.n_segs) * 4);
+    FGFA_HIP(nm.prefix, hipGetLastError());
+    return FLATGFA_OK;
+}
+
+// ---- the device-level C ABI's arguments (include/flatgfa.h Part 3) ----
+inline ChopIn chop_in_of(const flatgfa_dev_graph_t &g) {
+    ChopIn in;
+    in.steps = g.steps;
+    in.n_steps = g.n_steps;
+    in.path_begin = g.path_begin;
+    in.path_end = g.path_end;
+    in.n_paths = g.n_paths;
+    in.n_segs = g.n_segs;
+    in.seg_len = g.seg_len;
+    return in;
+}
+inline ChopOut chop_out_of(uint32_t *steps, uint32_t *path_begin, uint32_t *path_end, uint32_t *seg_len) {
+    ChopOut out;
+    out.steps = steps;
+    out.path_begin = path_begin;
+    out.path_end = path_end;
+    out.seg_len = seg_len;
+    return out;
 }
 
 }  // namespace

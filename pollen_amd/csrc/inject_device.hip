@@ -13,7 +13,9 @@
 //                 k_sort_short sorts the rows of up to 16 keys by one lane and lists the longer ones, k_sort_long sorts each
 //                 listed row with a workgroup (bitonic, in place), a scan of the "differs from the key before" flags
 //                 compacts them: cut_row[s] .. cut_row[s + 1] are the distinct sorted cuts of s, seg_first[s] = s + cut_row[s].
-//   expansion     chop's kernels (expand_kernels.hpp) with the piece count of a segment taken from the table: k + 1.
+//   expansion     the kernels and the driver that chop uses too (expand_kernels.hpp: the Expansion and its expand_* functions,
+//                 called in order below with inject's launches between them), with the piece count of a segment taken from
+//                 the table: k + 1.
 //   new paths     noff[i] = the new steps before old step i of the pool (a u32 scan); k_line_spans finds each line's
 //                 [n_lo, n_hi) relative to its path's new begin -- the old step that holds low or high, plus the pieces before
 //                 the cut within it (reversed for a backward step) -- a scan of the lengths lays the new paths out behind the old
@@ -40,7 +42,6 @@ constexpr uint32_t kPer = 4;         // consecutive elements per lane of the til
 constexpr uint32_t kScanTile = kThreads * kPer;
 constexpr uint32_t kLinear = 16;     // cut rows up to this long are sorted by one lane
 constexpr uint32_t kMaxGrid = 2048;  // workgroups of a grid-stride launch
-constexpr uint32_t kBadPath = 16;    // (the flag bits below it are expand_kernels.hpp's)
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 
 // the pieces of a segment: one more than its distinct cuts
@@ -48,8 +49,6 @@ struct CutPieces {
     const uint32_t *cut_row;
     __device__ uint64_t operator()(uint32_t s) const { return (uint64_t)(cut_row[s + 1] - cut_row[s]) + 1; }
 };
-using SegCount = SegCountT<CutPieces>;
-using StepCount = StepCountT<CutPieces>;
 
 // ---- positions ----
 struct PosOp {  // pre[i] = the lengths of the steps before i (a step that names no segment has none); i runs to n inclusive
@@ -333,19 +332,17 @@ __global__ __launch_bounds__(kThreads) void k_copy_lines(uint32_t *steps, uint64
     }
 }
 
+constexpr ExpandNames kInject{"inject: ", "graph", "k_inject_reduce_segs", "k_inject_reduce_steps", "k_inject_reduce_paths",
+                              "k_inject_expand_steps", "k_inject_expand_paths", "k_inject_expand_segs"};
+
 }  // namespace
 
 struct InjectJob {
-    ChopIn in;
+    Expansion x;  // (N_add: the new paths' steps)
     InjectLines lines;
-    bool links = false, counted = false, tiling = true;
-    uint32_t *seg_first = nullptr;
-    uint64_t S2 = 0, N_old2 = 0, N2 = 0, L2 = 0;
-    DeviceMem dm;  // (waits for the last stream, then frees)
-    uint64_t *hdr = nullptr;  // [0] flags, [1] new segments, [2] old paths' new steps (tiling), [3] (per path), [4] the new paths' steps
-    uint64_t *plen = nullptr, *line_len = nullptr;
-    uint32_t *cut_row = nullptr, *cuts = nullptr, *line_rel = nullptr, *maps = nullptr;
-    ScanBuf seg, step, path, line;
+    uint64_t *line_len = nullptr;
+    uint32_t *cut_row = nullptr, *cuts = nullptr, *line_rel = nullptr;
+    ScanBuf line;
 };
 
 InjectJob *inject_new() { return new InjectJob(); }
@@ -355,70 +352,47 @@ void inject_free(InjectJob *j) { delete j; }
 
 int inject_count(InjectJob *j, const ChopIn &in, const InjectLines &ln, bool links, uint32_t *seg_first, hipStream_t st, uint64_t *n_new_segs,
                  uint64_t *n_new_steps, uint64_t *n_new_links) {
-    if ((in.n_segs && (!in.seg_len || !seg_first)) || (in.n_steps && !in.steps) || (in.n_paths && (!in.path_begin || !in.path_end)) ||
-        (links && in.n_links && !in.links) || (ln.n && (!ln.path_id || !ln.start || !ln.end))) {
-        set_error("inject: NULL argument");
-        return FLATGFA_ERR_ARG;
-    }
-    if (in.n_steps > 0xFFFFFFFFull || in.n_segs > 0x80000000u) { set_error("inject: graph too large for 32-bit ids"); return FLATGFA_ERR_TOO_LARGE; }
+    if (int rc = expand_check_args(kInject, in, links, seg_first, ln.n && (!ln.path_id || !ln.start || !ln.end))) return rc;
     if (ln.n >= 0x7FFFFFFFull || (uint64_t)in.n_paths + ln.n > 0xFFFFFFFFull) {
         set_error("inject: " + std::to_string(ln.n) + " lines: more paths than 32-bit ids hold");
         return FLATGFA_ERR_TOO_LARGE;
     }
-    if (j->counted) { set_error("inject: this job was counted already"); return FLATGFA_ERR_ARG; }
-    j->in = in;
+    Expansion &x = j->x;
+    const uint64_t N = in.n_steps, S = in.n_segs, n = ln.n, M = 2 * n;
+    // behind the driver's scratch, in its one block: the lines' scan and their lengths
+    uint64_t *p = nullptr;
+    if (int rc = expand_begin(x, kInject, in, links, seg_first, st, ScanBuf::words_for(n) + n, &p)) return rc;
     j->lines = ln;
-    j->links = links;
-    j->seg_first = seg_first;
-    j->dm.st = st;
-    const uint64_t N = in.n_steps, S = in.n_segs, P = in.n_paths, n = ln.n, M = 2 * n;
-    // the scans' scratch (chop's layout): header, segments, steps, paths, lines, per-path lengths, per-line lengths
-    const size_t words = 8 + ScanBuf::words_for(S) + ScanBuf::words_for(N) + ScanBuf::words_for(P) + ScanBuf::words_for(n) + P + n;
-    uint64_t *mem = nullptr;
-    INJ_HIP(j->dm.alloc(&mem, words));
-    INJ_HIP(hipMemsetAsync(mem, 0, words * 8, st));
-    uint64_t *p = mem;
-    j->hdr = p;
-    p += 8;
-    j->seg.place(S, p);
-    j->step.place(N, p);
-    j->path.place(P, p);
     j->line.place(n, p);
-    j->plen = p;
-    j->line_len = p + P;
-    uint32_t *flags = reinterpret_cast<uint32_t *>(j->hdr);
+    j->line_len = p;
+    uint32_t *flags = reinterpret_cast<uint32_t *>(x.hdr);
     // positions, line ends, the cut table
     uint64_t *pre = nullptr, *raw = nullptr;
     uint32_t *noff = nullptr, *end_step = nullptr, *end_seg = nullptr, *end_pos = nullptr, *raw_row = nullptr, *cursor = nullptr, *list = nullptr,
              *dpos = nullptr, *words4 = nullptr;
     const uint64_t list_cap = M / (kLinear + 1) + 1;  // (a listed row holds more than kLinear of the M keys)
     const uint64_t n_pos = n ? N + 1 : 0;  // (no line: no position is asked for, and the copy of the graph costs no 12 bytes a step)
-    INJ_HIP(j->dm.alloc(&pre, n_pos));
-    INJ_HIP(j->dm.alloc(&noff, n_pos));
-    INJ_HIP(j->dm.alloc(&end_step, 3 * M));
+    INJ_HIP(x.dm.alloc(&pre, n_pos));
+    INJ_HIP(x.dm.alloc(&noff, n_pos));
+    INJ_HIP(x.dm.alloc(&end_step, 3 * M));
     end_seg = end_step + M;
     end_pos = end_seg + M;
-    INJ_HIP(j->dm.alloc(&raw_row, 2 * (S + 2)));  // the raw rows, then the rows of distinct cuts
+    INJ_HIP(x.dm.alloc(&raw_row, 2 * (S + 2)));  // the raw rows, then the rows of distinct cuts
     j->cut_row = raw_row + (S + 2);
-    INJ_HIP(j->dm.alloc(&cursor, S));
-    INJ_HIP(j->dm.alloc(&list, list_cap));
-    INJ_HIP(j->dm.alloc(&raw, M));
-    INJ_HIP(j->dm.alloc(&dpos, M + 1));
-    INJ_HIP(j->dm.alloc(&j->cuts, M));
-    INJ_HIP(j->dm.alloc(&j->line_rel, n));
-    INJ_HIP(j->dm.alloc(&words4, 4));  // the long-row count
+    INJ_HIP(x.dm.alloc(&cursor, S));
+    INJ_HIP(x.dm.alloc(&list, list_cap));
+    INJ_HIP(x.dm.alloc(&raw, M));
+    INJ_HIP(x.dm.alloc(&dpos, M + 1));
+    INJ_HIP(x.dm.alloc(&j->cuts, M));
+    INJ_HIP(x.dm.alloc(&j->line_rel, n));
+    INJ_HIP(x.dm.alloc(&words4, 4));  // the long-row count
     Spine<Sum<uint64_t>> sp;  // (one spine for the scans below, which run one behind another)
-    INJ_HIP(sp.alloc(&j->dm, blocks(std::max<uint64_t>(std::max(n_pos, M), S) + 2, kScanTile)));
+    INJ_HIP(sp.alloc(&x.dm, blocks(std::max<uint64_t>(std::max(n_pos, M), S) + 2, kScanTile)));
     INJ_HIP(hipMemsetAsync(raw_row, 0, 2 * (S + 2) * 4, st));
     INJ_HIP(hipMemsetAsync(cursor, 0, std::max<uint64_t>(S, 1) * 4, st));
     INJ_HIP(hipMemsetAsync(words4, 0, 16, st));
     INJ_HIP(hipMemsetAsync(dpos, 0, 4, st));
-    if (P == 0) INJ_HIP(hipMemsetAsync(flags, kNonTiling, 1, st));  // (no path: the pool is not walked)
-    if (P)
-        hipLaunchKernelGGL(k_check_spans, dim3((uint32_t)blocks(P, kThreads)), dim3(kThreads), 0, st, in.path_begin, in.path_end, in.n_paths, N, flags);
-    if (links && in.n_links)
-        hipLaunchKernelGGL(k_check_links<kThreads>, dim3((uint32_t)blocks(in.n_links, kThreads)), dim3(kThreads), 0, st, in.links, in.n_links, in.n_segs,
-                           flags, kBadLink);
+    if (int rc = expand_check_graph(x, kInject, st)) return rc;
     const Spine<Sum<uint32_t>> sp32{sp.aggr, sp.prefix, sp.total};
     if (n) {
         ProfScope ps("k_inject_positions", st);
@@ -449,15 +423,9 @@ int inject_count(InjectJob *j, const ChopIn &in, const InjectLines &ln, bool lin
         hipLaunchKernelGGL(k_cut_compact, dim3((uint32_t)blocks(M, kThreads)), dim3(kThreads), 0, st, raw, raw_row + S, dpos, j->cuts);
         hipLaunchKernelGGL(k_cut_rows, dim3((uint32_t)blocks(S + 1, kThreads)), dim3(kThreads), 0, st, raw_row, dpos, S + 1, j->cut_row);
     }
-    // the piece counts, as chop's
+    // the piece counts, from the table
     const CutPieces pc{j->cut_row};
-    launch_reduce(j->seg, SegCount{pc}, j->hdr + 1, st, "k_inject_reduce_segs");
-    launch_reduce(j->step, StepCount{in.steps, in.n_segs, pc, flags}, j->hdr + 2, st, "k_inject_reduce_steps");
-    if (P) {
-        hipLaunchKernelGGL(k_path_lens<CutPieces>, dim3(std::min<uint32_t>(in.n_paths, 4096)), dim3(kThreads), 0, st, in.steps, in.path_begin,
-                           in.path_end, in.n_paths, N, pc, in.n_segs, flags, j->plen);
-        launch_reduce(j->path, ArrCount{j->plen}, j->hdr + 3, st, "k_inject_reduce_paths");
-    }
+    expand_reduce(x, kInject, pc, st);
     // the new paths' lengths
     if (n) {
         ProfScope ps("k_inject_line_spans", st);
@@ -466,102 +434,28 @@ int inject_count(InjectJob *j, const ChopIn &in, const InjectLines &ln, bool lin
         scan_apply<kThreads, kPer>(nop, N + 1, sp32, st);
         hipLaunchKernelGGL(k_line_spans, dim3((uint32_t)blocks(n, kThreads)), dim3(kThreads), 0, st, ln.path_id, ln.start, n, in.path_begin, in.path_end,
                            in.n_paths, in.steps, N, pre, noff, end_step, end_seg, end_pos, j->cut_row, j->cuts, j->line_rel, j->line_len);
-        launch_reduce(j->line, ArrCount{j->line_len}, j->hdr + 4, st, "k_inject_reduce_lines");
+        launch_reduce(j->line, ArrCount{j->line_len}, x.hdr + 4, st, "k_inject_reduce_lines");
     }
-    INJ_HIP(hipGetLastError());
-    uint64_t h[5];
-    INJ_HIP(hipMemcpyAsync(h, j->hdr, sizeof h, hipMemcpyDeviceToHost, st));
-    INJ_HIP(hipStreamSynchronize(st));
-    const uint32_t f = (uint32_t)h[0];
-    if (f & kBadSpan) { set_error("inject: a path has a step span outside the steps pool"); return FLATGFA_ERR_BOUNDS; }
-    if (f & kBadPath) { set_error("inject: a line names a path id that is out of range"); return FLATGFA_ERR_BOUNDS; }
-    if (f & kBadStep) { set_error("inject: a step refers to a segment id that is out of range"); return FLATGFA_ERR_BOUNDS; }
-    if (f & kBadLink) { set_error("inject: a link refers to a segment id that is out of range"); return FLATGFA_ERR_BOUNDS; }
-    j->tiling = !(f & kNonTiling);
-    j->S2 = h[1];
-    j->N_old2 = j->tiling ? h[2] : h[3];
-    j->N2 = j->N_old2 + h[4];
-    j->L2 = links ? j->S2 - S + in.n_links : 0;
-    if (j->S2 >= 0x80000000ull || j->N_old2 > 0xFFFFFFFFull || j->N2 > 0xFFFFFFFFull || j->L2 > 0xFFFFFFFFull) {
-        set_error("inject: the graph would have " + std::to_string(j->S2) + " segments, " + std::to_string(j->N2) + " steps and " +
-                  std::to_string(j->L2) + " links: more than 32-bit ids hold");
-        return FLATGFA_ERR_TOO_LARGE;
-    }
-    // the tile maps of the two expansions
-    j->seg.n_out_tiles = (j->S2 + kOutTile - 1) / kOutTile;
-    j->step.n_out_tiles = j->tiling ? (j->N_old2 + kOutTile - 1) / kOutTile : 0;
-    const uint64_t mw = j->seg.n_out_tiles + j->step.n_out_tiles;
-    if (mw) {
-        INJ_HIP(j->dm.alloc(&j->maps, mw));
-        j->seg.map = j->maps;
-        j->step.map = j->maps + j->seg.n_out_tiles;
-    }
-    // seg_first, now that it fits
-    if (S) {
-        launch_prefix(j->seg, st);
-        hipLaunchKernelGGL((k_offsets<SegCount, SegFirstWriter>), dim3((uint32_t)j->seg.n_tiles), dim3(kThreads), 0, st, SegCount{pc}, S, j->seg.prefix,
-                           SegFirstWriter{seg_first});
-    } else if (seg_first) {
-        INJ_HIP(hipMemsetAsync(seg_first, 0, 4, st));
-    }
-    INJ_HIP(hipGetLastError());
-    j->counted = true;
-    *n_new_segs = j->S2;
-    *n_new_steps = j->N2;
-    if (n_new_links) *n_new_links = j->L2;
-    return FLATGFA_OK;
+    return expand_totals(x, kInject, pc, st, n_new_segs, n_new_steps, n_new_links);
 }
 
 int inject_fill(InjectJob *j, const ChopOut &out, hipStream_t st) {
-    if (!j->counted) { set_error("inject: fill before a successful count"); return FLATGFA_ERR_ARG; }
-    const ChopIn &in = j->in;
+    Expansion &x = j->x;
+    const ChopIn &in = x.in;
     const uint64_t n = j->lines.n;
-    if ((j->N2 && !out.steps) || ((in.n_paths || n) && (!out.path_begin || !out.path_end)) || (j->links && j->L2 && !out.links)) {
-        set_error("inject: NULL output");
-        return FLATGFA_ERR_ARG;
-    }
-    j->dm.st = st;
-    // the old paths, as chop's
-    if (j->tiling) {
-        launch_prefix(j->step, st);
-        launch_map(j->step, st);
-        if (j->N_old2) {
-            ProfScope ps("k_inject_expand_steps", st);
-            hipLaunchKernelGGL((k_expand<StepLoad, StepEmit>), dim3((uint32_t)j->step.n_out_tiles), dim3(kThreads), 0, st,
-                               StepLoad{in.steps, j->seg_first, in.n_segs}, StepEmit{}, in.n_steps, j->step.prefix, j->step.n_tiles, j->step.map,
-                               j->N_old2, out.steps);
-        }
-        if (in.n_paths)
-            hipLaunchKernelGGL(k_path_spans, dim3((uint32_t)blocks(in.n_paths, kThreads / 64)), dim3(kThreads), 0, st, in.steps, in.path_begin, in.path_end,
-                               in.n_paths, in.n_steps, j->seg_first, in.n_segs, j->step.prefix, out.path_begin, out.path_end);
-    } else if (in.n_paths) {
-        launch_prefix(j->path, st);
-        hipLaunchKernelGGL((k_offsets<ArrCount, PathWriter>), dim3((uint32_t)j->path.n_tiles), dim3(kThreads), 0, st, ArrCount{j->plen},
-                           (uint64_t)in.n_paths, j->path.prefix, PathWriter{out.path_begin, out.path_end});
-        ProfScope ps("k_inject_expand_paths", st);
-        hipLaunchKernelGGL(k_expand_paths, dim3(std::min<uint32_t>(in.n_paths, 4096)), dim3(kThreads), 0, st, in.steps, in.path_begin,
-                           in.path_end, in.n_paths, in.n_steps, j->seg_first, in.n_segs, out.path_begin, out.steps);
-    }
-    if (j->S2) {
-        launch_map(j->seg, st);
-        ProfScope ps("k_inject_expand_segs", st);
-        hipLaunchKernelGGL((k_expand<CutSegLoad, CutSegEmit>), dim3((uint32_t)j->seg.n_out_tiles), dim3(kThreads), 0, st,
-                           CutSegLoad{in.seg_len, j->cut_row}, CutSegEmit{j->cuts, in.seq_start, out.seg_recs, j->links ? out.links : nullptr},
-                           (uint64_t)in.n_segs, j->seg.prefix, j->seg.n_tiles, j->seg.map, j->S2, out.seg_len);
-    }
-    if (j->links && in.n_links)
-        hipLaunchKernelGGL(k_links, dim3((uint32_t)blocks(in.n_links, kThreads)), dim3(kThreads), 0, st, in.links, in.n_links, j->seg_first, in.n_segs,
-                           out.links + (j->S2 - in.n_segs) * 4);
+    if (int rc = expand_fill(x, kInject, CutSegLoad{in.seg_len, j->cut_row},
+                             CutSegEmit{j->cuts, in.seq_start, out.seg_recs, x.links ? out.links : nullptr}, out, n, st))
+        return rc;
     // the new paths, behind the old ones
     if (n) {
         uint32_t *nb = out.path_begin + in.n_paths, *ne = out.path_end + in.n_paths;
         launch_prefix(j->line, st);
         hipLaunchKernelGGL((k_offsets<ArrCount, NewPathWriter>), dim3((uint32_t)j->line.n_tiles), dim3(kThreads), 0, st, ArrCount{j->line_len}, n,
-                           j->line.prefix, NewPathWriter{nb, ne, j->N_old2});
-        if (j->N2 > j->N_old2) {
+                           j->line.prefix, NewPathWriter{nb, ne, x.N_old2});
+        if (x.N_add) {
             ProfScope ps("k_inject_copy_lines", st);
-            hipLaunchKernelGGL(k_copy_lines, dim3((uint32_t)blocks(j->N2 - j->N_old2, kOutTile)), dim3(kThreads), 0, st, out.steps, j->N_old2, j->N2, nb,
-                               ne, n, j->lines.path_id, j->line_rel, out.path_begin);
+            hipLaunchKernelGGL(k_copy_lines, dim3((uint32_t)blocks(x.N_add, kOutTile)), dim3(kThreads), 0, st, out.steps, x.N_old2, x.N2(), nb, ne, n,
+                               j->lines.path_id, j->line_rel, out.path_begin);
         }
     }
     INJ_HIP(hipGetLastError());
@@ -571,10 +465,7 @@ int inject_fill(InjectJob *j, const ChopOut &out, hipStream_t st) {
 }  // namespace fgfa_dev
 
 // ---- the device-level C ABI (include/flatgfa.h Part 3) ----
-struct flatgfa_dev_inject {
-    fgfa_dev::InjectJob *job = nullptr;
-    ~flatgfa_dev_inject() { fgfa_dev::inject_free(job); }
-};
+struct flatgfa_dev_inject : fgfa_dev::InjectJob {};
 
 extern "C" {
 
@@ -584,22 +475,13 @@ int flatgfa_dev_inject_count(const flatgfa_dev_graph_t *g, const uint32_t *d_pat
     if (job) *job = nullptr;
     if (!g || !job || !n_segs_out || !n_steps_out || !n_paths_out) { fgfa_dev::set_error("flatgfa_dev_inject_count: NULL argument"); return FLATGFA_ERR_ARG; }
     if (!g->seg_len) { fgfa_dev::set_error("flatgfa_dev_inject_count: the graph has no seg_len"); return FLATGFA_ERR_ARG; }
-    fgfa_dev::ChopIn in;
-    in.steps = g->steps;
-    in.n_steps = g->n_steps;
-    in.path_begin = g->path_begin;
-    in.path_end = g->path_end;
-    in.n_paths = g->n_paths;
-    in.n_segs = g->n_segs;
-    in.seg_len = g->seg_len;
     fgfa_dev::InjectLines ln;
     ln.path_id = d_path_id;
     ln.start = d_start;
     ln.end = d_end;
     ln.n = n;
     auto *h = new flatgfa_dev_inject();
-    h->job = fgfa_dev::inject_new();
-    const int rc = fgfa_dev::inject_count(h->job, in, ln, false, seg_first, (hipStream_t)stream, n_segs_out, n_steps_out, nullptr);
+    const int rc = fgfa_dev::inject_count(h, fgfa_dev::chop_in_of(*g), ln, false, seg_first, (hipStream_t)stream, n_segs_out, n_steps_out, nullptr);
     if (rc) {
         delete h;
         return rc;
@@ -611,12 +493,7 @@ int flatgfa_dev_inject_count(const flatgfa_dev_graph_t *g, const uint32_t *d_pat
 
 int flatgfa_dev_inject_fill(flatgfa_dev_inject_t *job, uint32_t *steps, uint32_t *path_begin, uint32_t *path_end, uint32_t *seg_len, void *stream) {
     if (!job) { fgfa_dev::set_error("flatgfa_dev_inject_fill: NULL job"); return FLATGFA_ERR_ARG; }
-    fgfa_dev::ChopOut out;
-    out.steps = steps;
-    out.path_begin = path_begin;
-    out.path_end = path_end;
-    out.seg_len = seg_len;
-    return fgfa_dev::inject_fill(job->job, out, (hipStream_t)stream);
+    return fgfa_dev::inject_fill(job, fgfa_dev::chop_out_of(steps, path_begin, path_end, seg_len), (hipStream_t)stream);
 }
 
 void flatgfa_dev_inject_free(flatgfa_dev_inject_t *job) { delete job; }

@@ -20,7 +20,8 @@ struct InjectLines {
 // One inject: count() checks the graph and the lines, locates the cuts, builds the cut table, scans the piece counts and the new
 // paths' lengths, waits for the totals (its one host synchronization), checks them and enqueues the write of seg_first; fill()
 // enqueues the rest.  A fill writes ChopOut with path_begin / path_end of n_paths + n entries: the old paths, then one new
-// path per line.  Both return FLATGFA_* codes (flatgfa_last_error).
+// path per line.  Both return FLATGFA_* codes (flatgfa_last_error).  The job is an Expansion (expand_kernels.hpp, the driver
+// chop and inject share) plus the lines, the cut table and the lines' scan; inject_free waits and frees as chop_free does.
 struct InjectJob;
 InjectJob *inject_new();
 void inject_free(InjectJob *j);

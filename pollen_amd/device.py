@@ -318,36 +318,45 @@ def pangenotype_row(gfa, text, row, first_bad, stream=None) -> None:
                                                       first_bad.data_ptr(), ctypes.c_void_p(st.cuda_stream)), "dev_pangenotype_row")
 
 
-def chop(graph: DeviceGraph, max_size: int, stream=None) -> Tuple[DeviceGraph, object]:
-    """chop (flatgfa/src/ops/chop.rs, without links) of a resident graph image, on the device: returns the chopped image
-    as a new DeviceGraph (int32 tensors on the same device; a valid input to DepthPlan) and seg_first (int32[n_segs + 1]:
-    old segment s became the new segments [seg_first[s], seg_first[s + 1])).  Needs graph.seg_len.  Waits for the stream
-    once, to learn the sizes (flatgfa_dev_chop_count); the rest is enqueued on it (torch's current stream by default)."""
+def _ptr(t):
+    return t.data_ptr() if t.numel() else None
+
+
+def _expand(graph: DeviceGraph, what: str, stream, count, n_added: int = 0):
+    """What chop and inject share: `count(L, g, seg_first, stream, job, n_segs, n_steps)` calls flatgfa_dev_<what>_count
+    with the feature's own arguments beside these and returns its code; the image of graph.n_paths + n_added paths is then
+    allocated and filled, and the job freed.  Returns (the new DeviceGraph, seg_first)."""
     torch = _torch()
     if graph.seg_len is None:
-        raise FlatGFAError("chop: the graph has no seg_len", -1)
+        raise FlatGFAError(what + ": the graph has no seg_len", -1)
     with torch.cuda.device(graph.device):
         st = stream if stream is not None else torch.cuda.current_stream(graph.device)
+        st_ptr = ctypes.c_void_p(st.cuda_stream)
         g = graph.c_struct()
         seg_first = torch.empty(graph.n_segs + 1, dtype=torch.int32, device=graph.device)
         job = ctypes.c_void_p()
         n_segs, n_steps = ctypes.c_uint64(), ctypes.c_uint64()
         L = _lib.lib()
-        _check(L.flatgfa_dev_chop_count(ctypes.byref(g), int(max_size), seg_first.data_ptr(), ctypes.c_void_p(st.cuda_stream),
-                                        ctypes.byref(job), ctypes.byref(n_segs), ctypes.byref(n_steps)), "dev_chop_count")
+        _check(count(L, ctypes.byref(g), seg_first.data_ptr(), st_ptr, ctypes.byref(job), ctypes.byref(n_segs), ctypes.byref(n_steps)),
+               "dev_%s_count" % what)
         try:
             steps = torch.empty(n_steps.value, dtype=torch.int32, device=graph.device)
-            pb = torch.empty(graph.n_paths, dtype=torch.int32, device=graph.device)
-            pe = torch.empty(graph.n_paths, dtype=torch.int32, device=graph.device)
+            pb = torch.empty(graph.n_paths + n_added, dtype=torch.int32, device=graph.device)
+            pe = torch.empty(graph.n_paths + n_added, dtype=torch.int32, device=graph.device)
             seg_len = torch.empty(n_segs.value, dtype=torch.int32, device=graph.device)
-
-            def ptr(t):
-                return t.data_ptr() if t.numel() else None
-            _check(L.flatgfa_dev_chop_fill(job, ptr(steps), ptr(pb), ptr(pe), ptr(seg_len), ctypes.c_void_p(st.cuda_stream)),
-                   "dev_chop_fill")
+            _check(getattr(L, "flatgfa_dev_%s_fill" % what)(job, _ptr(steps), _ptr(pb), _ptr(pe), _ptr(seg_len), st_ptr), "dev_%s_fill" % what)
         finally:
-            L.flatgfa_dev_chop_free(job)  # (waits for the fill)
+            getattr(L, "flatgfa_dev_%s_free" % what)(job)  # (waits for the fill)
         return DeviceGraph.from_tensors(steps, pb, pe, n_segs.value, seg_len), seg_first
+
+
+def chop(graph: DeviceGraph, max_size: int, stream=None) -> Tuple[DeviceGraph, object]:
+    """chop (flatgfa/src/ops/chop.rs, without links) of a resident graph image, on the device: returns the chopped image
+    as a new DeviceGraph (int32 tensors on the same device; a valid input to DepthPlan) and seg_first (int32[n_segs + 1]:
+    old segment s became the new segments [seg_first[s], seg_first[s + 1])).  Needs graph.seg_len.  Waits for the stream
+    once, to learn the sizes (flatgfa_dev_chop_count); the rest is enqueued on it (torch's current stream by default)."""
+    return _expand(graph, "chop", stream, lambda L, g, seg_first, st, job, n_segs, n_steps:
+                   L.flatgfa_dev_chop_count(g, int(max_size), seg_first, st, job, n_segs, n_steps))
 
 
 def inject(graph: DeviceGraph, path_ids, starts, ends, stream=None) -> Tuple[DeviceGraph, object]:
@@ -364,29 +373,10 @@ def inject(graph: DeviceGraph, path_ids, starts, ends, stream=None) -> Tuple[Dev
     assert path_ids.dtype == torch.int32 and starts.dtype == torch.int64 and ends.dtype == torch.int64
     assert starts.numel() == n and ends.numel() == n
     assert all(t.is_cuda and t.is_contiguous() for t in (path_ids, starts, ends))
-    with torch.cuda.device(graph.device):
-        st = stream if stream is not None else torch.cuda.current_stream(graph.device)
-        g = graph.c_struct()
-        seg_first = torch.empty(graph.n_segs + 1, dtype=torch.int32, device=graph.device)
-        job = ctypes.c_void_p()
-        n_segs, n_steps, n_paths = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-        L = _lib.lib()
-
-        def ptr(t):
-            return t.data_ptr() if t.numel() else None
-        _check(L.flatgfa_dev_inject_count(ctypes.byref(g), ptr(path_ids), ptr(starts), ptr(ends), n, seg_first.data_ptr(),
-                                          ctypes.c_void_p(st.cuda_stream), ctypes.byref(job), ctypes.byref(n_segs), ctypes.byref(n_steps),
-                                          ctypes.byref(n_paths)), "dev_inject_count")
-        try:
-            steps = torch.empty(n_steps.value, dtype=torch.int32, device=graph.device)
-            pb = torch.empty(n_paths.value, dtype=torch.int32, device=graph.device)
-            pe = torch.empty(n_paths.value, dtype=torch.int32, device=graph.device)
-            seg_len = torch.empty(n_segs.value, dtype=torch.int32, device=graph.device)
-            _check(L.flatgfa_dev_inject_fill(job, ptr(steps), ptr(pb), ptr(pe), ptr(seg_len), ctypes.c_void_p(st.cuda_stream)),
-                   "dev_inject_fill")
-        finally:
-            L.flatgfa_dev_inject_free(job)  # (waits for the fill)
-        return DeviceGraph.from_tensors(steps, pb, pe, n_segs.value, seg_len), seg_first
+    n_paths = ctypes.c_uint64()  # (graph.n_paths + n)
+    return _expand(graph, "inject", stream, lambda L, g, seg_first, st, job, n_segs, n_steps:
+                   L.flatgfa_dev_inject_count(g, _ptr(path_ids), _ptr(starts), _ptr(ends), n, seg_first, st, job, n_segs, n_steps,
+                                              ctypes.byref(n_paths)), n)
 
 
 def crush(graph: DeviceGraph, seg_seq, seq_data, stream=None):
