@@ -389,6 +389,28 @@ int flatgfa_flatten_bed(flatgfa_t gfa, const char *name, size_t name_len, char *
  * ends the call with FLATGFA_ERR_IO, and nothing more is delivered. */
 typedef int (*flatgfa_sink_t)(void *ctx, const char *bytes, size_t n); /* nonzero: stop */
 int flatgfa_flatten_stream(flatgfa_t gfa, const char *name, size_t name_len, int what, flatgfa_sink_t sink, void *ctx);
+/* The packed-sequence codec (flatgfa/src/packedseq.rs; `fgfa seq-export INPUT OUTPUT`, `fgfa seq-import FILE`,
+ * cli/cmds.rs:415-452).  No graph is read.  The file: a 25-byte header without padding -- u64 magic 0x12, u64 len, u64
+ * capacity (the writer's equals len), u8 high_nibble_end (1: an even number of bases, zero included), little-endian -- then
+ * len data bytes of two bases each, base 2k in the low nibble of byte k and base 2k + 1 in the high one, A = 0, C = 1, T = 2,
+ * G = 3; the unused high nibble of an odd sequence's last byte is written as 0 and never read.
+ * flatgfa_seq_export packs `text` on the GPU (device 0) into a malloc'd file image (release with flatgfa_free_text):
+ * whitespace -- space, \t, \n, \x0C, \r; not \x0B -- is dropped and every other byte must be one of A C T G, else
+ * FLATGFA_ERR_PARSE with flatgfa_last_error naming the smallest offending offset and its byte ("seq-export: byte 0x6e at offset
+ * 12 is not a nucleotide"), *file_image left NULL and, for flatgfa_seq_export_file, no file made.  flatgfa_seq_import unpacks a
+ * file image into the bases, without a newline, in a malloc'd buffer (release with flatgfa_free_text); flatgfa_seq_import_stream
+ * hands the same bytes to `sink` in pieces (a sink that returns nonzero: FLATGFA_ERR_IO).  FLATGFA_ERR_PARSE, before any
+ * device work, for a file shorter than the header, a wrong magic, high_nibble_end not 0 or 1, capacity < len, fewer than
+ * capacity bytes behind the header, or len == 0 with high_nibble_end == 0; and, with nothing delivered, for a nibble above 3
+ * among the bases, flatgfa_last_error naming the smallest such base index.  Bytes behind the data are ignored.
+ * flatgfa_seq_packed_info is the header check alone, on the host: the base count and where the data begin.  n == 0 is valid
+ * with a NULL pointer.  Text and packed bytes travel in chunks of 64 MiB; the result does not depend on where they are cut.
+ * Without a device the export and import calls return FLATGFA_ERR_NO_DEVICE; NULL arguments: FLATGFA_ERR_ARG. */
+int flatgfa_seq_export(const uint8_t *text, size_t n, uint8_t **file_image, size_t *file_len);
+int flatgfa_seq_export_file(const uint8_t *text, size_t n, const char *filename);
+int flatgfa_seq_import(const uint8_t *file, size_t n, char **text, size_t *text_len);
+int flatgfa_seq_import_stream(const uint8_t *file, size_t n, flatgfa_sink_t sink, void *ctx);
+int flatgfa_seq_packed_info(const uint8_t *file, size_t n, uint64_t *n_bases, uint64_t *data_offset);
 /* format_float (ops/depth.rs:192-197); returns bytes written (no NUL). */
 int flatgfa_format_float(double x, int digits, char *out, int cap);
 
@@ -633,6 +655,23 @@ int flatgfa_dev_crush_count(const uint32_t *seg_seq, const uint8_t *seq_data, ui
                             void *stream, flatgfa_dev_crush_t **job, uint64_t *bytes_out, uint64_t *dropped_out);
 int flatgfa_dev_crush_fill(flatgfa_dev_crush_t *job, uint8_t *seq_out, uint32_t *seg_seq_out, void *stream);
 void flatgfa_dev_crush_free(flatgfa_dev_crush_t *job);
+/* The packed-sequence codec (flatgfa_seq_export, flatgfa_seq_import) on text and packed bytes in device memory; offsets and
+ * counts are 64-bit throughout.  flatgfa_dev_seq_pack_count classifies text[0, n) (at any alignment; n == 0 with NULL is
+ * valid), counts the kept bases, waits for `stream` once and returns a job in *job and the count in *n_bases; a byte that is
+ * neither whitespace nor one of A C T G: FLATGFA_ERR_PARSE with no job, flatgfa_last_error naming the smallest such offset.
+ * flatgfa_dev_seq_pack_fill enqueues on `stream` the packed bytes of "the carry, then the kept bases" into out (at any
+ * alignment): carry is -1 for none or a code 0..3 that takes the first low nibble (what a caller who cuts its text in pieces
+ * holds back from the piece before); out is u8[(*n_bases + (carry >= 0) + 1) / 2], every byte of it written exactly once,
+ * the unused last high nibble as 0, and nothing beside it.  It does not wait; the text must stay as it was until it has run.
+ * flatgfa_dev_seq_pack_free waits for the job's stream and releases its scratch.  flatgfa_dev_seq_unpack writes the letters of
+ * the first n_bases nibbles of `packed` into text_out u8[n_bases] (any alignment; 16-byte loads and stores where both are
+ * 16-byte aligned) and waits for `stream` once: a nibble above 3 among them is FLATGFA_ERR_PARSE, flatgfa_last_error naming
+ * the smallest such base index; the unused high nibble of an odd count's last byte is not looked at. */
+typedef struct flatgfa_dev_seq_pack flatgfa_dev_seq_pack_t;
+int flatgfa_dev_seq_pack_count(const uint8_t *text, uint64_t n, void *stream, flatgfa_dev_seq_pack_t **job, uint64_t *n_bases);
+int flatgfa_dev_seq_pack_fill(flatgfa_dev_seq_pack_t *job, int carry, uint8_t *out, void *stream);
+void flatgfa_dev_seq_pack_free(flatgfa_dev_seq_pack_t *job);
+int flatgfa_dev_seq_unpack(const uint8_t *packed, uint64_t n_bases, uint8_t *text_out, void *stream);
 /* The legend of flatten (flatten.py:13-19; flatgfa_flatten_legend) of a graph image in device memory: d_offset_out[s] = the
  * sum of g->seg_len before s, d_offset_out[n_segs] = the sum of all, in 64 bits (g->seg_len is required: FLATGFA_ERR_ARG when
  * NULL; the steps and spans are not read).  Enqueued on `stream`, which is waited for: the scan's scratch goes before the

@@ -98,6 +98,11 @@ SIGNATURES = {
     "flatgfa_flatten_fasta": (c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_flatten_bed": (c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_flatten_stream": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_void_p, c_void_p]),
+    "flatgfa_seq_export": (c_int, [c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_seq_export_file": (c_int, [c_char_p, c_size_t, c_char_p]),
+    "flatgfa_seq_import": (c_int, [c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_seq_import_stream": (c_int, [c_char_p, c_size_t, c_void_p, c_void_p]),
+    "flatgfa_seq_packed_info": (c_int, [c_char_p, c_size_t, POINTER(c_uint64), POINTER(c_uint64)]),
     "flatgfa_sharded_create": (c_void_p, [c_void_p, c_void_p, c_int, ctypes.c_uint]),
     "flatgfa_sharded_free": (None, [c_void_p]),
     "flatgfa_sharded_layout": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint32),
@@ -145,6 +150,10 @@ SIGNATURES = {
                                         POINTER(c_uint64), POINTER(c_uint64)]),
     "flatgfa_dev_crush_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "flatgfa_dev_crush_free": (None, [c_void_p]),
+    "flatgfa_dev_seq_pack_count": (c_int, [c_void_p, c_uint64, c_void_p, POINTER(c_void_p), POINTER(c_uint64)]),
+    "flatgfa_dev_seq_pack_fill": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "flatgfa_dev_seq_pack_free": (None, [c_void_p]),
+    "flatgfa_dev_seq_unpack": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p]),
     "flatgfa_dev_flatten_legend": (c_int, [POINTER(flatgfa_dev_graph_t), c_void_p, c_void_p]),
     "flatgfa_dev_status": (c_int, [c_void_p, c_void_p]),
     "flatgfa_dev_profile_enable": (None, [c_int]),

@@ -1,7 +1,7 @@
 // extern "C" surface of libflatgfa.so: the flatgfa-c drop-in (Part 1 of include/flatgfa.h)
 // plus the additive loaders, the depth queries and the host routes of the other features (Part 2).  The kernels live in the
 // .hip files -- depth_device.hip and its kin for depth, gaf_device.hip, gaf_lookup_device.hip, chop_device.hip,
-// extract_device.hip, topology_device.hip, flatten_device.hip, crush_device.hip for the rest -- and are reached through their headers; this file uses the HIP runtime
+// extract_device.hip, topology_device.hip, flatten_device.hip, crush_device.hip, seq_device.hip for the rest -- and are reached through their headers; this file uses the HIP runtime
 // API only.  Every host route that is not a depth query holds what it has on the device in one DevScope (below).
 #include <hip/hip_runtime_api.h>
 
@@ -40,6 +40,7 @@
 #include "interval_device.hpp"
 #include "flatten_device.hpp"
 #include "crush_device.hpp"
+#include "seq_device.hpp"
 
 using fgfa_dev::set_error;
 
@@ -167,7 +168,7 @@ int count_devices(const std::string &who, int *ndev) {
     return FLATGFA_OK;
 }
 
-// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree, flatten, crush -- holds on the device,
+// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree, flatten, crush, seq-export, seq-import -- holds on the device,
 // given back on every way out: the work stream is waited for, then the job, the events and the memory go, then the streams
 // return to the pool.  A thread that still copies on one of the streams is joined first: its joiner is declared after the scope.
 struct DevScope {
@@ -229,9 +230,10 @@ struct DevScope {
     }
 };
 
-// The device a call on `gfa` runs on (the one it is resident on, else 0), made current, with the work stream.
+// The device a call on `gfa` runs on (the one it is resident on, else 0), made current, with the work stream.  A route that
+// reads no graph (the packed-sequence codec) passes null: device 0, nothing resident.
 int open_scope(CStore *gfa, DevScope *sc, const char *what) {
-    {
+    if (gfa) {
         std::lock_guard<std::mutex> lk(gfa->dev_mu);
         if (gfa->on_device) sc->device = gfa->device, sc->resident = true;  // (beside the graph; it is not made resident)
     }
@@ -1913,6 +1915,154 @@ int flatgfa_crush(flatgfa_t gfa, flatgfa_t *out) {
     for (size_t i = 0; i < v.paths.len; ++i) h.paths[i] = fgfa::Path{v.paths[i].name, v.paths[i].steps, fgfa::Span{0, 0}};  // crush.py:27
     cs->view = h.view();
     *out = cs.release();
+    return FLATGFA_OK;
+}
+
+// ---- the packed-sequence codec (packedseq.rs, cli/cmds.rs:415-452) ----
+
+extern "C++" {
+namespace {
+// The size text and packed bytes are cut to for the device: 64 MiB, or what the tests ask for.
+size_t seq_chunk_bytes() {
+    if (const char *h = test_hook("FLATGFA_SEQ_CHUNK_BYTES")) return std::max<size_t>(1, strtoull(h, nullptr, 10));
+    return (size_t)64 << 20;
+}
+
+struct FreeBytes {
+    void operator()(void *p) const { free(p); }
+};
+struct FreePackJob {
+    void operator()(fgfa_dev::SeqPackJob *j) const { fgfa_dev::seq_pack_free(j); }
+};
+
+// The file image of `text` into a malloc'd buffer.  The text travels a chunk at a time, cut anywhere: a chunk that ends on a
+// low nibble (its bases and the carry in front of them are an odd number) and is not the last keeps its final byte back, and
+// that byte's low nibble is the carry in front of the next chunk.  The packed bytes land where they stay.
+int seq_export_image(const uint8_t *text, size_t n, uint8_t **image, size_t *image_len) {
+    DevScope sc;
+    if (int rc = open_scope(nullptr, &sc, "seq-export")) return rc;
+    hipStream_t st = sc.stream;
+    const size_t chunk = seq_chunk_bytes(), room = std::min(n, chunk);
+    uint8_t *d_text = nullptr, *d_out = nullptr;
+    CAPI_HIP(sc.alloc(&d_text, room));
+    CAPI_HIP(sc.alloc(&d_out, room / 2 + 2));
+    std::unique_ptr<uint8_t, FreeBytes> buf((uint8_t *)malloc(fgfa::kPackedSeqHeader + n / 2 + 2));
+    if (!buf) { set_error("seq-export: out of memory"); return FLATGFA_ERR_IO; }
+    size_t at = fgfa::kPackedSeqHeader;
+    uint64_t bases = 0;
+    int carry = fgfa_dev::kSeqNoCarry;
+    for (size_t a = 0; a < n;) {
+        const size_t m = std::min(chunk, n - a);
+        const bool last = a + m == n;
+        CAPI_HIP(fgfa_dev::staged_copy(d_text, text + a, m, hipMemcpyHostToDevice, st));
+        std::unique_ptr<fgfa_dev::SeqPackJob, FreePackJob> job(fgfa_dev::seq_pack_new());
+        uint64_t kept = 0;
+        if (int rc = fgfa_dev::seq_pack_count(job.get(), d_text, m, a, st, &kept)) return rc;
+        if (int rc = fgfa_dev::seq_pack_fill(job.get(), carry, d_out, st)) return rc;
+        const uint64_t logical = kept + (carry >= 0 ? 1 : 0), bytes = fgfa_dev::seq_packed_bytes(logical);
+        if (bytes) CAPI_HIP(fgfa_dev::staged_copy(buf.get() + at, d_out, bytes, hipMemcpyDeviceToHost, st));
+        if (!last && (logical & 1)) {
+            carry = buf.get()[at + bytes - 1] & 0xF;
+            at += bytes - 1;
+        } else {
+            carry = fgfa_dev::kSeqNoCarry;
+            at += bytes;
+        }
+        bases += kept;
+        a += m;
+    }
+    if (at != fgfa::kPackedSeqHeader + fgfa_dev::seq_packed_bytes(bases)) {
+        set_error("seq-export: internal: the packed bytes are not as many as the bases counted");
+        return FLATGFA_ERR_HIP;
+    }
+    fgfa::packed_seq_header(bases, buf.get());
+    *image = buf.release();
+    *image_len = at;
+    return FLATGFA_OK;
+}
+
+// The bases of a packed file in device memory (*d_text, the scope's): the header is checked before any device work, the data
+// travel a chunk at a time, cut on even base indices, and every nibble is checked before a base is delivered.
+int seq_import_device(const uint8_t *file, size_t n, DevScope *sc, uint8_t **d_text, uint64_t *n_bases) {
+    size_t off = 0;
+    std::string err;
+    if (!fgfa::parse_packed_seq(file, n, n_bases, &off, &err)) { set_error(err); return FLATGFA_ERR_PARSE; }
+    if (int rc = open_scope(nullptr, sc, "seq-import")) return rc;
+    const uint64_t n_bytes = fgfa_dev::seq_packed_bytes(*n_bases);
+    const size_t chunk = seq_chunk_bytes();
+    uint8_t *d_packed = nullptr;
+    CAPI_HIP(sc->alloc(&d_packed, std::min<uint64_t>(n_bytes, chunk)));
+    CAPI_HIP(sc->alloc(d_text, *n_bases));
+    for (uint64_t a = 0; a < n_bytes;) {
+        const uint64_t m = std::min<uint64_t>(chunk, n_bytes - a), here = std::min<uint64_t>(2 * m, *n_bases - 2 * a);
+        CAPI_HIP(fgfa_dev::staged_copy(d_packed, file + off + a, m, hipMemcpyHostToDevice, sc->stream));
+        if (int rc = fgfa_dev::seq_unpack(d_packed, here, 2 * a, *d_text + 2 * a, sc->stream)) return rc;
+        a += m;
+    }
+    return FLATGFA_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int flatgfa_seq_packed_info(const uint8_t *file, size_t n, uint64_t *n_bases, uint64_t *data_offset) {
+    if ((!file && n) || !n_bases || !data_offset) { set_error("flatgfa_seq_packed_info: NULL argument"); return FLATGFA_ERR_ARG; }
+    size_t off = 0;
+    std::string err;
+    if (!fgfa::parse_packed_seq(file ? file : (const uint8_t *)"", n, n_bases, &off, &err)) { set_error(err); return FLATGFA_ERR_PARSE; }
+    *data_offset = off;
+    return FLATGFA_OK;
+}
+
+int flatgfa_seq_export(const uint8_t *text, size_t n, uint8_t **file_image, size_t *file_len) {
+    if (file_image) *file_image = nullptr;
+    if (file_len) *file_len = 0;
+    if ((!text && n) || !file_image || !file_len) { set_error("flatgfa_seq_export: NULL argument"); return FLATGFA_ERR_ARG; }
+    return seq_export_image(text, n, file_image, file_len);
+}
+
+int flatgfa_seq_export_file(const uint8_t *text, size_t n, const char *filename) {
+    if ((!text && n) || !filename) { set_error("flatgfa_seq_export_file: NULL argument"); return FLATGFA_ERR_ARG; }
+    uint8_t *image = nullptr;
+    size_t len = 0;
+    if (int rc = seq_export_image(text, n, &image, &len)) return rc;  // (no file then)
+    std::unique_ptr<uint8_t, FreeBytes> hold(image);
+    FILE *f = fopen(filename, "wb");
+    if (!f || fwrite(image, 1, len, f) != len || fclose(f)) {
+        set_error(std::string("seq-export: cannot write ") + filename);
+        return FLATGFA_ERR_IO;
+    }
+    return FLATGFA_OK;
+}
+
+int flatgfa_seq_import(const uint8_t *file, size_t n, char **text, size_t *text_len) {
+    if (text) *text = nullptr;
+    if (text_len) *text_len = 0;
+    if ((!file && n) || !text || !text_len) { set_error("flatgfa_seq_import: NULL argument"); return FLATGFA_ERR_ARG; }
+    DevScope sc;
+    uint8_t *d_text = nullptr;
+    uint64_t bases = 0;
+    if (int rc = seq_import_device(file ? file : (const uint8_t *)"", n, &sc, &d_text, &bases)) return rc;
+    std::unique_ptr<char, FreeBytes> buf((char *)malloc(bases + 1));
+    if (!buf) { set_error("seq-import: out of memory"); return FLATGFA_ERR_IO; }
+    if (bases) CAPI_HIP(fgfa_dev::staged_copy(buf.get(), d_text, bases, hipMemcpyDeviceToHost, sc.stream));
+    buf.get()[bases] = 0;
+    *text = buf.release();
+    *text_len = bases;
+    return FLATGFA_OK;
+}
+
+int flatgfa_seq_import_stream(const uint8_t *file, size_t n, flatgfa_sink_t sink, void *ctx) {
+    if ((!file && n) || !sink) { set_error("flatgfa_seq_import_stream: NULL argument"); return FLATGFA_ERR_ARG; }
+    DevScope sc;
+    uint8_t *d_text = nullptr;
+    uint64_t bases = 0;
+    if (int rc = seq_import_device(file ? file : (const uint8_t *)"", n, &sc, &d_text, &bases)) return rc;
+    std::vector<char> piece(std::min<uint64_t>(bases, std::min<size_t>(seq_chunk_bytes(), (size_t)64 << 20)));
+    for (uint64_t a = 0; a < bases; a += piece.size()) {
+        const size_t m = std::min<uint64_t>(piece.size(), bases - a);
+        CAPI_HIP(fgfa_dev::staged_copy(piece.data(), d_text + a, m, hipMemcpyDeviceToHost, sc.stream));
+        if (sink(ctx, piece.data(), m)) { set_error("seq-import: the sink stopped the stream"); return FLATGFA_ERR_IO; }
+    }
     return FLATGFA_OK;
 }
 

@@ -6,12 +6,15 @@
 //            | window-depth PATH SIZE | window-depth-all SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l] | inject -b BED [-l] | crush
 //            | extract -n NAME -c DIST [-d N] [-e N] | position -p PATH,OFFSET,+ | validate | degree
 //            | flatten [-n NAME] [-f FASTA] [-b BED]
+//   fgfa seq-export INPUT OUTPUT | fgfa seq-import FILE        (no graph is read)
 //
 // With no -i/-I the GFA text is read from stdin; with no COMMAND the graph is written out
 // (-o binary, -O text, otherwise text on stdout).  `depth` output is byte-identical to the
 // reference's and is computed on the GPU, as are `matrix` (cmds.rs:453-475), `position` (cmds.rs:105-152), and `chop`
 // (cli/main.rs:139-159) and `extract` (cmds.rs:174-215), whose graph is written out as the input graph would be; `validate` and `degree` print what slow_odgi's validate.py and
-// degree.py print, `crush` writes out the graph of its crush.py, `flatten` what its flatten.py prints (or, with -f / -b, what `odgi flatten` writes to those files).  Everything else in the reference CLI is out of scope.
+// degree.py print, `crush` writes out the graph of its crush.py, `flatten` what its flatten.py prints (or, with -f / -b, what `odgi flatten` writes to those files).
+// `seq-export` and `seq-import` (cmds.rs:415-452) are the packed-sequence codec of packedseq.rs, on the GPU as well; like the
+// reference's they take files, not a graph, and stdin is never read.  Of the reference CLI that leaves `bench` and `bed-intersect`.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -121,7 +124,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "crush" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten";
+    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "crush" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten" || cmd == "seq-export" || cmd == "seq-import";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -133,6 +136,49 @@ int main(int argc, char **argv) {
     if (const char *k = getenv("FLATGFA_KEEP_HOST_MEMORY"); !(k && k[0] == '0')) (void)flatgfa_keep_host_memory(1);
     std::thread warm;
     if (wants_device && !getenv("FLATGFA_NO_WARM")) warm = std::thread([] { (void)flatgfa_warm_device(0); });
+
+    // cli/cmds.rs:415-452: fgfa seq-export INPUT OUTPUT, fgfa seq-import FILE -- before any graph is loaded: neither reads one
+    if (cmd == "seq-export" || cmd == "seq-import") {
+        const bool exporting = cmd == "seq-export";
+        int rc = 0;
+        if (argc - i != (exporting ? 2 : 1)) {
+            fprintf(stderr, exporting ? "usage: fgfa seq-export INPUT OUTPUT\n" : "usage: fgfa seq-import FILE\n");
+            rc = 2;
+        } else {
+            const int fd = open(argv[i], O_RDONLY);
+            struct stat sb;
+            void *m = nullptr;
+            size_t n = 0;
+            if (fd < 0 || fstat(fd, &sb) != 0) {
+                fprintf(stderr, "fgfa: cannot open %s\n", argv[i]);
+                rc = 1;
+            } else if ((n = (size_t)sb.st_size) && (m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0)) == MAP_FAILED) {
+                fprintf(stderr, "fgfa: cannot map %s\n", argv[i]);
+                rc = 1;
+            }
+            if (fd >= 0) close(fd);
+            if (!rc && m) (void)madvise(m, n, MADV_SEQUENTIAL);
+            if (!rc && exporting) {
+                if (flatgfa_seq_export_file((const uint8_t *)m, n, argv[i + 1])) rc = die("seq-export");
+            } else if (!rc) {
+                // the bases, then one newline (cmds.rs:427-429); checked whole before a byte is printed
+                char *text = nullptr;
+                size_t len = 0;
+                if (flatgfa_seq_import((const uint8_t *)m, n, &text, &len)) {
+                    rc = die("seq-import");
+                } else {
+                    write_all(text, len);
+                    write_all("\n", 1);
+                }
+                flatgfa_free_text(text);
+            }
+        }
+        if (warm.joinable()) warm.join();
+        fflush(stdout);
+        fflush(stderr);
+        if (!test_hook("FLATGFA_SLOW_EXIT")) _exit(rc);
+        return rc;
+    }
 
     flatgfa_t g;
     if (in_flat) {

@@ -1323,4 +1323,42 @@ void cut_lines(const uint8_t *text, size_t len, size_t target, std::vector<std::
     }
 }
 
+// ---- the packed-sequence file (packedseq.rs) ----
+static void put_le64(uint8_t *p, uint64_t v) {
+    for (int k = 0; k < 8; ++k) p[k] = (uint8_t)(v >> (8 * k));
+}
+static uint64_t get_le64(const uint8_t *p) {
+    uint64_t v = 0;
+    for (int k = 0; k < 8; ++k) v |= (uint64_t)p[k] << (8 * k);
+    return v;
+}
+
+void packed_seq_header(uint64_t n_bases, uint8_t out[kPackedSeqHeader]) {
+    const uint64_t len = n_bases / 2 + (n_bases & 1);
+    put_le64(out, kPackedSeqMagic);
+    put_le64(out + 8, len);
+    put_le64(out + 16, len);
+    out[24] = n_bases & 1 ? 0 : 1;
+}
+
+bool parse_packed_seq(const uint8_t *file, size_t n, uint64_t *n_bases, size_t *data_offset, std::string *err) {
+    if (n < kPackedSeqHeader) {
+        *err = "seq-import: the file is shorter than the " + std::to_string(kPackedSeqHeader) + "-byte header";
+        return false;
+    }
+    const uint64_t magic = get_le64(file), len = get_le64(file + 8), cap = get_le64(file + 16);
+    const uint8_t hne = file[24];
+    if (magic != kPackedSeqMagic) { *err = "seq-import: the magic number is " + std::to_string(magic) + ", not 18"; return false; }
+    if (hne > 1) { *err = "seq-import: high_nibble_end is " + std::to_string(hne) + ", not 0 or 1"; return false; }
+    if (cap < len) { *err = "seq-import: the capacity " + std::to_string(cap) + " is below the length " + std::to_string(len); return false; }
+    if (cap > n - kPackedSeqHeader) {
+        *err = "seq-import: the header promises " + std::to_string(cap) + " bytes and " + std::to_string(n - kPackedSeqHeader) + " follow it";
+        return false;
+    }
+    if (len == 0 && hne == 0) { *err = "seq-import: no data bytes, but the last base is said to be a low nibble"; return false; }
+    *n_bases = 2 * len - (1 - hne);
+    *data_offset = kPackedSeqHeader;
+    return true;
+}
+
 }  // namespace fgfa

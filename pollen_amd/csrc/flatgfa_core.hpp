@@ -315,6 +315,18 @@ void emit_degree(const View &v, const uint64_t *degree, std::string *out);
 // at all: no piece).
 void cut_lines(const uint8_t *text, size_t len, size_t target, std::vector<std::pair<size_t, size_t>> *pieces);
 
+// The packed-sequence file (packedseq.rs:108-147): a 25-byte header without padding -- u64 magic 0x12,
+// u64 len, u64 capacity, u8 high_nibble_end, little-endian -- then `len` data bytes of two bases each.
+constexpr size_t kPackedSeqHeader = 25;
+constexpr uint64_t kPackedSeqMagic = 0x12;
+// The header of n_bases bases, as the reference's writer makes it: len = capacity = the data bytes, high_nibble_end = 1 for an
+// even count (0 included).
+void packed_seq_header(uint64_t n_bases, uint8_t out[kPackedSeqHeader]);
+// What the reference's reader panics on, as false with *err: a file shorter than the header, a wrong magic, high_nibble_end
+// not 0 or 1, capacity < len, fewer than `capacity` bytes behind the header, len == 0 with high_nibble_end == 0 (a length of
+// -1).  Otherwise *n_bases = 2 len - (1 - high_nibble_end) and *data_offset = 25; bytes behind the data are ignored.
+bool parse_packed_seq(const uint8_t *file, size_t n, uint64_t *n_bases, size_t *data_offset, std::string *err);
+
 // The synthetic-graph generator of SURVEY.md 8(d) (spec: oracle/synth.py).
 // model 0 = pangenome, 1 = uniform, 2 = chromosome, 3 = haplotype (oracle/synth.py has the spec).
 void synth_store(uint64_t seed, uint32_t S, uint32_t P, uint32_t L, int model, bool with_seq, Store *out);

@@ -413,6 +413,45 @@ def crush(graph: DeviceGraph, seg_seq, seq_data, stream=None):
         return new, seq_out, seg_seq_out
 
 
+def seq_pack(text, stream=None, carry: int = -1):
+    """The packed-sequence codec's pack (packedseq.rs) of nucleotide text on the device: text is a uint8 CUDA tensor, at any
+    alignment (a slice will do).  Returns (packed, n_bases): a uint8 tensor of (n_bases + (carry >= 0) + 1) // 2 bytes -- two
+    bases a byte, A 0, C 1, T 2, G 3, the even base in the low nibble -- and the number of bases kept.  Whitespace is dropped;
+    another byte that is not one of A C T G raises FlatGFAError (code -7) naming the smallest offending offset.  carry: a code
+    0..3 that goes in front of the bases (what a caller that cuts its text in pieces held back from the piece before), or -1.
+    Waits for the stream once, to learn the count (flatgfa_dev_seq_pack_count); the rest is enqueued on it (torch's current
+    stream by default)."""
+    torch = _torch()
+    assert text.dtype == torch.uint8 and text.is_cuda and text.is_contiguous()
+    with torch.cuda.device(text.device):
+        st = stream if stream is not None else torch.cuda.current_stream(text.device)
+        job, kept = ctypes.c_void_p(), ctypes.c_uint64()
+        L = _lib.lib()
+        with torch.cuda.stream(st):  # (the output is the stream's: torch's allocator may hand its memory on behind it)
+            _check(L.flatgfa_dev_seq_pack_count(_ptr(text), int(text.numel()), ctypes.c_void_p(st.cuda_stream), ctypes.byref(job), ctypes.byref(kept)),
+                   "dev_seq_pack_count")
+            try:
+                packed = torch.empty((kept.value + (1 if carry >= 0 else 0) + 1) // 2, dtype=torch.uint8, device=text.device)
+                _check(L.flatgfa_dev_seq_pack_fill(job, int(carry), _ptr(packed), ctypes.c_void_p(st.cuda_stream)), "dev_seq_pack_fill")
+            finally:
+                L.flatgfa_dev_seq_pack_free(job)  # (waits for the fill, on this stream only)
+        return packed, kept.value
+
+
+def seq_unpack(packed, n_bases: int, stream=None):
+    """The letters of the first n_bases nibbles of `packed` (a uint8 CUDA tensor of at least (n_bases + 1) // 2 bytes) as a
+    uint8 tensor, on the device.  A nibble above 3 among them raises FlatGFAError (code -7) naming the smallest such base
+    index; the unused high nibble of an odd count's last byte is not looked at.  Waits for the stream once, for that answer."""
+    torch = _torch()
+    assert packed.dtype == torch.uint8 and packed.is_cuda and packed.is_contiguous() and packed.numel() >= (n_bases + 1) // 2
+    with torch.cuda.device(packed.device):
+        st = stream if stream is not None else torch.cuda.current_stream(packed.device)
+        with torch.cuda.stream(st):
+            text = torch.empty(n_bases, dtype=torch.uint8, device=packed.device)
+            _check(_lib.lib().flatgfa_dev_seq_unpack(_ptr(packed), int(n_bases), _ptr(text), ctypes.c_void_p(st.cuda_stream)), "dev_seq_unpack")
+        return text
+
+
 def profile_enable(on: bool) -> None:
     _lib.lib().flatgfa_dev_profile_enable(1 if on else 0)
 

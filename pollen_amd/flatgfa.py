@@ -756,6 +756,46 @@ def synth(seed: int, n_segs: int, n_paths: int, steps_per_path: int, model: str 
     return FlatGFA(_lib.lib().flatgfa_synth(seed, n_segs, n_paths, steps_per_path, m, with_seq))
 
 
+# ---- the packed-sequence codec (flatgfa/src/packedseq.rs; `fgfa seq-export`, `fgfa seq-import`) ----
+def seq_export(text: bytes) -> bytes:
+    """`fgfa seq-export`: the packed file image of nucleotide text, made on the GPU -- a 25-byte header, then two bases a byte
+    (A 0, C 1, T 2, G 3; the even base in the low nibble).  Whitespace is dropped; any other byte that is not one of A C T G
+    raises FlatGFAError (code -7) naming the smallest offending offset."""
+    text = bytes(text)
+    p, n = ctypes.c_void_p(), ctypes.c_size_t()
+    _check(_lib.lib().flatgfa_seq_export(text, len(text), ctypes.byref(p), ctypes.byref(n)), "seq_export")
+    return _take_text(p, n)
+
+
+def seq_export_file(text: bytes, filename: Union[str, os.PathLike]) -> None:
+    """seq_export into a file; on an error no file is made."""
+    text = bytes(text)
+    _check(_lib.lib().flatgfa_seq_export_file(text, len(text), os.fsencode(filename)), "seq_export_file")
+
+
+def seq_import(packed: bytes) -> bytes:
+    """`fgfa seq-import` without its newline: the bases of a packed file image, unpacked on the GPU.  A malformed header or a
+    nibble above 3 raises FlatGFAError (code -7)."""
+    packed = bytes(packed)
+    p, n = ctypes.c_void_p(), ctypes.c_size_t()
+    _check(_lib.lib().flatgfa_seq_import(packed, len(packed), ctypes.byref(p), ctypes.byref(n)), "seq_import")
+    return _take_text(p, n)
+
+
+def seq_import_file(filename: Union[str, os.PathLike]) -> bytes:
+    """seq_import of a file's contents."""
+    with open(filename, "rb") as f:
+        return seq_import(f.read())
+
+
+def seq_packed_info(packed: bytes) -> Tuple[int, int]:
+    """(the number of bases, the offset of the data bytes) of a packed file image: the header checks alone, on the host."""
+    packed = bytes(packed)
+    bases, off = ctypes.c_uint64(), ctypes.c_uint64()
+    _check(_lib.lib().flatgfa_seq_packed_info(packed, len(packed), ctypes.byref(bases), ctypes.byref(off)), "seq_packed_info")
+    return bases.value, off.value
+
+
 def format_float(x: float, digits: int) -> str:
     buf = ctypes.create_string_buffer(600)
     n = _lib.lib().flatgfa_format_float(x, digits, buf, 600)
