@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -281,6 +282,16 @@ struct flatgfa_dev_plan {
     std::vector<MarksJob> marks;       // one job per range / path group of `fast` that wants marks (fast itself, then more[0 ..]); empty once all are installed
     bool marks_to_start = false;       // ... whose jobs are enqueued by the first call (or status, or describe) behind the plan's creation: a caller that only wants the first answer never pays for them
     bool check_facts = false;          // FLATGFA_CHECK_NO_CLAIM=1: every call first looks again at what the plan took for granted about the step values
+    // the run-length image of the step array (run_poll): the plan's reference to the one its device's plans of this array share,
+    // the entries each of its own items reads, and where it stands
+    struct RunShare *run = nullptr;
+    void *run_item_ent = nullptr;
+    void *run_room = nullptr;          // (until the image is installed) the records k_scan_runs will put into each sub-bucket, counted
+    hipEvent_t run_items_done = nullptr;
+    int run_state = 0;                 // 0: not looked at yet, 1: the image is being made, 2: ... the items' entries, 3: installed, -1: none
+    const char *run_off = "";          // ... and why not
+    bool run_show = false;             // the description says which (plans the image is meant for by size, or the hook set)
+    int run_hook = -1;                 // FLATGFA_RUN_IMAGE as it was when the plan was made (0, 1; -1: unset)
 };
 
 // The Infinity Cache (256 MiB on MI355X) is one per device: what the plans of a process keep resident in it is
@@ -365,10 +376,218 @@ static void release_cache_claim(flatgfa_dev_plan_t *pl) {
     pl->cache_claim_shared = false;
 }
 
+// The device's low-priority side stream (one per device for the whole process: creating a stream costs as much as the first
+// answer): what is made behind a plan's first call -- the per-block no-claim marks, the run-length image -- is made there.
+// The lowest priority the device has: these kernels read the steps several more times, and a query that runs beside them
+// should not wait for that.  The plan's device must be current.
+static hipStream_t side_stream(flatgfa_dev_plan_t *pl) {
+    if (pl->side) return pl->side;
+    static std::mutex mu;
+    static hipStream_t pool[64] = {};
+    std::lock_guard<std::mutex> lk(mu);
+    hipStream_t &slot = pool[pl->device >= 0 && pl->device < 64 ? pl->device : 0];
+    if (!slot) {
+        int least = 0, greatest = 0;
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = 0; }
+        if (hipStreamCreateWithPriority(&slot, hipStreamNonBlocking, least) != hipSuccess) { (void)hipGetLastError(); slot = nullptr; return nullptr; }
+    }
+    pl->side = slot;
+    return slot;
+}
+
+// ---- the run-length image of the steps ----
+// One image per device and resident step array, whoever's plan asked first: the lanes of a pipeline and a stand-alone plan
+// on the same graph hold its 8 bytes per run once.  Reference-counted like the claim on the Infinity Cache; the last plan to
+// go frees it.  A plan whose steps were declared changed takes the image off the list (the plans that still hold it go on
+// with it until they are told too) and asks again: the next one is made from the steps as they are.
+struct RunShare {
+    int device;
+    const uint32_t *steps;
+    RunImage *img;
+    hipStream_t side;
+    int users;
+    bool listed;
+    bool any_ratio;  // (FLATGFA_RUN_IMAGE=1 of the plan that asked first: no limit on entries per step)
+};
+static std::mutex g_run_mu;
+static std::vector<RunShare *> g_run_shares;
+// Side-stream work of the image (its kernels, a plan's k_item_entries / k_run_room) enqueued on a device and not known to be
+// done.  A call's k_scan deals its items to the workgroups as they get to them: beside kernels that take CUs from it the deal
+// goes lopsided, and a sub-bucket sized on undisturbed calls can run over (seen: one in a few runs of the benchmark's extras,
+// which enqueue a second graph's first call while the first graph's image is being made).  So the image is made BETWEEN calls:
+// a call issued while such work is pending waits for it first -- up to two milliseconds, once per image.
+static std::atomic<int> g_side_pending[64];
+constexpr uint64_t kRunImageReserve = 1ull << 30;  // device memory the image must leave free
+static void side_work_wait(int device) {
+    if (device < 0 || device >= 64 || !g_side_pending[device].load(std::memory_order_acquire)) return;
+    std::lock_guard<std::mutex> lk(g_run_mu);
+    g_side_pending[device].store(0, std::memory_order_release);
+    hipStream_t side = nullptr;
+    for (RunShare *sh : g_run_shares) {
+        if (sh->device != device) continue;
+        side = sh->side;
+        (void)run_image_poll(sh->img, sh->side, true, kRunImageReserve, sh->any_ratio);  // (count, then write: the host stands between them)
+    }
+    if (side) (void)hipStreamSynchronize(side);
+}
+static void side_work_enqueued(int device) {
+    if (device >= 0 && device < 64) g_side_pending[device].store(1, std::memory_order_release);
+}
+constexpr bool kRunImageDefault = true;        // plans that qualify get the image without being asked (FLATGFA_RUN_IMAGE=0|1 decides otherwise)
+
+static void run_release(flatgfa_dev_plan_t *pl, bool steps_changed) {
+    if (pl->run_items_done) {
+        (void)hipEventSynchronize(pl->run_items_done);
+        (void)hipEventDestroy(pl->run_items_done);
+        pl->run_items_done = nullptr;
+    }
+    if (pl->run_item_ent) (void)hipFree(pl->run_item_ent);
+    if (pl->run_room) (void)hipFree(pl->run_room);
+    pl->run_item_ent = pl->run_room = nullptr;
+    pl->fast.run_ent = pl->fast.run_item_ent = nullptr;
+    if (RunShare *sh = pl->run) {
+        std::lock_guard<std::mutex> lk(g_run_mu);
+        sh->users -= 1;
+        if (sh->listed && (steps_changed || sh->users == 0)) {
+            g_run_shares.erase(std::find(g_run_shares.begin(), g_run_shares.end(), sh));
+            sh->listed = false;
+        }
+        if (sh->users == 0) {
+            run_image_free(sh->img, sh->side);
+            delete sh;
+        }
+        pl->run = nullptr;
+    }
+    pl->run_state = 0;
+    pl->run_off = "";
+}
+
+// Which plans read the image: decided by rule, not by a timed trial.
+static const char *run_image_refused(flatgfa_dev_plan_t *pl) {
+    const FastPlan &f = pl->fast;
+    const flatgfa_dev_graph_t &g = pl->g;
+    const bool hook = pl->run_hook >= 0, forced = pl->run_hook == 1;
+    const bool by_size = (uint64_t)g.n_steps * 4 >= (64ull << 20);  // (the floor of the cache claim: small graphs run what they always ran)
+    pl->run_show = by_size || hook;
+    if (pl->run_hook == 0) return "hook";
+    if (!forced && !kRunImageDefault) return "default";
+    if (!forced && !by_size) return "small";
+    if (!f.eligible) return "atomic";
+    if (!f.tagged) return "untagged";
+    if (f.n_more || f.n_groups > 1 || f.seg_base || f.n_range != g.n_segs) return "ranges";
+    if (f.packed) return "packed";
+    if (f.dense) return "dense";
+    if (f.n_short || f.n_medium || f.n_tiny) return "short_paths";
+    if (!f.n_items) return "no_items";
+    if (((uint64_t)f.n_items + std::min(f.n_items, f.n_slots) - 1) / std::min(f.n_items, f.n_slots) > f.tag_limit) return "items";  // (k_scan_runs deals the items evenly: a workgroup's share must fit its private tags)
+    if (f.cflags) return "marks";
+    if (pl->check_facts) return "check_no_claim";
+    if (f.dbg) return "debug";
+    if (f.wb < 10 || f.wb > 13) return "windows";  // (a run of up to 1024 steps must fit a record's length field, and cross one window edge at most)
+    // spans that overlap: the image would be right (an item's entries are clipped to its steps), but such plans are rare and untested here
+    std::vector<std::pair<uint32_t, uint32_t>> spans;
+    for (size_t p = 0; p < pl->hb.size(); ++p)
+        if (pl->he[p] > pl->hb[p]) spans.push_back({pl->hb[p], pl->he[p]});
+    std::sort(spans.begin(), spans.end());
+    for (size_t i = 1; i < spans.size(); ++i)
+        if (spans[i].first < spans[i - 1].second) return "overlap";
+    return nullptr;
+}
+
+// Moves the plan's image on (never blocks unless `wait`): asks for the shared image, then for its own items' entries, then
+// installs both.  Called between two calls of the plan, once its no-claim marks are settled.  The image's kernels are first
+// enqueued at the END of a call (`behind`: the stream that call's kernels went to, which the side stream then waits for -- the
+// answer of the call that starts them is not slowed by them), or where no call is in flight (`may_start`: status, describe).
+static void run_poll(flatgfa_dev_plan_t *pl, bool wait, bool may_start, hipStream_t behind = nullptr) {
+    if (pl->run_state == 3 || pl->run_state < 0) return;
+    if (pl->run_state == 0 && !may_start) return;
+    DeviceGuard guard;
+    if (guard.dev < 0 || !guard.switch_to(pl->device)) { (void)hipGetLastError(); return; }
+    const auto give_up = [&](const char *why) {
+        run_release(pl, false);
+        pl->run_state = -1;
+        pl->run_off = why;
+    };
+    if (pl->run_state == 0) {
+        if (const char *why = run_image_refused(pl)) { give_up(why); return; }
+        hipStream_t side = side_stream(pl);
+        if (!side) { give_up("error"); return; }
+        std::lock_guard<std::mutex> lk(g_run_mu);
+        if (behind) {
+            hipEvent_t after = nullptr;
+            if (hipEventCreateWithFlags(&after, hipEventDisableTiming) == hipSuccess) {
+                if (hipEventRecord(after, behind) == hipSuccess) (void)hipStreamWaitEvent(side, after, 0);
+                (void)hipEventDestroy(after);  // (released once it has completed)
+            }
+            (void)hipGetLastError();
+        }
+        for (RunShare *sh : g_run_shares)
+            if (sh->device == pl->device && sh->steps == pl->g.steps) pl->run = sh;
+        if (!pl->run) {
+            pl->run = new RunShare{pl->device, pl->g.steps, run_image_start(pl->g, side), side, 0, true, pl->run_hook == 1};
+            g_run_shares.push_back(pl->run);
+            side_work_enqueued(pl->device);
+        }
+        pl->run->users += 1;
+        pl->run_state = 1;
+    }
+    if (pl->run_state == 1) {
+        int r;
+        {
+            std::lock_guard<std::mutex> lk(g_run_mu);
+            r = run_image_poll(pl->run->img, pl->run->side, wait, kRunImageReserve, pl->run->any_ratio);  // (the hook waives both rules of size: the floor, and an entry for four steps at most)
+            side_work_enqueued(pl->device);  // (the image's second stage, the plan's items)
+            if (r > 0 && !run_items_start(pl->fast, pl->run->img, pl->run->side, &pl->run_item_ent, &pl->run_room, &pl->run_items_done)) r = -2;
+        }
+        if (r == 0) return;
+        if (r < 0) { give_up(r == -2 ? "error" : run_image_why(pl->run->img)); return; }
+        pl->run_state = 2;
+    }
+    if (pl->run_state == 2) {
+        const hipError_t e = wait ? hipEventSynchronize(pl->run_items_done) : hipEventQuery(pl->run_items_done);
+        if (e == hipErrorNotReady) { (void)hipGetLastError(); return; }
+        if (e != hipSuccess) { (void)hipGetLastError(); give_up("error"); return; }
+        // k_scan_runs deals the items to the workgroups in a fixed order, so what it puts into every sub-bucket is known now,
+        // for every call to come: the image is installed in a plan whose sub-buckets hold it.  (They were sized on calls of
+        // k_scan, with headroom; where that is not enough they are made larger here -- with the device drained, since calls
+        // of the plan may be in flight -- or the plan keeps k_scan.)
+        const uint32_t room = run_room_needed(pl->fast, pl->run_room);
+        (void)hipFree(pl->run_room);
+        pl->run_room = nullptr;
+        if (room == ~0u) { give_up("error"); return; }
+        if (room > pl->fast.cap) {
+            (void)hipDeviceSynchronize();
+            for (int k = 0; k < 3 && room > pl->fast.cap && pl->fast.eligible && !pl->fast.cap_forced; ++k)
+                if (!fast_plan_grow(&pl->fast)) { pl->fast.eligible = true; break; }  // (a plan that cannot grow keeps k_scan and its buckets)
+            if (room > pl->fast.cap) { give_up("room"); return; }
+        }
+        // plain reads (they allocate in the Infinity Cache) while image, records and results fit what the steps' claim is budgeted against
+        const int64_t traffic = (int64_t)run_image_bytes(pl->run->img) + 8ll * (int64_t)pl->g.n_segs + 8ll * (int64_t)pl->fast.est_records;
+        const char *mall = getenv("FLATGFA_MALL_MB");
+        const bool nt = traffic > (244ll << 20) || (mall && strtoull(mall, nullptr, 10) == 0);
+        run_image_install(&pl->fast, pl->run->img, pl->run_item_ent, nt);
+        pl->run_state = 3;
+    }
+}
+
 // The per-block no-claim marks are made on a stream of the plan's own, behind its creation:
 // (wait) for the jobs that are there, and install what they found.  Called between two calls of the plan.
 static void marks_start(flatgfa_dev_plan_t *pl);
-static void marks_poll(flatgfa_dev_plan_t *pl, bool wait) {
+static void marks_jobs_poll(flatgfa_dev_plan_t *pl, bool wait);
+static void marks_poll(flatgfa_dev_plan_t *pl, bool wait, bool before_a_call = false) {
+    if (before_a_call) {  // (no call runs beside the image's kernels: see g_side_pending)
+        side_work_wait(pl->device);
+        wait = wait || pl->run_state > 0;
+    }
+    marks_jobs_poll(pl, wait && !before_a_call);
+    // ... and behind them, for a plan that neither has nor waits for marks, the run-length image of the steps
+    if (pl->marks.empty() && !pl->marks_to_start) run_poll(pl, wait, !before_a_call);
+}
+// behind a call's kernels on `stream`: the image's kernels, if they are still to be started
+static void run_start_behind(flatgfa_dev_plan_t *pl, hipStream_t stream) {
+    if (pl->run_state == 0 && pl->marks.empty() && !pl->marks_to_start) run_poll(pl, false, true, stream);
+}
+static void marks_jobs_poll(flatgfa_dev_plan_t *pl, bool wait) {
     if (pl->marks_to_start) {
         pl->marks_to_start = false;
         marks_start(pl);
@@ -390,19 +609,7 @@ static void marks_start(flatgfa_dev_plan_t *pl) {
     // (the job's scratch and stream belong to the plan's device, whatever device the calling thread has current)
     DeviceGuard guard;
     if (guard.dev < 0 || !guard.switch_to(pl->device)) { (void)hipGetLastError(); return; }
-    if (!pl->side) {  // (one such stream per device for the whole process: creating a stream costs as much as the first answer)
-        static std::mutex mu;
-        static hipStream_t pool[64] = {};
-        std::lock_guard<std::mutex> lk(mu);
-        hipStream_t &slot = pool[pl->device >= 0 && pl->device < 64 ? pl->device : 0];
-        if (!slot) {
-            // the lowest priority the device has: the marks' kernels read the steps three more times, and a query that runs beside them should not wait for that
-            int least = 0, greatest = 0;
-            if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = 0; }
-            if (hipStreamCreateWithPriority(&slot, hipStreamNonBlocking, least) != hipSuccess) { (void)hipGetLastError(); slot = nullptr; return; }
-        }
-        pl->side = slot;
-    }
+    if (!side_stream(pl)) return;
     pl->marks.assign(1 + pl->fast.n_more, MarksJob());
     for (size_t k = 0; k < pl->marks.size(); ++k) {
         const FastPlan &fp = k == 0 ? pl->fast : pl->fast.more[k - 1];
@@ -691,6 +898,9 @@ static bool plan_build_fast(flatgfa_dev_plan_t *pl, uint32_t *first_depth, uint3
     // ... and what can wait until the first answer is out -- the per-block no-claim marks -- is enqueued, on a stream of the
     // plan's own, by whatever the caller does with the plan next (marks_poll)
     pl->marks_to_start = true;
+    // ... and so is the run-length image of the steps (run_poll), for the plans the rule gives one (FLATGFA_RUN_IMAGE=0|1: none / whatever the size)
+    const char *hook = test_hook("FLATGFA_RUN_IMAGE");
+    pl->run_hook = hook ? (hook[0] == '1' ? 1 : 0) : -1;
     return true;
 }
 
@@ -755,7 +965,7 @@ static flatgfa_dev_plan_t *plan_create_impl(const flatgfa_dev_graph_t *g, const 
 }
 
 // What plan_build_fast made, given back: the marks' jobs (waited for, nothing installed), the claim on the Infinity Cache, the plan.
-static void plan_release_fast(flatgfa_dev_plan_t *pl) {
+static void plan_release_fast(flatgfa_dev_plan_t *pl, bool steps_changed = false) {
     pl->marks_to_start = false;
     if (pl->side) (void)hipStreamSynchronize(pl->side);
     for (MarksJob &job : pl->marks) {
@@ -764,6 +974,7 @@ static void plan_release_fast(flatgfa_dev_plan_t *pl) {
         fast_marks_finish(&nothing, &job);
     }
     pl->marks.clear();
+    run_release(pl, steps_changed);
     release_cache_claim(pl);
     fast_plan_destroy(&pl->fast);
 }
@@ -774,7 +985,7 @@ extern "C" int flatgfa_dev_plan_steps_changed(flatgfa_dev_plan_t *pl, void *stre
     DeviceGuard guard;  // (every exit below leaves the caller's device current)
     if (!guard.switch_to(pl->device)) { set_error("dev_plan_steps_changed: cannot switch to the plan's device"); return FLATGFA_ERR_HIP; }
     fgfa_dev::TempScope temporaries;  // (as plan_create_impl: what the plan's creation takes from the thread's arena is taken back)
-    plan_release_fast(pl);
+    plan_release_fast(pl, true);  // (the run-length image goes off the list: the next one is made from the steps as they are)
     // everything else that was derived from the step values: the overlap query's bitmaps (the (seg_len, depth) table is
     // filled anew by every call that reads it)
     for (void **p : {(void **)&pl->overlap_bits, (void **)&pl->overlap_qbits}) {
@@ -837,7 +1048,7 @@ extern "C" int flatgfa_dev_seg_depth(flatgfa_dev_plan_t *pl, uint32_t *depth_out
     hipStream_t stream = (hipStream_t)stream_;
     const flatgfa_dev_graph_t &g = pl->g;
     if (g.n_segs == 0) return FLATGFA_OK;
-    marks_poll(pl, false);  // (the per-block no-claim marks, once they are there: installed between two calls)
+    marks_poll(pl, false, true);  // (the per-block no-claim marks and the run-length image, once they are there: installed between two calls)
     pl->last_fast = pl->fast.eligible;
     pl->last_depth = depth_out;
     pl->last_uniq = uniq_out;
@@ -848,7 +1059,9 @@ extern "C" int flatgfa_dev_seg_depth(flatgfa_dev_plan_t *pl, uint32_t *depth_out
             const int rc = fast_check_plan_facts(pl->fast, g, pl->hb.data(), pl->he.data(), pl->status, stream);
             if (rc) return rc;
         }
-        return fast_seg_depth(pl->fast, g, depth_out, uniq_out, pl->status, stream);
+        const int rc = fast_seg_depth(pl->fast, g, depth_out, uniq_out, pl->status, stream);
+        if (rc == FLATGFA_OK) run_start_behind(pl, stream);
+        return rc;
     }
     return atomic_seg_depth(pl, depth_out, uniq_out, stream);
 }
@@ -938,7 +1151,7 @@ extern "C" int flatgfa_dev_path_depth_all(flatgfa_dev_plan_t *pl, uint32_t *dept
         FGFA_HIP_OR(hipMemsetAsync(weighted_out, 0, (size_t)g.n_paths * 8, (hipStream_t)stream_), return FLATGFA_ERR_HIP);
         return FLATGFA_OK;
     }
-    marks_poll(pl, false);
+    marks_poll(pl, false, true);
     pl->last_fast = pl->fast.eligible;
     pl->last_depth = depth_out;
     pl->last_uniq = nullptr;
@@ -1006,7 +1219,7 @@ extern "C" int flatgfa_dev_status(flatgfa_dev_plan_t *pl, void *stream_) {
             // Several calls were enqueued since the last status and (at least) one of them ran out of
             // scratch room: which one is not recorded, and only the last one's outputs are known here.
             set_error("node depth: a call ran out of scratch room (the steps changed behind the plan?) and " + std::to_string(n_calls) +
-                      " calls were enqueued since the last flatgfa_dev_status: call it after every call to have such a call completed");
+                      " calls were enqueued since the last flatgfa_dev_status: call it after every call to have such a call completed (status words " + std::to_string(st3[0]) + " " + std::to_string(st3[2]) + ")");
             return FLATGFA_ERR_HIP;
         }
         // The last node-depth call ran out of sub-bucket room, so its outputs are incomplete: run
@@ -1055,6 +1268,10 @@ extern "C" int flatgfa_dev_plan_describe(flatgfa_dev_plan_t *pl, char *out, int 
         const bool packed = any_range(f, [](const FastPlan &q) { return q.packed; });
         s += std::string(" buckets=") + (packed ? "packed" : "even") + " scratch_mb=" + std::to_string((recs * 4 + (1u << 20) - 1) >> 20) +
              " cache_resident_mb=" + std::to_string((f.mall_steps * 4) >> 20);
+        if (pl->run_show) {
+            if (pl->run_state == 3) s += " run_image=" + std::to_string((run_image_bytes(pl->run->img) + (1u << 20) - 1) >> 20);
+            else s += std::string(" run_image=off(") + (pl->run_state < 0 ? pl->run_off : "pending") + ")";
+        }
     }
     const int n = (int)std::min<size_t>(s.size(), (size_t)cap - 1);
     memcpy(out, s.data(), (size_t)n);

@@ -1863,9 +1863,16 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
             sa.zero_a = depth_out;
             sa.zero_b = uniq_out;
         }
-        ProfScope pscope(fp.dense ? "k_scan_dense" : "k_scan", stream);
-        const int rc = launch_scan(fp, sa, tagged, grid, stream);
-        if (rc != FLATGFA_OK) return rc;
+        // (a tagged call of a plan with the steps' run-length image installed reads that: no plan that is given one has dense
+        // pass 1, packed buckets, ranges, marks or wave-per-path lists)
+        const bool from_image = tagged && fp.run_ent && fp.run_item_ent && !count_only && !fp.dense && !fp.packed && !sa.ranged && !sa.cflags && !has_pre && !fp.dbg;
+        ProfScope pscope(from_image ? "k_scan_runs" : fp.dense ? "k_scan_dense" : "k_scan", stream);
+        if (from_image) {
+            launch_scan_runs(fp, sa, grid, stream);
+        } else {
+            const int rc = launch_scan(fp, sa, tagged, grid, stream);
+            if (rc != FLATGFA_OK) return rc;
+        }
     }
     if (count_only) return hipGetLastError() == hipSuccess ? FLATGFA_OK : FLATGFA_ERR_HIP;  // (the counting call of a packed plan: pass 1 alone)
     if (fp.acc_parts > 1 && !grid && !fp.accumulate) {  // the window's workgroups add to the outputs: cleared by k_scan, or here when it does not run

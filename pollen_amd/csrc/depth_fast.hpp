@@ -123,6 +123,13 @@ struct FastPlan {
     void *psum_part = nullptr;         // ulonglong2[n_win * dstride] per-window path sums of k_scan's items (on first use)
     uint32_t *other_ids = nullptr;     // u32[n_other] the paths k_scan_short walks (their sums need k_path_sums)
     uint32_t n_other = 0;
+    // The run-length image of the step array, once it is installed (run_image_install): tagged calls then run k_scan_runs on
+    // the image's entries, not k_scan on the steps.  The entries are the image's (shared by the plans of one step array), the
+    // items' stretches of them are the plan's handle's; neither is freed by fast_plan_destroy.
+    const void *run_ent = nullptr;       // uint2[run_n_ent + 1]
+    const void *run_item_ent = nullptr;  // uint2[n_items] the entries each item reads
+    uint32_t run_n_ent = 0;
+    bool run_nt = false;                 // the entries are read past the caches (they do not fit the Infinity Cache beside the records)
 };
 
 // A plan's ranges and path groups, one after the other: the first plan itself, then more[0 .. n_more).  `Plan` is FastPlan or
@@ -171,6 +178,26 @@ void fast_marks_finish(FastPlan *fp, MarksJob *job);
 // per-block marks, the reversed copies -- and raises status bit kStStale where one no longer holds.
 int fast_check_plan_facts(const FastPlan &fp, const flatgfa_dev_graph_t &g, const uint32_t *host_path_begin, const uint32_t *host_path_end, uint32_t *status,
                           hipStream_t stream);
+
+// The run-length image of a resident step array (depth_scan_runs.hip): one 8-byte entry per maximal
+// run of consecutive segment ids, made by a few kernels on `side` in two stages with the host in between (it has to know how
+// many entries there are before it gives them room).
+struct RunImage;
+// Enqueues the first stage (count, scan).  Never null; an image that cannot be had says so when it is polled.
+RunImage *run_image_start(const flatgfa_dev_graph_t &g, hipStream_t side);
+// Moves the image on as far as it can without blocking (`wait`: until it is there): 1 = there, 0 = not yet, -1 = not to be had
+// (run_image_why: "runs" -- more than an entry for four steps, unless any_ratio --, "memory" -- it would leave less than `reserve` bytes of device memory free --, "error").
+int run_image_poll(RunImage *im, hipStream_t side, bool wait, uint64_t reserve, bool any_ratio);
+const char *run_image_why(const RunImage *im);
+uint64_t run_image_bytes(const RunImage *im);  // entries and index, once it is there
+void run_image_free(RunImage *im, hipStream_t side);
+// The entries each of the plan's items reads (uint2[n_items], the caller's to free) and, in *room (the caller's to free), how many
+// records k_scan_runs -- whose deal of the items is fixed -- will put into each sub-bucket, computed on `side`; *done is recorded behind it.
+bool run_items_start(const FastPlan &fp, const RunImage *im, hipStream_t side, void **item_ent, void **room, hipEvent_t *done);
+// ... the fullest of them (once *done has happened): the image is installed in a plan whose sub-buckets hold that many
+uint32_t run_room_needed(const FastPlan &fp, const void *room);
+// From the plan's next tagged call on, pass 1 reads the image.  (No call of the plan may be enqueued concurrently from another thread.)
+void run_image_install(FastPlan *fp, const RunImage *im, void *item_ent, bool nt);
 
 // Decides eligibility (16-byte aligned steps, directories that stay small next to the steps) and
 // allocates the scratch: one range of at most 2048 windows, or several.  Returns false only on a HIP error.

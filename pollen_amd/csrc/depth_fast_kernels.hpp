@@ -1,6 +1,7 @@
 // Internal to the bucketed node-depth path: what its translation units share -- the constants, the kernels'
 // argument blocks, the wave-level helpers and the streaming loads into pinned landing registers.
 //   depth_scan.hip        pass 1: k_scan (runs of long items), k_scan_dense (ids without runs)
+//   depth_scan_runs.hip   pass 1 from the run-length image of the steps: k_scan_runs, and the kernels that make the image
 //   depth_scan_paths.hip  pass 1 for short paths: k_scan_short / k_scan_medium / k_scan_tiny (a wave per path)
 //   depth_accum.hip       pass 2: k_accum, k_path_reduce
 //   depth_fast.hip        the plan (which kernel walks which path, the scratch) and the launches
@@ -528,6 +529,8 @@ bool path_kernels_setup();        // depth_scan_paths.hip
 bool accum_kernels_setup();       // depth_accum.hip
 // pass 1 over the plan's long items: k_scan in the build the plan needs (tagged / ranged / packed / big), or k_scan_dense
 int launch_scan(const FastPlan &fp, const ScanArgs &sa, bool tagged, uint32_t grid, hipStream_t stream);
+// pass 1 of a tagged call from the plan's run-length image (FastPlan::run_ent): k_scan_runs
+void launch_scan_runs(const FastPlan &fp, const ScanArgs &sa, uint32_t grid, hipStream_t stream);
 // the wave-per-path kernels: paths a wave holds whole (k_scan_tiny), short and medium ones (k_scan_short's two builds)
 void launch_scan_tiny(const FastPlan &fp, const ScanArgs &sk, bool uniq, uint32_t grid, hipStream_t stream);
 void launch_scan_short(const FastPlan &fp, const ScanArgs &sk, bool medium, bool uniq, uint32_t grid, hipStream_t stream);

@@ -212,8 +212,8 @@ class DepthPlan:
 
     def describe(self) -> str:
         """Which kernels this plan's calls run (the choices made, some by timing, when it was created)."""
-        buf = ctypes.create_string_buffer(512)
-        _lib.lib().flatgfa_dev_plan_describe(self._p, buf, 512)
+        buf = ctypes.create_string_buffer(1024)
+        _lib.lib().flatgfa_dev_plan_describe(self._p, buf, 1024)
         return buf.value.decode()
 
     def status(self) -> None:
