@@ -411,6 +411,23 @@ int flatgfa_seq_export_file(const uint8_t *text, size_t n, const char *filename)
 int flatgfa_seq_import(const uint8_t *file, size_t n, char **text, size_t *text_len);
 int flatgfa_seq_import_stream(const uint8_t *file, size_t n, flatgfa_sink_t sink, void *ctx);
 int flatgfa_seq_packed_info(const uint8_t *file, size_t n, uint64_t *n_bases, uint64_t *data_offset);
+/* The GFA text of flatgfa_print_gfa (flatgfa/src/print.rs:99-153, either order), formatted on the GPU: the same bytes
+ * (`fgfa print`).  flatgfa_print_gfa stays the route for a machine without a device.  Everything is
+ * checked and counted before a byte is delivered.  What stops flatgfa_print_gfa stops these with its code and sentence,
+ * FLATGFA_ERR_BOUNDS, found on the host before any device is asked for, the first of them in line order: "print: empty
+ * header", "print: too few segments", "print: too few paths", "print: too few links", "print: bad line kind", "print: path
+ * with no steps".  Where the host printer would read outside a pool -- a sequence, optional, name, steps, overlaps or
+ * alignment span that leaves its pool, a step or link that names no segment -- FLATGFA_ERR_BOUNDS, flatgfa_last_error naming
+ * the pool.  More than 2^32 - 1 steps or more than 2^31 segments: FLATGFA_ERR_TOO_LARGE.  Without a device:
+ * FLATGFA_ERR_NO_DEVICE; NULL arguments: FLATGFA_ERR_ARG, answered without one.  A resident handle's steps are read in place.
+ * An empty graph is zero bytes, and the sink is never called. */
+/* the size of the text, nothing delivered */
+int flatgfa_print_gfa_bytes(flatgfa_t gfa, uint64_t *bytes);
+/* the text in a malloc'd buffer (release with flatgfa_free_text) */
+int flatgfa_print_gfa_device(flatgfa_t gfa, char **text, size_t *len);
+/* the text in order, a piece at a time; a sink that returns nonzero ends the call with FLATGFA_ERR_IO, nothing more is
+ * delivered, and the handle answers as before */
+int flatgfa_print_gfa_stream(flatgfa_t gfa, flatgfa_sink_t sink, void *ctx);
 /* format_float (ops/depth.rs:192-197); returns bytes written (no NUL). */
 int flatgfa_format_float(double x, int digits, char *out, int cap);
 

@@ -98,6 +98,9 @@ SIGNATURES = {
     "flatgfa_flatten_fasta": (c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_flatten_bed": (c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_flatten_stream": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_void_p, c_void_p]),
+    "flatgfa_print_gfa_bytes": (c_int, [c_void_p, POINTER(c_uint64)]),
+    "flatgfa_print_gfa_device": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_print_gfa_stream": (c_int, [c_void_p, c_void_p, c_void_p]),
     "flatgfa_seq_export": (c_int, [c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_seq_export_file": (c_int, [c_char_p, c_size_t, c_char_p]),
     "flatgfa_seq_import": (c_int, [c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),

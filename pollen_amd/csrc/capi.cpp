@@ -1,7 +1,7 @@
 // extern "C" surface of libflatgfa.so: the flatgfa-c drop-in (Part 1 of include/flatgfa.h)
 // plus the additive loaders, the depth queries and the host routes of the other features (Part 2).  The kernels live in the
 // .hip files -- depth_device.hip and its kin for depth, gaf_device.hip, gaf_lookup_device.hip, chop_device.hip,
-// extract_device.hip, topology_device.hip, flatten_device.hip, crush_device.hip, seq_device.hip for the rest -- and are reached through their headers; this file uses the HIP runtime
+// extract_device.hip, topology_device.hip, flatten_device.hip, crush_device.hip, seq_device.hip, print_device.hip for the rest -- and are reached through their headers; this file uses the HIP runtime
 // API only.  Every host route that is not a depth query holds what it has on the device in one DevScope (below).
 #include <hip/hip_runtime_api.h>
 
@@ -41,6 +41,7 @@
 #include "flatten_device.hpp"
 #include "crush_device.hpp"
 #include "seq_device.hpp"
+#include "print_device.hpp"
 
 using fgfa_dev::set_error;
 
@@ -168,7 +169,7 @@ int count_devices(const std::string &who, int *ndev) {
     return FLATGFA_OK;
 }
 
-// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree, flatten, crush, seq-export, seq-import -- holds on the device,
+// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree, flatten, crush, seq-export, seq-import, the GFA printer -- holds on the device,
 // given back on every way out: the work stream is waited for, then the job, the events and the memory go, then the streams
 // return to the pool.  A thread that still copies on one of the streams is joined first: its joiner is declared after the scope.
 struct DevScope {
@@ -2606,6 +2607,154 @@ int flatgfa_flatten_stream(flatgfa_t gfa, const char *name, size_t name_len, int
     FlatCall c;
     if (int rc = flat_open(gfa, &c, name, name_len, what)) return rc;
     return flat_emit(&c, sink, ctx);
+}
+
+// ---- the GFA printer on the device (flatgfa/src/print.rs:99-153) ----
+
+extern "C++" {
+namespace {
+static_assert(sizeof(fgfa_dev::PrintSeg) == sizeof(fgfa::Segment), "the segs pool is read as it is");
+
+// How many items a chunk holds: kPrintChunkItems, or what the tests ask for.
+uint64_t print_chunk_items() {
+    if (const char *h = test_hook("FLATGFA_PRINT_CHUNK_ITEMS")) return std::max<uint64_t>(1, strtoull(h, nullptr, 10));
+    return fgfa_dev::kPrintChunkItems;
+}
+
+int print_refuse(const char *what, int rc = FLATGFA_ERR_BOUNDS) {
+    set_error(what);
+    return rc;
+}
+bool span_in(fgfa::Span sp, size_t pool_len) { return sp.start <= sp.end && sp.end <= pool_len; }
+
+// One print call between its two halves: everything is checked and counted (open) before a byte is delivered (emit).
+struct PrintCall {
+    DevScope sc;
+    fgfa_dev::PrintJob *job = nullptr;
+    uint64_t bytes = 0;
+};
+
+int print_open(CStore *gfa, PrintCall *c) {
+    const fgfa::View &v = gfa->view;
+    const size_t S = v.segs.len, P = v.paths.len, L = v.links.len, N = v.steps.len;
+    if (N > 0xFFFFFFFFull || S > 0x80000000ull || P > 0xFFFFFFFFull || L > 0xFFFFFFFFull)
+        return print_refuse("print: graph too large for 32-bit ids", FLATGFA_ERR_TOO_LARGE);
+    // The lines, and what print_gfa stops at first (flatgfa_core.cpp, print.rs:99-150): one pass, no device.
+    fgfa_dev::PrintGraph g;
+    if (!v.line_order.len) {
+        g.header_lines = v.header.len ? 1 : 0, g.seg_lines = S, g.path_lines = P, g.link_lines = L;
+        for (size_t p = 0; p < P; ++p)
+            if (v.paths[p].steps.start == v.paths[p].steps.end) return print_refuse("print: path with no steps");
+    } else {
+        for (size_t k = 0; k < v.line_order.len; ++k) {
+            switch (v.line_order[k]) {
+                case fgfa::kHeader:
+                    if (!v.header.len) return print_refuse("print: empty header");
+                    ++g.header_lines;
+                    break;
+                case fgfa::kSegment:
+                    if (g.seg_lines >= S) return print_refuse("print: too few segments");
+                    ++g.seg_lines;
+                    break;
+                case fgfa::kPath:
+                    if (g.path_lines >= P) return print_refuse("print: too few paths");
+                    if (v.paths[g.path_lines].steps.start == v.paths[g.path_lines].steps.end) return print_refuse("print: path with no steps");
+                    ++g.path_lines;
+                    break;
+                case fgfa::kLink:
+                    if (g.link_lines >= L) return print_refuse("print: too few links");
+                    ++g.link_lines;
+                    break;
+                default:
+                    return print_refuse("print: bad line kind");
+            }
+        }
+    }
+    g.n_lines = g.header_lines + g.seg_lines + g.path_lines + g.link_lines;
+    // Refused where the host printer would read outside a pool: the spans and link handles of the lines that are printed.
+    for (size_t i = 0; i < g.seg_lines; ++i) {
+        if (!span_in(v.segs[i].seq, v.seq_data.len)) return print_refuse("print: a segment has a sequence span outside seq_data");
+        if (!span_in(v.segs[i].optional, v.optional_data.len)) return print_refuse("print: a segment has an optional span outside optional_data");
+    }
+    for (size_t i = 0; i < g.path_lines; ++i) {
+        const fgfa::Path &p = v.paths[i];
+        if (!span_in(p.name, v.name_data.len)) return print_refuse("print: a path has a name span outside name_data");
+        if (!span_in(p.steps, N)) return print_refuse("print: a path has a step span outside the steps pool");
+        if (!span_in(p.overlaps, v.overlaps.len)) return print_refuse("print: a path has an overlaps span outside the overlaps pool");
+        for (uint32_t o = p.overlaps.start; o < p.overlaps.end; ++o)
+            if (!span_in(v.overlaps[o], v.alignment.len)) return print_refuse("print: a path overlap has a span outside the alignment pool");
+    }
+    for (size_t i = 0; i < g.link_lines; ++i) {
+        const fgfa::Link &l = v.links[i];
+        if ((l.from >> 1) >= S || (l.to >> 1) >= S) return print_refuse("print: a link refers to a segment id that is out of range");
+        if (!span_in(l.overlap, v.alignment.len)) return print_refuse("print: a link has an overlap span outside the alignment pool");
+    }
+    DevScope &sc = c->sc;
+    if (int rc = open_scope(gfa, &sc, "the device GFA printer")) return rc;
+    c->job = sc.hold<fgfa_dev::PrintJob, fgfa_dev::print_free>(fgfa_dev::print_new(print_chunk_items()));
+    if (!g.n_lines) return fgfa_dev::print_begin(c->job, g, sc.stream, &c->bytes);  // (no text: nothing to upload)
+    // the pools as they are (the segment names in full: u64, as the pool holds them)
+    uint8_t *d_header = nullptr, *d_seq = nullptr, *d_names = nullptr, *d_opt = nullptr, *d_order = nullptr;
+    fgfa_dev::PrintSeg *d_segs = nullptr;
+    uint32_t *d_paths = nullptr, *d_links = nullptr, *d_steps = nullptr, *d_overlaps = nullptr, *d_align = nullptr;
+    CAPI_HIP(sc.upload(&d_header, v.header.data, v.header.len));
+    CAPI_HIP(sc.upload(&d_segs, v.segs.data, S));
+    CAPI_HIP(sc.upload(&d_paths, v.paths.data, 6 * P));
+    CAPI_HIP(sc.upload(&d_links, v.links.data, 4 * L));
+    CAPI_HIP(sc.upload(&d_overlaps, v.overlaps.data, 2 * v.overlaps.len));
+    CAPI_HIP(sc.upload(&d_align, v.alignment.data, v.alignment.len));
+    CAPI_HIP(sc.upload(&d_seq, v.seq_data.data, v.seq_data.len));
+    CAPI_HIP(sc.upload(&d_names, v.name_data.data, v.name_data.len));
+    CAPI_HIP(sc.upload(&d_opt, v.optional_data.data, v.optional_data.len));
+    if (v.line_order.len) CAPI_HIP(sc.upload(&d_order, v.line_order.data, v.line_order.len));
+    if (sc.resident) d_steps = gfa->d_steps;  // (read in place)
+    else CAPI_HIP(sc.upload(&d_steps, v.steps.data, N));
+    g.header = d_header, g.header_len = (uint32_t)v.header.len, g.segs = d_segs, g.n_segs = (uint32_t)S, g.paths = d_paths, g.links = d_links;
+    g.steps = d_steps, g.overlaps = d_overlaps, g.alignment = d_align, g.seq_data = d_seq, g.name_data = d_names, g.optional_data = d_opt;
+    g.line_order = d_order;
+    return fgfa_dev::print_begin(c->job, g, sc.stream, &c->bytes);
+}
+}  // namespace
+}  // extern "C++"
+
+int flatgfa_print_gfa_bytes(flatgfa_t gfa, uint64_t *bytes) {
+    if (!gfa || !bytes) { set_error("flatgfa_print_gfa_bytes: NULL argument"); return FLATGFA_ERR_ARG; }
+    *bytes = 0;
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    PrintCall c;
+    if (int rc = print_open(gfa, &c)) return rc;
+    *bytes = c.bytes;
+    return FLATGFA_OK;
+}
+
+int flatgfa_print_gfa_device(flatgfa_t gfa, char **text, size_t *len) {
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (!gfa || !text || !len) { set_error("flatgfa_print_gfa_device: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    PrintCall c;
+    if (int rc = print_open(gfa, &c)) return rc;
+    TextSink t{nullptr, (size_t)c.bytes, 0};
+    t.buf = (char *)malloc(t.cap + 1);
+    if (!t.buf) { set_error("flatgfa_print_gfa_device: out of memory"); return FLATGFA_ERR_IO; }
+    int rc = fgfa_dev::print_emit(c.job, TextSink::take, &t);
+    if (!rc && t.at != t.cap) { set_error("flatgfa_print_gfa_device: internal: the text is not as long as it was counted"); rc = FLATGFA_ERR_HIP; }
+    if (rc) {
+        free(t.buf);
+        return rc;
+    }
+    t.buf[t.cap] = 0;
+    *text = t.buf;
+    *len = t.cap;
+    return FLATGFA_OK;
+}
+
+int flatgfa_print_gfa_stream(flatgfa_t gfa, flatgfa_sink_t sink, void *ctx) {
+    if (!gfa || !sink) { set_error("flatgfa_print_gfa_stream: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    PrintCall c;
+    if (int rc = print_open(gfa, &c)) return rc;
+    return fgfa_dev::print_emit(c.job, sink, ctx);
 }
 
 }  // extern "C"

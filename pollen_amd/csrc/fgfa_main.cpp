@@ -5,7 +5,7 @@
 //   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [--bed-paths FILE.bed] [-s PATHS]
 //            | window-depth PATH SIZE | window-depth-all SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l] | inject -b BED [-l] | crush
 //            | extract -n NAME -c DIST [-d N] [-e N] | position -p PATH,OFFSET,+ | validate | degree
-//            | flatten [-n NAME] [-f FASTA] [-b BED]
+//            | flatten [-n NAME] [-f FASTA] [-b BED] | print [-O OUT.gfa]
 //   fgfa seq-export INPUT OUTPUT | fgfa seq-import FILE        (no graph is read)
 //
 // With no -i/-I the GFA text is read from stdin; with no COMMAND the graph is written out
@@ -63,6 +63,20 @@ static int write_fd(void *ctx, const char *p, size_t n) {
         p += w;
         n -= (size_t)w;
     }
+    return 0;
+}
+
+// flatgfa_sink_t of the GFA text: stdout, or a file that is made when the first piece arrives -- the text has been checked by
+// then, so that a print error leaves no file behind
+struct TextOut {
+    const char *file;
+    int fd = -1;
+    bool failed = false;
+};
+static int write_text(void *ctx, const char *p, size_t n) {
+    TextOut *o = static_cast<TextOut *>(ctx);
+    if (o->fd < 0 && (o->fd = o->file ? open(o->file, O_WRONLY | O_CREAT | O_TRUNC, 0666) : STDOUT_FILENO) < 0) o->failed = true;
+    if (o->fd < 0 || write_fd(&o->fd, p, n)) return o->failed = true, 1;
     return 0;
 }
 
@@ -124,7 +138,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "crush" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten" || cmd == "seq-export" || cmd == "seq-import";
+    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "crush" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten" || cmd == "print" || cmd == "seq-export" || cmd == "seq-import";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -208,9 +222,28 @@ int main(int argc, char **argv) {
 #endif
     if (warm.joinable()) warm.join();
 
-    // dump (cli/main.rs:192-212): -o FILE as .flatgfa, else -O FILE as GFA text, else GFA text on stdout
+    // the GFA text through the device printer, as it streams: to `file`, else to stdout
+    auto print_stream = [&](flatgfa_t gr, const char *file) -> int {
+        TextOut o{file};
+        int r = 0;
+        if (flatgfa_print_gfa_stream(gr, write_text, &o)) {
+            if (o.failed) fprintf(stderr, "fgfa: cannot write %s\n", file ? file : "the output");
+            else die("print");
+            r = 1;
+        } else if (file && o.fd < 0 && (o.fd = open(file, O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0) {  // (no text: an empty file)
+            fprintf(stderr, "fgfa: cannot write %s\n", file);
+            r = 1;
+        }
+        if (file && o.fd >= 0 && close(o.fd) && !r) { fprintf(stderr, "fgfa: cannot write %s\n", file); r = 1; }
+        return r;
+    };
+
+    // dump (cli/main.rs:192-212): -o FILE as .flatgfa, else -O FILE as GFA text, else GFA text on stdout.  The text of a
+    // command that has brought the device up (chop, inject, crush, extract) is formatted there; a bare `fgfa` prints on the
+    // host, where a small graph does not pay for the HIP runtime coming up.
     auto dump = [&](flatgfa_t gr) -> int {
         if (out_flat) return flatgfa_write_flatgfa(gr, out_flat) ? die("write") : 0;
+        if (wants_device) return print_stream(gr, out_gfa);
         char *text = nullptr;
         size_t n = 0;
         int r = 0;
@@ -380,6 +413,19 @@ int main(int argc, char **argv) {
         if (!fasta && !bed) rc = to(nullptr, 3);
         if (fasta) rc = to(fasta, 1);
         if (bed && !rc) rc = to(bed, 2);
+    } else if (cmd == "print") {
+        // the graph as GFA text (cli/main.rs:192-212 with no command), formatted on the GPU: fgfa print [-O FILE]
+        bool bad = false;
+        for (; i < argc; ++i) {
+            if (!strcmp(argv[i], "-O") && i + 1 < argc) out_gfa = argv[++i];
+            else bad = true;
+        }
+        if (bad) {
+            fprintf(stderr, "usage: fgfa [-i FILE | -I FILE] print\n");
+            flatgfa_free(g);
+            return 2;
+        }
+        rc = print_stream(g, out_gfa);
     } else if (cmd == "toc") {
         bool bytes = i < argc && !strcmp(argv[i], "-b");
         static const char *names[11] = {"header", "segs", "paths", "links", "steps", "seq_data",

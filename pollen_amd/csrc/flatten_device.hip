@@ -10,7 +10,8 @@
 //            tile stored with 16-byte vector stores.  Reads no base.
 //
 // Both texts leave in pieces of kFlatPieceBytes: a piece is formatted into one of two device buffers, copied into one half
-// of a borrowed staging buffer on the job's copy stream, and handed to the sink while the next piece travels.
+// of a borrowed staging buffer on the job's copy stream, and handed to the sink while the next piece travels (Pipe in
+// text_tiles.hpp, which the GFA printer shares).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,34 +23,15 @@
 #include "flatten_device.hpp"
 #include "host_copy.hpp"
 #include "prof.hpp"
+#include "text_tiles.hpp"
 
 namespace fgfa_dev {
 namespace {
 
 #define FL_HIP(expr) FGFA_HIP("flatten: ", expr)
 
-static_assert(kFlatTile % (16 * kFlatThreads) == 0, "every lane stores whole 16-byte vectors of a tile");
-static_assert(kFlatPieceBytes % kFlatTile == 0 && 2 * kFlatPieceBytes <= kStagingBytes, "two pieces share a staging buffer");
-// clipped copies of more than kFlatLongName bytes are disjoint stretches of one tile
-constexpr uint32_t kLongCap = kFlatTile / (kFlatLongName + 1) + 2;
 constexpr uint32_t kBedFixed = 7;  // five tabs, the strand, the newline
 const char kBedHeader[] = "#name\tstart\tend\tpath.name\tstrand\tstep.rank\n";
-
-// the last index of [lo, hi] whose value is at or before x (a[lo] <= x holds)
-__device__ __forceinline__ uint64_t last_at_or_before(const uint64_t *__restrict__ a, uint64_t lo, uint64_t hi, uint64_t x) {
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo + 1) >> 1);
-        if (a[mid] <= x) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t digits10(uint64_t x) {
-    uint32_t n = 1;
-    for (uint64_t p = 10; n < 20 && x >= p; p *= 10) ++n;
-    return n;
-}
 
 // ---- the legend ----
 struct LegendOp {
@@ -151,11 +133,6 @@ struct FlatLineLen {
     __device__ __forceinline__ void store(uint64_t i, uint64_t before, const Sum<uint64_t> &) const { off[i] = before; }
 };
 
-struct LongCopy {
-    const uint8_t *src;
-    uint32_t dst, len;
-};
-
 // The tile [B0, B0 + tlen) of a chunk of n lines and `bytes` bytes; positions are kept relative to B0, so a line that began in
 // an earlier tile has a negative one.
 __global__ __launch_bounds__(kFlatThreads) void k_flat_bed(FlatPaths g, const uint8_t *__restrict__ name, uint32_t name_len, uint64_t j0, uint64_t n,
@@ -243,12 +220,9 @@ int flatten_legend(const uint32_t *seg_len, uint32_t n_segs, uint64_t *offset_ou
     return FLATGFA_OK;
 }
 
-struct FlatJob {
+struct FlatJob : PieceBufs {  // (the streams, the events and the two piece buffers: text_tiles.hpp)
     uint64_t chunk_lines = kFlatChunkLines;
     uint64_t chunks = 0;
-    hipStream_t st = nullptr, copy = nullptr;  // the caller's work stream; the job's own copy stream
-    hipEvent_t made[2] = {}, copied[2] = {};   // piece b is formatted / has arrived
-    uint8_t *out[2] = {};                      // kFlatPieceBytes each
     uint64_t *off = nullptr;                   // u64[chunk_lines]: line offsets within the chunk
     uint64_t *total = nullptr;                 // the check's byte count, then its flag word
     uint8_t *name = nullptr;
@@ -267,11 +241,7 @@ FlatJob *flatten_new(uint64_t chunk_lines) {
 
 void flatten_free(FlatJob *j) {
     if (!j) return;
-    if (j->st) (void)hipStreamSynchronize(j->st);
-    if (j->copy) (void)hipStreamSynchronize(j->copy);
-    for (hipEvent_t e : {j->made[0], j->made[1], j->copied[0], j->copied[1]})
-        if (e) (void)hipEventDestroy(e);
-    if (j->copy) (void)hipStreamDestroy(j->copy);
+    pieces_free(j);
     delete j;  // (the device memory goes with mem)
 }
 
@@ -282,83 +252,10 @@ uint64_t flatten_fasta_bytes(uint64_t total_bases, size_t name_len) {
     return 2 + (uint64_t)name_len + body;
 }
 
-namespace {
-
-// the copy stream, the events and the two piece buffers, made once per job
-int job_ready(FlatJob *j, hipStream_t st) {
-    j->st = st;
-    j->mem.st = st;
-    if (j->copy) return FLATGFA_OK;
-    FL_HIP(hipStreamCreateWithFlags(&j->copy, hipStreamNonBlocking));
-    for (int b = 0; b < 2; ++b) {
-        FL_HIP(hipEventCreateWithFlags(&j->made[b], hipEventDisableTiming));
-        FL_HIP(hipEventCreateWithFlags(&j->copied[b], hipEventDisableTiming));
-        FL_HIP(j->mem.alloc(&j->out[b], kFlatPieceBytes));
-    }
-    return FLATGFA_OK;
-}
-
-// The pieces on their way out.  Piece k is formatted into device buffer k & 1 on the work stream, copied into half k & 1 of
-// the borrowed staging buffer on the copy stream, and piece k - 1 is handed to the sink while it travels.
-struct Pipe {
-    FlatJob *j;
-    FlatSink sink;
-    void *ctx;
-    char *pin = nullptr;
-    std::unique_lock<std::mutex> lock;
-    uint64_t k = 0;
-    size_t len[2] = {};
-    Pipe(FlatJob *job, FlatSink s, void *c) : j(job), sink(s), ctx(c) { lock = borrow_staging(&pin); }
-    ~Pipe() {  // nothing may still travel into the staging buffer when it goes back
-        (void)hipStreamSynchronize(j->st);
-        (void)hipStreamSynchronize(j->copy);
-    }
-    int give(const char *p, size_t n) {
-        if (n && sink(ctx, p, n)) {
-            set_error("flatten: the sink stopped the call");
-            return FLATGFA_ERR_IO;
-        }
-        return FLATGFA_OK;
-    }
-    int retire(int b) {
-        FL_HIP(hipEventSynchronize(j->copied[b]));
-        return give(pin + (size_t)b * kFlatPieceBytes, len[b]);
-    }
-    // launch(out) enqueues on the work stream the kernel that writes the piece's `bytes` bytes to out
-    template <class Launch>
-    int push(size_t bytes, const Launch &launch) {
-        const int b = (int)(k & 1);
-        launch(j->out[b]);
-        FL_HIP(hipGetLastError());
-        FL_HIP(hipEventRecord(j->made[b], j->st));
-        FL_HIP(hipStreamWaitEvent(j->copy, j->made[b], 0));
-        FL_HIP(hipMemcpyAsync(pin + (size_t)b * kFlatPieceBytes, j->out[b], bytes, hipMemcpyDeviceToHost, j->copy));
-        FL_HIP(hipEventRecord(j->copied[b], j->copy));
-        len[b] = bytes;
-        const int rc = k ? retire(b ^ 1) : FLATGFA_OK;  // (whose buffers piece k + 1 takes)
-        ++k;
-        return rc;
-    }
-    int finish() { return k ? retire((int)((k - 1) & 1)) : FLATGFA_OK; }
-    // `bytes` bytes of tiles, piece by piece: launch(out, first tile, tiles)
-    template <class Launch>
-    int tiles(uint64_t bytes, const Launch &launch) {
-        for (uint64_t at = 0; at < bytes; at += kFlatPieceBytes) {
-            const uint64_t n = std::min<uint64_t>(kFlatPieceBytes, bytes - at);
-            const uint64_t tile0 = at / kFlatTile;
-            const uint32_t nt = (uint32_t)blocks(n, kFlatTile);
-            if (int rc = push((size_t)n, [&](uint8_t *out) { launch(out, tile0, nt); })) return rc;
-        }
-        return FLATGFA_OK;
-    }
-};
-
-}  // namespace
-
 int flatten_fasta(FlatJob *j, const FlatSeqs &g, const uint8_t *name, size_t name_len, hipStream_t st, FlatSink sink, void *ctx) {
     if (!j || !sink || (name_len && !name)) { set_error("flatten: NULL argument"); return FLATGFA_ERR_ARG; }
-    if (int rc = job_ready(j, st)) return rc;
-    Pipe pipe(j, sink, ctx);
+    if (int rc = pieces_ready(j, &j->mem, st, "flatten: ")) return rc;
+    Pipe pipe(j, sink, ctx, "flatten: ");
     if (!pipe.pin) { set_error("flatten: no pinned staging buffer"); return FLATGFA_ERR_HIP; }
     std::string head = ">";
     head.append((const char *)name, name_len).push_back('\n');
@@ -376,7 +273,7 @@ int flatten_bed_begin(FlatJob *j, const FlatPaths &g, const uint8_t *name, size_
     if (!j || !bytes || (name_len && !name)) { set_error("flatten: NULL argument"); return FLATGFA_ERR_ARG; }
     if (name_len > 0xFFFFFFFFull) { set_error("flatten: the name is longer than 2^32 - 1 bytes"); return FLATGFA_ERR_TOO_LARGE; }
     j->begun = false;
-    if (int rc = job_ready(j, st)) return rc;
+    if (int rc = pieces_ready(j, &j->mem, st, "flatten: ")) return rc;
     if (!j->total) {
         FL_HIP(j->mem.alloc(&j->total, 2));
         FL_HIP(j->mem.alloc(&j->off, j->chunk_lines));
@@ -412,7 +309,7 @@ int flatten_bed_emit(FlatJob *j, FlatSink sink, void *ctx) {
     if (!j || !sink) { set_error("flatten: NULL argument"); return FLATGFA_ERR_ARG; }
     if (!j->begun) { set_error("flatten: emit before a successful begin"); return FLATGFA_ERR_ARG; }
     j->chunks = 0;
-    Pipe pipe(j, sink, ctx);
+    Pipe pipe(j, sink, ctx, "flatten: ");
     if (!pipe.pin) { set_error("flatten: no pinned staging buffer"); return FLATGFA_ERR_HIP; }
     if (int rc = pipe.give(kBedHeader, sizeof kBedHeader - 1)) return rc;
     const FlatPaths &g = j->g;

@@ -181,6 +181,51 @@ class FlatGFA:
     def __str__(self) -> str:
         return self.gfa_text().decode(errors="replace")
 
+    # ---- the same text, formatted on the GPU (print.rs:99-153; no CPU fallback: gfa_text is that route) ----
+    def gfa_bytes(self) -> int:
+        """How many bytes the GFA text has (flatgfa_print_gfa_bytes): everything checked and counted, nothing delivered."""
+        n = ctypes.c_uint64()
+        _check(_lib.lib().flatgfa_print_gfa_bytes(self._h, ctypes.byref(n)), "print_gfa_bytes")
+        return int(n.value)
+
+    def gfa_text_device(self) -> bytes:
+        """The bytes of gfa_text(), formatted on the GPU (flatgfa_print_gfa_device)."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(_lib.lib().flatgfa_print_gfa_device(self._h, ctypes.byref(p), ctypes.byref(n)), "print_gfa_device")
+        return _take_text(p, n)
+
+    def gfa_stream(self, write) -> None:
+        """flatgfa_print_gfa_stream: `write(bytes)` receives the text of gfa_text() in order, a piece at a time.  A `write`
+        that raises, or returns something true, stops the call."""
+        raised = []
+
+        def sink(_ctx, ptr, n):
+            try:
+                return 1 if write(ctypes.string_at(ptr, n)) else 0  # (a piece is a few megabytes: within string_at's C int)
+            except BaseException as e:  # noqa: BLE001  (must not unwind through the C caller)
+                raised.append(e)
+                return 1
+        rc = _lib.lib().flatgfa_print_gfa_stream(self._h, _lib.SINK_T(sink), None)
+        if raised:
+            raise raised[0]
+        _check(rc, "print_gfa_stream")
+
+    def write_gfa_device(self, filename: str) -> None:
+        """write_gfa through the GPU printer, written as it streams.  The file is made once the text has been checked."""
+        f = []
+
+        def write(b):
+            if not f:
+                f.append(open(filename, "wb"))
+            f[0].write(b)
+        try:
+            self.gfa_stream(write)
+            if not f:
+                f.append(open(filename, "wb"))  # (an empty graph: an empty file)
+        finally:
+            if f:
+                f[0].close()
+
     # ---- depth queries (HIP) ----
     def to_device(self, device: int = 0) -> None:
         _check(_lib.lib().flatgfa_to_device(self._h, device), "to_device")
