@@ -396,13 +396,18 @@ static hipStream_t side_stream(flatgfa_dev_plan_t *pl) {
 }
 
 // ---- the run-length image of the steps ----
-// One image per device and resident step array, whoever's plan asked first: the lanes of a pipeline and a stand-alone plan
-// on the same graph hold its 8 bytes per run once.  Reference-counted like the claim on the Infinity Cache; the last plan to
-// go frees it.  A plan whose steps were declared changed takes the image off the list (the plans that still hold it go on
+// One image per device, resident step array and number of steps, whoever's plan asked first: the lanes of a pipeline and a
+// stand-alone plan on the same graph hold its 8 bytes per run once.  The paths' spans and n_segs are NOT part of the key: an
+// image cuts its runs where the first plan's paths begin and end, every reader clips a run to its own item's steps, and ids
+// are checked against the reader's n_segs.  The number of steps is: the image's block index has one word per 1024 steps of
+// the array it was made of, and its last entry closes the last run there -- a plan over more steps of the same allocation
+// (a graph made of a longer slice of one tensor) would read past both, so it gets an image of its own.  Reference-counted
+// like the claim on the Infinity Cache; the last plan to go frees it.  A plan whose steps were declared changed takes the image off the list (the plans that still hold it go on
 // with it until they are told too) and asks again: the next one is made from the steps as they are.
 struct RunShare {
     int device;
     const uint32_t *steps;
+    uint64_t n_steps;
     RunImage *img;
     hipStream_t side;
     int users;
@@ -473,17 +478,19 @@ static const char *run_image_refused(flatgfa_dev_plan_t *pl) {
     if (!forced && !kRunImageDefault) return "default";
     if (!forced && !by_size) return "small";
     if (!f.eligible) return "atomic";
+    // (k_scan_runs deals the items evenly: a workgroup's share must fit its private tags.  Asked before `tagged`, which the
+    // same shortage takes away: the description then names the cause)
+    if (f.n_items && ((uint64_t)f.n_items + std::min(f.n_items, f.n_slots) - 1) / std::min(f.n_items, f.n_slots) > f.tag_limit) return "items";
     if (!f.tagged) return "untagged";
     if (f.n_more || f.n_groups > 1 || f.seg_base || f.n_range != g.n_segs) return "ranges";
     if (f.packed) return "packed";
     if (f.dense) return "dense";
     if (f.n_short || f.n_medium || f.n_tiny) return "short_paths";
     if (!f.n_items) return "no_items";
-    if (((uint64_t)f.n_items + std::min(f.n_items, f.n_slots) - 1) / std::min(f.n_items, f.n_slots) > f.tag_limit) return "items";  // (k_scan_runs deals the items evenly: a workgroup's share must fit its private tags)
     if (f.cflags) return "marks";
     if (pl->check_facts) return "check_no_claim";
     if (f.dbg) return "debug";
-    if (f.wb < 10 || f.wb > 13) return "windows";  // (a run of up to 1024 steps must fit a record's length field, and cross one window edge at most)
+    if (f.wb < 11 || f.wb > 13) return "windows";  // (the widths pass 2 has builds for: a run of up to 1024 steps fits a record's length field at all of them, and crosses one window edge at most)
     // spans that overlap: the image would be right (an item's entries are clipped to its steps), but such plans are rare and untested here
     std::vector<std::pair<uint32_t, uint32_t>> spans;
     for (size_t p = 0; p < pl->hb.size(); ++p)
@@ -522,9 +529,9 @@ static void run_poll(flatgfa_dev_plan_t *pl, bool wait, bool may_start, hipStrea
             (void)hipGetLastError();
         }
         for (RunShare *sh : g_run_shares)
-            if (sh->device == pl->device && sh->steps == pl->g.steps) pl->run = sh;
+            if (sh->device == pl->device && sh->steps == pl->g.steps && sh->n_steps == pl->g.n_steps) pl->run = sh;
         if (!pl->run) {
-            pl->run = new RunShare{pl->device, pl->g.steps, run_image_start(pl->g, side), side, 0, true, pl->run_hook == 1};
+            pl->run = new RunShare{pl->device, pl->g.steps, pl->g.n_steps, run_image_start(pl->g, side), side, 0, true, pl->run_hook == 1};
             g_run_shares.push_back(pl->run);
             side_work_enqueued(pl->device);
         }
@@ -1269,8 +1276,13 @@ extern "C" int flatgfa_dev_plan_describe(flatgfa_dev_plan_t *pl, char *out, int 
         s += std::string(" buckets=") + (packed ? "packed" : "even") + " scratch_mb=" + std::to_string((recs * 4 + (1u << 20) - 1) >> 20) +
              " cache_resident_mb=" + std::to_string((f.mall_steps * 4) >> 20);
         if (pl->run_show) {
-            if (pl->run_state == 3) s += " run_image=" + std::to_string((run_image_bytes(pl->run->img) + (1u << 20) - 1) >> 20);
-            else s += std::string(" run_image=off(") + (pl->run_state < 0 ? pl->run_off : "pending") + ")";
+            if (pl->run_state == 3) {  // (its size in MB, the steps it was made of, the plans that hold it now, how k_scan_runs reads it)
+                std::lock_guard<std::mutex> lk(g_run_mu);
+                s += " run_image=" + std::to_string((run_image_bytes(pl->run->img) + (1u << 20) - 1) >> 20) + " run_image_steps=" + std::to_string(pl->run->n_steps) +
+                     " run_image_plans=" + std::to_string(pl->run->users) + " run_image_reads=" + (f.run_nt ? "nt" : "plain");
+            } else {
+                s += std::string(" run_image=off(") + (pl->run_state < 0 ? pl->run_off : "pending") + ")";
+            }
         }
     }
     const int n = (int)std::min<size_t>(s.size(), (size_t)cap - 1);

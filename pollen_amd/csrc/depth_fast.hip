@@ -500,7 +500,10 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
     // difference array and per-path bitsets in LDS).
     uint32_t wb = g.n_segs <= 1024u * 4096u ? 12u : 13u;
     if (force_wb) wb = force_wb;  // (fast_plan_create: 4096-segment windows on a larger graph, for the sake of its split paths)
-    if (const char *f = test_hook("FLATGFA_WB")) wb = (uint32_t)strtoul(f, nullptr, 10);
+    if (const char *f = test_hook("FLATGFA_WB")) {  // (11, 12 or 13: the widths pass 2 has builds for; anything else is not a width)
+        const uint32_t asked = (uint32_t)strtoul(f, nullptr, 10);
+        if (asked >= 11u && asked <= 13u) wb = asked;
+    }
     const uint32_t n_win = (uint32_t)(((uint64_t)n_range + (1u << wb) - 1) >> wb);
     if (n_win > max_win) return true;
     int dev = 0;

@@ -24,7 +24,8 @@ pytestmark = pytest.mark.gpu
 
 HOOKS = ("FLATGFA_RUN_IMAGE", "FLATGFA_DEPTH_PATH", "FLATGFA_SHORT_MAX", "FLATGFA_PIECE_STEPS", "FLATGFA_SCAN_WGS", "FLATGFA_ACC_PARTS",
          "FLATGFA_CHECK_NO_CLAIM", "FLATGFA_RANGE_SEGS", "FLATGFA_MALL_MB", "FLATGFA_TAGGED", "FLATGFA_WB", "FLATGFA_DENSE",
-         "FLATGFA_NO_CLAIM_BLOCKS_OFF", "FLATGFA_PACKED", "FLATGFA_BUCKET_CAP")
+         "FLATGFA_NO_CLAIM_BLOCKS_OFF", "FLATGFA_PACKED", "FLATGFA_BUCKET_CAP", "FLATGFA_TAG_LIMIT", "FLATGFA_TAG_MEAN_ONLY",
+         "FLATGFA_PATH_GROUPS")
 IMAGE = re.compile(r" run_image=(\d+)\b")
 OFF = re.compile(r" run_image=off\((\w+)\)")
 
