@@ -428,6 +428,30 @@ int flatgfa_print_gfa_device(flatgfa_t gfa, char **text, size_t *len);
 /* the text in order, a piece at a time; a sink that returns nonzero ends the call with FLATGFA_ERR_IO, nothing more is
  * delivered, and the handle answers as before */
 int flatgfa_print_gfa_stream(flatgfa_t gfa, flatgfa_sink_t sink, void *ctx);
+/* GFA text parsed on the GPU (`fgfa -D`): a handle whose pools are byte for byte those of
+ * flatgfa_parse_bytes (from_stream == 0) or flatgfa_parse_stream_bytes (from_stream != 0) on the same text.  The device
+ * judges the plain grammar only -- one H line at most, `S <digits> <seq> [<rest>]`, `L <digits> [+-] <digits> [+-] <cigar>`,
+ * `P <name> <steps> <overlaps>` with single commas, every number of at most 32 digits, every name one a segment has --
+ * and hands every other text, the same bytes, to the host parser: that parser's handle, or NULL with its message, is then
+ * the call's.  flatgfa_parse_device maps the file, as flatgfa_parse does.  NULL with "no HIP device is visible; the device
+ * GFA parser has no CPU fallback" without a device (flatgfa_parse_bytes stays the route there); NULL data with len > 0, or a
+ * NULL filename: NULL with a message, answered without a device; a device allocation that fails: NULL with HIP's message. */
+flatgfa_t flatgfa_parse_bytes_device(const uint8_t *data, size_t len, int from_stream);
+flatgfa_t flatgfa_parse_device(const char *filename);
+/* The calling thread's last flatgfa_parse_bytes_device / flatgfa_parse_device call that reached a device: out[0] = the
+ * route (1: the device made the pools, 0: the host parser), out[1] = why (one of the codes below), out[2] = the bytes of a
+ * text tile of the step kernels, out[3] = the tiles of the call's text.  FLATGFA_ERR_ARG for NULL or before such a call. */
+enum {
+    FLATGFA_PARSE_PLAIN = 0,   /* the device route */
+    FLATGFA_PARSE_GRAMMAR = 1, /* a line that is not of the plain forms */
+    FLATGFA_PARSE_NAME = 2,    /* a link or a step names no segment, name 0, or a segment id >= 2^31 */
+    FLATGFA_PARSE_LIMIT = 3    /* a number of more than 32 digits, or a pool past 2^32 - 1 items */
+};
+int flatgfa_parse_device_info(uint64_t out[4]);
+/* ... and that call's milliseconds: the text's upload; every kernel and scan of the call, by HIP events; of those the two
+ * step kernels alone; the pools' download.  What is left of the whole call is the host's: totals read back, allocations,
+ * the name map.  Zeros on the host route. */
+int flatgfa_parse_device_times(double out[4]);
 /* format_float (ops/depth.rs:192-197); returns bytes written (no NUL). */
 int flatgfa_format_float(double x, int digits, char *out, int cap);
 

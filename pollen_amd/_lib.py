@@ -98,6 +98,10 @@ SIGNATURES = {
     "flatgfa_flatten_fasta": (c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_flatten_bed": (c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_flatten_stream": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_void_p, c_void_p]),
+    "flatgfa_parse_bytes_device": (c_void_p, [c_char_p, c_size_t, c_int]),
+    "flatgfa_parse_device": (c_void_p, [c_char_p]),
+    "flatgfa_parse_device_info": (c_int, [POINTER(c_uint64)]),
+    "flatgfa_parse_device_times": (c_int, [POINTER(ctypes.c_double)]),
     "flatgfa_print_gfa_bytes": (c_int, [c_void_p, POINTER(c_uint64)]),
     "flatgfa_print_gfa_device": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_print_gfa_stream": (c_int, [c_void_p, c_void_p, c_void_p]),

@@ -42,6 +42,7 @@
 #include "crush_device.hpp"
 #include "seq_device.hpp"
 #include "print_device.hpp"
+#include "parse_device.hpp"
 
 using fgfa_dev::set_error;
 
@@ -283,6 +284,74 @@ flatgfa_t flatgfa_parse(const char *filename) {
     std::string err;
     if (!f.open(filename, &err)) { set_error(err); return nullptr; }
     return flatgfa_parse_bytes(f.data, f.size);
+}
+
+// ---- GFA text parsed on the device ----
+
+extern "C++" {
+namespace {
+struct ParseRecord {
+    bool any = false;
+    uint64_t info[4] = {0, 0, 0, 0};
+    double ms[4] = {0, 0, 0, 0};
+};
+thread_local ParseRecord t_parse_record;
+
+// What no pool may pass on the device route: 2^32 - 1 items, or what the tests ask for.
+uint64_t parse_device_limit() {
+    if (const char *h = test_hook("FLATGFA_PARSE_DEVICE_LIMIT")) return strtoull(h, nullptr, 10);
+    return 0xFFFFFFFFull;
+}
+
+flatgfa_t parse_device_common(const uint8_t *data, size_t len, bool stream_mode) {
+    auto cs = std::make_unique<CStore>();
+    fgfa_dev::ParseInfo info;
+    {
+        DevScope sc;
+        if (open_scope(nullptr, &sc, "the device GFA parser")) return nullptr;
+        if (fgfa_dev::parse_device(data ? data : (const uint8_t *)"", len, stream_mode, parse_device_limit(), sc.stream, &cs->heap, &info))
+            return nullptr;
+    }
+    ParseRecord &r = t_parse_record;
+    r.any = true;
+    r.info[0] = (uint64_t)info.device_route;
+    r.info[1] = (uint64_t)info.reason;
+    r.info[2] = info.tile_bytes;
+    r.info[3] = info.tiles;
+    r.ms[0] = info.upload_ms, r.ms[1] = info.kernel_ms, r.ms[2] = info.step_ms, r.ms[3] = info.download_ms;
+    if (!info.device_route) {  // not the plain grammar: the host parser's handle, or its error, on the same bytes
+        r.ms[0] = r.ms[1] = r.ms[2] = r.ms[3] = 0;
+        return parse_common(data, len, stream_mode);
+    }
+    cs->view = cs->heap.view();
+    return cs.release();
+}
+}  // namespace
+}  // extern "C++"
+
+flatgfa_t flatgfa_parse_bytes_device(const uint8_t *data, size_t len, int from_stream) {
+    if (!data && len) { set_error("flatgfa_parse_bytes_device: NULL data with a length"); return nullptr; }
+    return parse_device_common(data, len, from_stream != 0);
+}
+
+flatgfa_t flatgfa_parse_device(const char *filename) {
+    if (!filename) { set_error("flatgfa_parse_device: NULL filename"); return nullptr; }
+    fgfa::MappedFile f;
+    std::string err;
+    if (!f.open(filename, &err)) { set_error(err); return nullptr; }
+    return parse_device_common(f.data, f.size, false);
+}
+
+int flatgfa_parse_device_info(uint64_t out[4]) {
+    if (!out || !t_parse_record.any) { set_error("flatgfa_parse_device_info: NULL argument, or no device parse on this thread yet"); return FLATGFA_ERR_ARG; }
+    for (int i = 0; i < 4; ++i) out[i] = t_parse_record.info[i];
+    return FLATGFA_OK;
+}
+
+int flatgfa_parse_device_times(double out[4]) {
+    if (!out || !t_parse_record.any) { set_error("flatgfa_parse_device_times: NULL argument, or no device parse on this thread yet"); return FLATGFA_ERR_ARG; }
+    for (int i = 0; i < 4; ++i) out[i] = t_parse_record.ms[i];
+    return FLATGFA_OK;
 }
 
 flatgfa_t flatgfa_load(const char *filename) {

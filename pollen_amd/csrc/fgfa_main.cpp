@@ -1,14 +1,15 @@
 // `fgfa` -- the slice of the reference CLI that sits on the depth path
 // (cucapra/pollen flatgfa/src/cli/main.rs:9-55, cmds.rs:16-97,217-285), built on the C ABI:
 //
-//   fgfa [-i FILE.flatgfa | -I FILE.gfa] [-o OUT.flatgfa] [-O OUT.gfa] [COMMAND]
+//   fgfa [-i FILE.flatgfa | -I FILE.gfa] [-D] [-o OUT.flatgfa] [-O OUT.gfa] [COMMAND]
 //   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [--bed-paths FILE.bed] [-s PATHS]
 //            | window-depth PATH SIZE | window-depth-all SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l] | inject -b BED [-l] | crush
 //            | extract -n NAME -c DIST [-d N] [-e N] | position -p PATH,OFFSET,+ | validate | degree
 //            | flatten [-n NAME] [-f FASTA] [-b BED] | print [-O OUT.gfa]
 //   fgfa seq-export INPUT OUTPUT | fgfa seq-import FILE        (no graph is read)
 //
-// With no -i/-I the GFA text is read from stdin; with no COMMAND the graph is written out
+// With no -i/-I the GFA text is read from stdin; with -D that text, or -I's, is parsed on the GPU (the same graph; a text that
+// is not of the plain grammar goes to the host parser; without a device: an error); with no COMMAND the graph is written out
 // (-o binary, -O text, otherwise text on stdout).  `depth` output is byte-identical to the
 // reference's and is computed on the GPU, as are `matrix` (cmds.rs:453-475), `position` (cmds.rs:105-152), and `chop`
 // (cli/main.rs:139-159) and `extract` (cmds.rs:174-215), whose graph is written out as the input graph would be; `validate` and `degree` print what slow_odgi's validate.py and
@@ -91,6 +92,7 @@ static void write_all(const char *p, size_t n) {
 
 int main(int argc, char **argv) {
     const char *in_flat = nullptr, *in_gfa = nullptr, *out_flat = nullptr, *out_gfa = nullptr, *prealloc = nullptr;
+    bool device_parse = false;  // -D: the text of -I FILE, or of stdin, is parsed on the device
     bool mutate = false;  // -m: with -o, write the preallocated container (cli/main.rs:88-96); with -i, open for mutation (read the same way here)
     int i = 1;
     for (; i < argc; ++i) {
@@ -104,10 +106,15 @@ int main(int argc, char **argv) {
         else if (a == "-o") need(&out_flat);
         else if (a == "-O") need(&out_gfa);
         else if (a == "-m") mutate = true;
+        else if (a == "-D") device_parse = true;
         else if (a == "-p") need(&prealloc);
         else break;
     }
     std::string cmd = i < argc ? argv[i++] : "";
+    if (device_parse && in_flat) {
+        fprintf(stderr, "usage: fgfa -D parses GFA text (-I FILE, or stdin): it does not go with -i\n");
+        return 2;
+    }
 
     // The special case the reference's main starts with (cli/main.rs:61-66): `-m -o OUT` with no command and
     // no -i is prealloc_translate -- GFA text (the mapped -I file, or stdin) parsed straight into the mapped,
@@ -138,7 +145,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "crush" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten" || cmd == "print" || cmd == "seq-export" || cmd == "seq-import";
+    const bool wants_device = device_parse || cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "crush" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten" || cmd == "print" || cmd == "seq-export" || cmd == "seq-import";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -198,13 +205,14 @@ int main(int argc, char **argv) {
     if (in_flat) {
         g = flatgfa_load(in_flat);
     } else if (in_gfa) {
-        g = flatgfa_parse(in_gfa);
+        g = device_parse ? flatgfa_parse_device(in_gfa) : flatgfa_parse(in_gfa);
     } else {
         std::string buf;
         char tmp[1 << 16];
         ssize_t r;
         while ((r = read(STDIN_FILENO, tmp, sizeof tmp)) > 0) buf.append(tmp, (size_t)r);
-        g = flatgfa_parse_stream_bytes((const uint8_t *)buf.data(), buf.size());
+        g = device_parse ? flatgfa_parse_bytes_device((const uint8_t *)buf.data(), buf.size(), 1)
+                         : flatgfa_parse_stream_bytes((const uint8_t *)buf.data(), buf.size());
     }
     if (!g) {
         if (warm.joinable()) warm.join();

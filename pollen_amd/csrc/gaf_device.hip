@@ -26,6 +26,7 @@
 #include "../../include/flatgfa.h"
 #include "device_common.hpp"
 #include "gaf_device.hpp"
+#include "name_lookup.hpp"
 #include "prof.hpp"
 
 namespace fgfa_dev {
@@ -151,18 +152,7 @@ struct Names {
 
 __device__ __forceinline__ void emit(uint64_t num, const Names &nm, unsigned long long *row,
                                      unsigned long long *first_bad, uint64_t report) {
-    uint32_t id = 0xFFFFFFFFu;
-    if (num <= nm.seq_max) {  // namemap.rs:28-29 (name 0 wraps to u32::MAX)
-        id = (uint32_t)(num - 1);
-    } else {  // namemap.rs:31
-        uint32_t lo = 0, hi = nm.n_others;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (nm.keys[mid] < num) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo < nm.n_others && nm.keys[lo] == num) id = nm.ids[lo];
-    }
+    const uint32_t id = name_map_get(num, nm.keys, nm.ids, nm.n_others, nm.seq_max);
     if (id >= nm.n_segs) {  // the reference panics: a missing key, or an index past the row
         atomicMin(first_bad, (unsigned long long)report);
         return;

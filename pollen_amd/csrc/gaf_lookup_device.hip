@@ -38,6 +38,7 @@
 #include "device_common.hpp"
 #include "device_scan.hpp"
 #include "gaf_lookup_device.hpp"
+#include "name_lookup.hpp"
 #include "prof.hpp"
 
 namespace fgfa_dev {
@@ -277,14 +278,7 @@ struct Graph {
 
 // NameMap::get (namemap.rs:27-33); an id >= n_segs is where the reference panics
 __device__ __forceinline__ uint32_t name_id(uint64_t num, const Graph &g) {
-    if (num <= g.seq_max) return (uint32_t)(num - 1);  // (name 0 wraps to u32::MAX)
-    uint32_t lo = 0, hi = g.n_others;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (g.keys[mid] < num) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < g.n_others && g.keys[lo] == num ? g.ids[lo] : 0xFFFFFFFFu;
+    return name_map_get(num, g.keys, g.ids, g.n_others, g.seq_max);
 }
 
 struct EventOut {

@@ -781,6 +781,39 @@ def parse_stream_bytes(gfa: bytes) -> FlatGFA:
     return FlatGFA(_lib.lib().flatgfa_parse_stream_bytes(gfa, len(gfa)))
 
 
+PARSE_REASONS = ("plain", "grammar", "name", "limit")
+
+
+def parse_device_info() -> dict:
+    """This thread's last device-parse call (flatgfa_parse_device_info, flatgfa_parse_device_times): the route taken ("device" or
+    "host"), why, the step kernels' text tile in bytes, the tiles of the text, and the call's milliseconds."""
+    info = (ctypes.c_uint64 * 4)()
+    ms = (ctypes.c_double * 4)()
+    _check(_lib.lib().flatgfa_parse_device_info(info), "parse_device_info")
+    _check(_lib.lib().flatgfa_parse_device_times(ms), "parse_device_times")
+    return {"parsed_on": "device" if info[0] else "host", "reason": PARSE_REASONS[info[1]], "tile_bytes": int(info[2]), "tiles": int(info[3]),
+            "upload_ms": ms[0], "kernel_ms": ms[1], "step_ms": ms[2], "download_ms": ms[3]}
+
+
+def _parsed_on_device(handle: int) -> FlatGFA:
+    g = FlatGFA(handle)
+    info = parse_device_info()
+    g.parsed_on, g.parse_reason, g.parse_info = info["parsed_on"], info["reason"], info
+    return g
+
+
+def parse_bytes_device(gfa: bytes, stream: bool = False) -> FlatGFA:
+    """The graph of parse_bytes (stream=False) or parse_stream_bytes (stream=True), its pools made on the GPU where the text is
+    of the plain grammar and by the host parser where it is not: `parsed_on` says which ("device" or
+    "host"), `parse_reason` why ("plain", "grammar", "name", "limit").  Without a device: FlatGFAError."""
+    return _parsed_on_device(_lib.lib().flatgfa_parse_bytes_device(gfa, len(gfa), 1 if stream else 0))
+
+
+def parse_device(filename) -> FlatGFA:
+    """parse(filename) through the device route (flatgfa_parse_device)."""
+    return _parsed_on_device(_lib.lib().flatgfa_parse_device(os.fsencode(filename)))
+
+
 def translate_prealloc(gfa: bytes, filename: Union[str, os.PathLike], factor: int = 32, from_stream: bool = False) -> None:
     """`fgfa -m -p FACTOR -o OUT [-I GFA]` (cli/main.rs:216-248): the text is parsed straight into the
     mapped, preallocated output file (file.rs:255-272); no graph is built in between.  `from_stream`:
