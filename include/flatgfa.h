@@ -428,6 +428,28 @@ int flatgfa_print_gfa_device(flatgfa_t gfa, char **text, size_t *len);
 /* the text in order, a piece at a time; a sink that returns nonzero ends the call with FLATGFA_ERR_IO, nothing more is
  * delivered, and the handle answers as before */
 int flatgfa_print_gfa_stream(flatgfa_t gfa, flatgfa_sink_t sink, void *ctx);
+/* Which lines of BED text `b` lie under the intervals of BED text `a` (`fgfa bed -a FILE -b FILE`; cli/cmds.rs:392-413,
+ * flatbed.rs:37-57): byte for byte what the reference prints.  Both texts are read as flatgfa_bed_depth_table
+ * reads its BED text (flatbed.rs:125-158: an unterminated last line is dropped, `#` lines are skipped, the name is the bytes
+ * before the first tab, numbers are u64 and wrap, columns after the third are ignored), and what stops it stops these with
+ * its code and sentence.  The entries of `a` are taken in file order, and for each the entries x of `b` in file order: with
+ * s = max(x.start, a.start) and e = min(x.end, a.end), "name \t s \t e \n" is printed where the two names are equal byte for
+ * byte and e > s.  Duplicates are kept.  No graph is read.  The pairs are not all tried: the entries of `b` are grouped by
+ * name, and where a group's starts never decrease in file order an entry of `a` meets only the stretch of the group that
+ * can overlap it; a group that is not so sorted is walked whole for each entry of `a` of its name (the same text, at the cost
+ * of the reference's double loop restricted to that name).
+ * A text of 2^32 bytes or more, or a file of 2^32 - 1 entries or more: FLATGFA_ERR_BOUNDS and a sentence that starts "bed: ",
+ * the former before a byte of the text is read.  NULL arguments (a text may be NULL only with length 0): FLATGFA_ERR_ARG,
+ * answered without a device; so are the parse errors and the refusals.  Without a device: FLATGFA_ERR_NO_DEVICE. */
+/* the text in a malloc'd, NUL-terminated buffer (release with flatgfa_free_text) */
+int flatgfa_bed_intersect(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, char **text, size_t *len);
+/* the text in order, a piece at a time; a sink that returns nonzero ends the call with FLATGFA_ERR_IO, nothing more is
+ * delivered; with no line to print the sink is never called */
+int flatgfa_bed_intersect_stream(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, flatgfa_sink_t sink, void *ctx);
+/* the same work without the text: how many lines and bytes the text has, how many pairs were tried (*candidates), and how
+ * many of b's name groups were walked whole (*unsorted_groups) */
+int flatgfa_bed_intersect_count(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint64_t *lines, uint64_t *bytes,
+                                uint64_t *candidates, uint64_t *unsorted_groups);
 /* GFA text parsed on the GPU (`fgfa -D`): a handle whose pools are byte for byte those of
  * flatgfa_parse_bytes (from_stream == 0) or flatgfa_parse_stream_bytes (from_stream != 0) on the same text.  The device
  * judges the plain grammar only -- one H line at most, `S <digits> <seq> [<rest>]`, `L <digits> [+-] <digits> [+-] <cigar>`,
@@ -713,6 +735,25 @@ int flatgfa_dev_seq_pack_count(const uint8_t *text, uint64_t n, void *stream, fl
 int flatgfa_dev_seq_pack_fill(flatgfa_dev_seq_pack_t *job, int carry, uint8_t *out, void *stream);
 void flatgfa_dev_seq_pack_free(flatgfa_dev_seq_pack_t *job);
 int flatgfa_dev_seq_unpack(const uint8_t *packed, uint64_t n_bases, uint8_t *text_out, void *stream);
+/* BED intersection (flatgfa_bed_intersect, without names or text) of entries in device memory.  Entry i of a side has the
+ * name id id[i] and the interval [start[i], end[i]).  b's ids are below n_groups and never decrease (b is grouped by name,
+ * file order kept inside a group); a's ids are below n_groups, or 0xFFFFFFFF for a name b does not have; anything else:
+ * FLATGFA_ERR_BOUNDS, with no job.  Either side may be empty (its pointers may then be NULL); 2^32 - 1 entries or more on a
+ * side: FLATGFA_ERR_BOUNDS.  flatgfa_dev_bed_begin finds the groups and every a entry's candidate range, waits for `stream`
+ * once and returns a job in *job, the number of candidate pairs, the number of rounds they are cut into -- round_cands
+ * candidates each, 0 for the library's own size -- and the number of groups that are walked whole.  flatgfa_dev_bed_round
+ * writes the hits of round `round` in the reference's order into caller memory with room for min(round_cands, *candidates)
+ * records each -- a_index and b_index (the entries' indices as given), start = max of the starts, end = min of the ends --
+ * and waits for the job's stream to return their number in *n_hits.  Rounds may be asked for in any order, one at a time.
+ * The sides' arrays must stay as they are until the job is freed.  flatgfa_dev_bed_free waits for the job's stream and
+ * releases its scratch. */
+typedef struct flatgfa_dev_bed flatgfa_dev_bed_t;
+int flatgfa_dev_bed_begin(const uint32_t *a_id, const uint64_t *a_start, const uint64_t *a_end, uint64_t n_a, const uint32_t *b_id,
+                          const uint64_t *b_start, const uint64_t *b_end, uint64_t n_b, uint32_t n_groups, uint64_t round_cands, void *stream,
+                          flatgfa_dev_bed_t **job, uint64_t *candidates, uint64_t *rounds, uint64_t *unsorted_groups);
+int flatgfa_dev_bed_round(flatgfa_dev_bed_t *job, uint64_t round, uint32_t *a_index, uint32_t *b_index, uint64_t *start, uint64_t *end,
+                          uint64_t *n_hits);
+void flatgfa_dev_bed_free(flatgfa_dev_bed_t *job);
 /* The legend of flatten (flatten.py:13-19; flatgfa_flatten_legend) of a graph image in device memory: d_offset_out[s] = the
  * sum of g->seg_len before s, d_offset_out[n_segs] = the sum of all, in 64 bits (g->seg_len is required: FLATGFA_ERR_ARG when
  * NULL; the steps and spans are not read).  Enqueued on `stream`, which is waited for: the scan's scratch goes before the

@@ -105,6 +105,10 @@ SIGNATURES = {
     "flatgfa_print_gfa_bytes": (c_int, [c_void_p, POINTER(c_uint64)]),
     "flatgfa_print_gfa_device": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_print_gfa_stream": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "flatgfa_bed_intersect": (c_int, [c_char_p, c_size_t, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "flatgfa_bed_intersect_stream": (c_int, [c_char_p, c_size_t, c_char_p, c_size_t, c_void_p, c_void_p]),
+    "flatgfa_bed_intersect_count": (c_int, [c_char_p, c_size_t, c_char_p, c_size_t, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64),
+                                            POINTER(c_uint64)]),
     "flatgfa_seq_export": (c_int, [c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
     "flatgfa_seq_export_file": (c_int, [c_char_p, c_size_t, c_char_p]),
     "flatgfa_seq_import": (c_int, [c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
@@ -161,6 +165,10 @@ SIGNATURES = {
     "flatgfa_dev_seq_pack_fill": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "flatgfa_dev_seq_pack_free": (None, [c_void_p]),
     "flatgfa_dev_seq_unpack": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p]),
+    "flatgfa_dev_bed_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_uint64, c_void_p,
+                                      POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    "flatgfa_dev_bed_round": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
+    "flatgfa_dev_bed_free": (None, [c_void_p]),
     "flatgfa_dev_flatten_legend": (c_int, [POINTER(flatgfa_dev_graph_t), c_void_p, c_void_p]),
     "flatgfa_dev_status": (c_int, [c_void_p, c_void_p]),
     "flatgfa_dev_profile_enable": (None, [c_int]),

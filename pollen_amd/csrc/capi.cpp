@@ -18,6 +18,7 @@
 #include <mutex>
 #include <thread>
 #include <unordered_map>
+#include <string_view>
 #include <unordered_set>
 #include <vector>
 
@@ -43,6 +44,7 @@
 #include "seq_device.hpp"
 #include "print_device.hpp"
 #include "parse_device.hpp"
+#include "bed_device.hpp"
 
 using fgfa_dev::set_error;
 
@@ -170,7 +172,7 @@ int count_devices(const std::string &who, int *ndev) {
     return FLATGFA_OK;
 }
 
-// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree, flatten, crush, seq-export, seq-import, the GFA printer -- holds on the device,
+// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree, flatten, crush, seq-export, seq-import, the GFA printer, bed -- holds on the device,
 // given back on every way out: the work stream is waited for, then the job, the events and the memory go, then the streams
 // return to the pool.  A thread that still copies on one of the streams is joined first: its joiner is declared after the scope.
 struct DevScope {
@@ -2824,6 +2826,180 @@ int flatgfa_print_gfa_stream(flatgfa_t gfa, flatgfa_sink_t sink, void *ctx) {
     PrintCall c;
     if (int rc = print_open(gfa, &c)) return rc;
     return fgfa_dev::print_emit(c.job, sink, ctx);
+}
+
+// ---- BED intersection (cli/cmds.rs:392-413, flatbed.rs:37-57) ----
+
+extern "C++" {
+namespace {
+// How many candidates a round holds: kBedRoundCands, or what the tests ask for.
+uint64_t bed_round_cands() {
+    if (const char *h = test_hook("FLATGFA_BED_ROUND_CANDS")) return std::max<uint64_t>(1, strtoull(h, nullptr, 10));
+    return fgfa_dev::kBedRoundCands;
+}
+
+int bed_refuse(const char *what) {
+    set_error(what);
+    return FLATGFA_ERR_BOUNDS;
+}
+
+// One side as the device takes it.
+struct BedColumns {
+    std::vector<uint32_t> id;
+    std::vector<uint64_t> start, end;
+};
+
+// One intersect call: the texts parsed, B's names interned and B grouped on the host -- all of it O(lines), all of it before
+// a device is asked for -- then the entries on the device with the groups and candidate ranges found (bed_begin).
+struct BedCall {
+    DevScope sc;
+    fgfa_dev::BedJob *job = nullptr;
+    uint64_t candidates = 0, unsorted_groups = 0;
+};
+
+int bed_open(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, BedCall *c) {
+    // (parse_bed keeps name offsets in 32 bits; decided before a byte is read)
+    if ((uint64_t)a_len >= (1ull << 32) || (uint64_t)b_len >= (1ull << 32)) return bed_refuse("bed: a text of 2^32 bytes or more is not taken");
+    fgfa::Bed A, B;
+    std::string err;
+    if (!fgfa::parse_bed(a ? a : (const uint8_t *)"", a_len, &A, &err) || !fgfa::parse_bed(b ? b : (const uint8_t *)"", b_len, &B, &err)) {
+        set_error(err);
+        return FLATGFA_ERR_BOUNDS;  // (flatgfa_bed_depth_table's code)
+    }
+    const size_t nA = A.entries.size(), nB = B.entries.size();
+    if (nA >= 0xFFFFFFFFull || nB >= 0xFFFFFFFFull) return bed_refuse("bed: a file of 2^32 - 1 entries or more is not taken");
+    // B's names get dense ids in the order they first appear; A's names are looked up in the same table
+    const auto name_of = [](const fgfa::Bed &bed, const fgfa::BedEntry &e) {
+        return std::string_view((const char *)bed.name_data.data() + e.name_start, e.name_end - e.name_start);
+    };
+    std::unordered_map<std::string_view, uint32_t> ids;
+    std::vector<uint32_t> b_id(nB), gname, group_start(1, 0);
+    std::vector<uint8_t> names;
+    {
+        std::string_view last;
+        uint32_t last_id = 0;
+        for (size_t i = 0; i < nB; ++i) {
+            const std::string_view nm = name_of(B, B.entries[i]);
+            if (!i || nm != last) {  // (a file sorted by name asks the table once a name)
+                const auto got = ids.emplace(nm, (uint32_t)ids.size());
+                if (got.second) {
+                    gname.push_back((uint32_t)names.size());
+                    gname.push_back((uint32_t)nm.size());
+                    names.insert(names.end(), nm.begin(), nm.end());
+                    group_start.push_back(0);
+                }
+                last = nm, last_id = got.first->second;
+            }
+            b_id[i] = last_id;
+            ++group_start[last_id + 1];
+        }
+    }
+    const uint32_t G = (uint32_t)ids.size();
+    for (uint32_t g = 0; g < G; ++g) group_start[g + 1] += group_start[g];
+    BedColumns ca, cb;  // B grouped by id, stably: file order is kept inside a group
+    cb.id.resize(nB), cb.start.resize(nB), cb.end.resize(nB);
+    {
+        std::vector<uint32_t> next(group_start.begin(), group_start.end() - 1);
+        for (size_t i = 0; i < nB; ++i) {
+            const uint32_t at = next[b_id[i]]++;
+            cb.id[at] = b_id[i], cb.start[at] = B.entries[i].start, cb.end[at] = B.entries[i].end;
+        }
+    }
+    ca.id.resize(nA), ca.start.resize(nA), ca.end.resize(nA);
+    {
+        std::string_view last;
+        uint32_t last_id = fgfa_dev::kBedNone;
+        for (size_t i = 0; i < nA; ++i) {
+            const std::string_view nm = name_of(A, A.entries[i]);
+            if (!i || nm != last) {
+                const auto it = ids.find(nm);
+                last = nm, last_id = it == ids.end() ? fgfa_dev::kBedNone : it->second;
+            }
+            ca.id[i] = last_id, ca.start[i] = A.entries[i].start, ca.end[i] = A.entries[i].end;
+        }
+    }
+    DevScope &sc = c->sc;
+    if (int rc = open_scope(nullptr, &sc, "bed")) return rc;
+    fgfa_dev::BedInput in;
+    uint32_t *d_aid = nullptr, *d_bid = nullptr, *d_gname = nullptr;
+    uint64_t *d_as = nullptr, *d_ae = nullptr, *d_bs = nullptr, *d_be = nullptr;
+    uint8_t *d_names = nullptr;
+    CAPI_HIP(sc.upload(&d_aid, ca.id.data(), nA));
+    CAPI_HIP(sc.upload(&d_as, ca.start.data(), nA));
+    CAPI_HIP(sc.upload(&d_ae, ca.end.data(), nA));
+    CAPI_HIP(sc.upload(&d_bid, cb.id.data(), nB));
+    CAPI_HIP(sc.upload(&d_bs, cb.start.data(), nB));
+    CAPI_HIP(sc.upload(&d_be, cb.end.data(), nB));
+    CAPI_HIP(sc.upload(&d_gname, gname.data(), gname.size()));
+    CAPI_HIP(sc.upload(&d_names, names.data(), names.size()));
+    in.a = fgfa_dev::BedSide{d_aid, d_as, d_ae, nA};
+    in.b = fgfa_dev::BedSide{d_bid, d_bs, d_be, nB};
+    in.n_groups = G, in.names = d_names, in.gname = d_gname;
+    c->job = sc.hold<fgfa_dev::BedJob, fgfa_dev::bed_free>(fgfa_dev::bed_new(bed_round_cands()));
+    return fgfa_dev::bed_begin(c->job, in, sc.stream, &c->candidates, &c->unsorted_groups);
+}
+
+// a malloc'd text that grows as the pieces arrive
+struct GrowSink {
+    char *buf = nullptr;
+    size_t cap = 0, at = 0;
+    static int take(void *ctx, const char *bytes, size_t n) {
+        GrowSink *t = static_cast<GrowSink *>(ctx);
+        if (n > t->cap - t->at) {
+            const size_t cap = std::max(t->at + n, 2 * t->cap);
+            char *p = (char *)realloc(t->buf, cap + 1);
+            if (!p) return 1;
+            t->buf = p, t->cap = cap;
+        }
+        memcpy(t->buf + t->at, bytes, n);
+        t->at += n;
+        return 0;
+    }
+};
+}  // namespace
+}  // extern "C++"
+
+int flatgfa_bed_intersect(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, char **text, size_t *len) {
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if ((!a && a_len) || (!b && b_len) || !text || !len) { set_error("flatgfa_bed_intersect: NULL argument"); return FLATGFA_ERR_ARG; }
+    BedCall c;
+    if (int rc = bed_open(a, a_len, b, b_len, &c)) return rc;
+    GrowSink t;
+    t.buf = (char *)malloc(1);
+    if (!t.buf) { set_error("flatgfa_bed_intersect: out of memory"); return FLATGFA_ERR_IO; }
+    const int rc = fgfa_dev::bed_emit(c.job, GrowSink::take, &t, nullptr);
+    if (rc == FLATGFA_ERR_IO) set_error("flatgfa_bed_intersect: out of memory");  // (the one reason this sink stops)
+    if (rc) {
+        free(t.buf);
+        return rc;
+    }
+    t.buf[t.at] = 0;
+    *text = t.buf;
+    *len = t.at;
+    return FLATGFA_OK;
+}
+
+int flatgfa_bed_intersect_stream(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, flatgfa_sink_t sink, void *ctx) {
+    if ((!a && a_len) || (!b && b_len) || !sink) { set_error("flatgfa_bed_intersect_stream: NULL argument"); return FLATGFA_ERR_ARG; }
+    BedCall c;
+    if (int rc = bed_open(a, a_len, b, b_len, &c)) return rc;
+    return fgfa_dev::bed_emit(c.job, sink, ctx, nullptr);
+}
+
+int flatgfa_bed_intersect_count(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint64_t *lines, uint64_t *bytes,
+                                uint64_t *candidates, uint64_t *unsorted_groups) {
+    if ((!a && a_len) || (!b && b_len) || !lines || !bytes || !candidates || !unsorted_groups) {
+        set_error("flatgfa_bed_intersect_count: NULL argument");
+        return FLATGFA_ERR_ARG;
+    }
+    *lines = *bytes = *candidates = *unsorted_groups = 0;
+    BedCall c;
+    if (int rc = bed_open(a, a_len, b, b_len, &c)) return rc;
+    fgfa_dev::BedTotals t;
+    if (int rc = fgfa_dev::bed_count(c.job, &t)) return rc;
+    *lines = t.lines, *bytes = t.bytes, *candidates = t.candidates, *unsorted_groups = t.unsorted_groups;
+    return FLATGFA_OK;
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 //            | window-depth PATH SIZE | window-depth-all SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l] | inject -b BED [-l] | crush
 //            | extract -n NAME -c DIST [-d N] [-e N] | position -p PATH,OFFSET,+ | validate | degree
 //            | flatten [-n NAME] [-f FASTA] [-b BED] | print [-O OUT.gfa]
-//   fgfa seq-export INPUT OUTPUT | fgfa seq-import FILE        (no graph is read)
+//   fgfa seq-export INPUT OUTPUT | fgfa seq-import FILE | fgfa bed -a FILE -b FILE        (no graph is read)
 //
 // With no -i/-I the GFA text is read from stdin; with -D that text, or -I's, is parsed on the GPU (the same graph; a text that
 // is not of the plain grammar goes to the host parser; without a device: an error); with no COMMAND the graph is written out
@@ -15,7 +15,8 @@
 // (cli/main.rs:139-159) and `extract` (cmds.rs:174-215), whose graph is written out as the input graph would be; `validate` and `degree` print what slow_odgi's validate.py and
 // degree.py print, `crush` writes out the graph of its crush.py, `flatten` what its flatten.py prints (or, with -f / -b, what `odgi flatten` writes to those files).
 // `seq-export` and `seq-import` (cmds.rs:415-452) are the packed-sequence codec of packedseq.rs, on the GPU as well; like the
-// reference's they take files, not a graph, and stdin is never read.  Of the reference CLI that leaves `bench` and `bed-intersect`.
+// reference's they take files, not a graph, and stdin is never read.  So does `bed` (cmds.rs:378-413, bed-intersect): the lines
+// of -b that lie under the intervals of -a, found and printed on the GPU.  Of the reference CLI that leaves `bench`.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -145,7 +146,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = device_parse || cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "crush" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten" || cmd == "print" || cmd == "seq-export" || cmd == "seq-import";
+    const bool wants_device = device_parse || cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "crush" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten" || cmd == "print" || cmd == "seq-export" || cmd == "seq-import" || cmd == "bed";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -195,6 +196,45 @@ int main(int argc, char **argv) {
             }
         }
         if (warm.joinable()) warm.join();
+        fflush(stdout);
+        fflush(stderr);
+        if (!test_hook("FLATGFA_SLOW_EXIT")) _exit(rc);
+        return rc;
+    }
+
+    // cli/cmds.rs:378-413: fgfa bed -a FILE -b FILE -- before any graph is loaded too; both files are mapped, the text goes to
+    // stdout as it streams
+    if (cmd == "bed") {
+        const char *file[2] = {nullptr, nullptr};
+        bool bad = false;
+        for (; i < argc; ++i) {
+            const int k = !strcmp(argv[i], "-a") ? 0 : !strcmp(argv[i], "-b") ? 1 : -1;
+            if (k < 0 || i + 1 >= argc || file[k]) { bad = true; break; }
+            file[k] = argv[++i];
+        }
+        int rc = 0;
+        void *m[2] = {nullptr, nullptr};
+        size_t n[2] = {0, 0};
+        if (bad || !file[0] || !file[1]) {
+            fprintf(stderr, "usage: fgfa bed -a FILE -b FILE\n");
+            rc = 2;
+        }
+        for (int k = 0; k < 2 && !rc; ++k) {
+            const int fd = open(file[k], O_RDONLY);
+            struct stat sb;
+            if (fd < 0 || fstat(fd, &sb) != 0) {
+                fprintf(stderr, "fgfa: cannot open %s\n", file[k]);
+                rc = 1;
+            } else if ((n[k] = (size_t)sb.st_size) && (m[k] = mmap(nullptr, n[k], PROT_READ, MAP_PRIVATE, fd, 0)) == MAP_FAILED) {
+                fprintf(stderr, "fgfa: cannot map %s\n", file[k]);
+                rc = 1;
+            }
+            if (fd >= 0) close(fd);
+            if (!rc && m[k]) (void)madvise(m[k], n[k], MADV_SEQUENTIAL);
+        }
+        if (warm.joinable()) warm.join();
+        int out = STDOUT_FILENO;
+        if (!rc && flatgfa_bed_intersect_stream((const uint8_t *)m[0], n[0], (const uint8_t *)m[1], n[1], write_fd, &out)) rc = die("bed");
         fflush(stdout);
         fflush(stderr);
         if (!test_hook("FLATGFA_SLOW_EXIT")) _exit(rc);

@@ -1,6 +1,6 @@
-// What the device's text writers share (flatten_device.hip: FASTA and BED; print_device.hip: GFA text): the small device
-// functions of a tile of output bytes, and the pieces on their way to the sink.  HIP only; templates and inline functions, so
-// both .hip files include it.  DESIGN.md sections 15 and 19.
+// What the device's text writers share (flatten_device.hip: FASTA and BED; print_device.hip: GFA text; bed_device.hip: the
+// intersect lines): the small device functions of a tile of output bytes, and the pieces on their way to the sink.  HIP only;
+// templates and inline functions, so all of them include it.  DESIGN.md sections 15, 19 and 21.
 //
 // The tile shape is flatten's (flatten_device.hpp): kFlatThreads lanes own kFlatTile consecutive output bytes, form them in
 // LDS and store them with 16-byte vector stores; a piece of kFlatPieceBytes is what one launch writes and one copy takes to

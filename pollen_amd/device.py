@@ -452,6 +452,55 @@ def seq_unpack(packed, n_bases: int, stream=None):
         return text
 
 
+BED_ROUND_CANDS = 1 << 22  # kBedRoundCands (csrc/bed_device.hpp)
+
+
+def bed_intersect(a_ids, a_start, a_end, b_ids, b_start, b_end, n_groups=None, stream=None, round_cands: int = BED_ROUND_CANDS):
+    """BED intersection (pollen_amd.bed_intersect, without names or text) of entries on the device.  Entry i of a side has the
+    name id ids[i] (int32 CUDA tensor) and the interval [start[i], end[i]) (int64 CUDA tensors, read as u64).  b is grouped:
+    its ids never decrease and lie below n_groups (by default the last id + 1), file order kept inside a group; a's ids lie
+    below n_groups, or are -1 for a name b does not have.  Returns (a_index, b_index, start, end): one record per hit in the
+    reference's order -- a entry after a entry, inside one in b's order -- with start = the max of the two starts and end =
+    the min of the two ends.  The hits are found round_cands candidate pairs at a time, into scratch of that size.  Waits for
+    the stream once per round."""
+    torch = _torch()
+    for t in (a_ids, b_ids):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    for t in (a_start, a_end, b_start, b_end):
+        assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous()
+    n_a, n_b = int(a_ids.numel()), int(b_ids.numel())
+    assert a_start.numel() == a_end.numel() == n_a and b_start.numel() == b_end.numel() == n_b and round_cands >= 1
+    dev = a_ids.device
+    with torch.cuda.device(dev):
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        if n_groups is None:
+            n_groups = int(b_ids[-1].item()) + 1 if n_b else 0
+        L = _lib.lib()
+        job = ctypes.c_void_p()
+        cands, rounds, unsorted = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        parts = []
+        with torch.cuda.stream(st):  # (the outputs are the stream's: torch's allocator may hand their memory on behind it)
+            _check(L.flatgfa_dev_bed_begin(_ptr(a_ids), _ptr(a_start), _ptr(a_end), n_a, _ptr(b_ids), _ptr(b_start), _ptr(b_end), n_b,
+                                           int(n_groups), int(round_cands), ctypes.c_void_p(st.cuda_stream), ctypes.byref(job),
+                                           ctypes.byref(cands), ctypes.byref(rounds), ctypes.byref(unsorted)), "dev_bed_begin")
+            try:
+                room = min(cands.value, int(round_cands))
+                ai = torch.empty(room, dtype=torch.int32, device=dev)
+                bi = torch.empty(room, dtype=torch.int32, device=dev)
+                s = torch.empty(room, dtype=torch.int64, device=dev)
+                e = torch.empty(room, dtype=torch.int64, device=dev)
+                for r in range(rounds.value):
+                    n = ctypes.c_uint64()
+                    _check(L.flatgfa_dev_bed_round(job, r, _ptr(ai), _ptr(bi), _ptr(s), _ptr(e), ctypes.byref(n)), "dev_bed_round")
+                    parts.append(tuple(t[:n.value].clone() for t in (ai, bi, s, e)))
+            finally:
+                L.flatgfa_dev_bed_free(job)
+            if not parts:
+                parts.append((torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                              torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev)))
+            return tuple(torch.cat([p[k] for p in parts]) for k in range(4))
+
+
 def profile_enable(on: bool) -> None:
     _lib.lib().flatgfa_dev_profile_enable(1 if on else 0)
 

@@ -874,6 +874,52 @@ def seq_packed_info(packed: bytes) -> Tuple[int, int]:
     return bases.value, off.value
 
 
+# ---- BED intersection (flatgfa/src/cli/cmds.rs:392-413; `fgfa bed -a FILE -b FILE`) ----
+def _bed_text(x) -> bytes:
+    """BED text given as bytes, or as the path of a file that holds it."""
+    if isinstance(x, (str, os.PathLike)):
+        with open(x, "rb") as f:
+            return f.read()
+    return bytes(x)
+
+
+def bed_intersect(a, b) -> bytes:
+    """`fgfa bed -a A -b B`: for every entry of `a` in file order, the entries of `b` of the same name that overlap it, in
+    file order, cut to the overlap -- "name<TAB>start<TAB>end" lines, byte for byte the reference's -- found and formatted on
+    the GPU.  a and b are BED text (bytes) or paths."""
+    a, b = _bed_text(a), _bed_text(b)
+    p, n = ctypes.c_void_p(), ctypes.c_size_t()
+    _check(_lib.lib().flatgfa_bed_intersect(a, len(a), b, len(b), ctypes.byref(p), ctypes.byref(n)), "bed_intersect")
+    return _take_text(p, n)
+
+
+def bed_intersect_stream(a, b, write) -> None:
+    """flatgfa_bed_intersect_stream: `write(bytes)` receives the text of bed_intersect(a, b) in order, a piece at a time; never
+    called where there is no line to print.  A `write` that raises, or returns something true, stops the call."""
+    a, b = _bed_text(a), _bed_text(b)
+    raised = []
+
+    def sink(_ctx, ptr, n):
+        try:
+            return 1 if write(ctypes.string_at(ptr, n)) else 0  # (a piece is a few megabytes: within string_at's C int)
+        except BaseException as e:  # noqa: BLE001  (must not unwind through the C caller)
+            raised.append(e)
+            return 1
+    rc = _lib.lib().flatgfa_bed_intersect_stream(a, len(a), b, len(b), _lib.SINK_T(sink), None)
+    if raised:
+        raise raised[0]
+    _check(rc, "bed_intersect_stream")
+
+
+def bed_intersect_count(a, b) -> Tuple[int, int, int, int]:
+    """(lines, bytes, candidates, unsorted_groups) of bed_intersect(a, b) without its text: how long the text is, how many
+    pairs of entries were tried, and how many of b's name groups were walked whole because their starts are not in order."""
+    a, b = _bed_text(a), _bed_text(b)
+    out = [ctypes.c_uint64() for _ in range(4)]
+    _check(_lib.lib().flatgfa_bed_intersect_count(a, len(a), b, len(b), *[ctypes.byref(x) for x in out]), "bed_intersect_count")
+    return tuple(x.value for x in out)
+
+
 def format_float(x: float, digits: int) -> str:
     buf = ctypes.create_string_buffer(600)
     n = _lib.lib().flatgfa_format_float(x, digits, buf, 600)
