@@ -572,8 +572,13 @@ typedef struct flatgfa_dev_graph_t {
  * steps need, and reports an error -- or completes the call through the simple kernels -- rather
  * than a wrong answer when they no longer fit; what it does not re-check per step is that a path
  * the plan found strictly monotone still is (a compare per step: 12-18 % of the step scan on a
- * graph of such paths, profiles/NOTES.md R5.8), that a no-claim mark still holds, or that the
- * reversed copy of a short downward path still mirrors it.  A caller that DOES change step values
+ * graph of such paths, profiles/NOTES.md R5.8), that a no-claim mark still holds, that the
+ * reversed copy of a short downward path still mirrors it, or -- for a plan that reads the steps'
+ * run-length image (its description names run_image=<MiB> ... records=kept) -- that the steps are
+ * those the image and the run records were made of: such a plan turns the image into records in
+ * the first of a row of node-depth calls and counts the calls behind it from those records without
+ * reading the steps at all (no answer is kept: every call counts anew, into the caller's buffers;
+ * another kind of call, a status that reports anything, or changed steps end the row).  A caller that DOES change step values
  * under a live plan says so with flatgfa_dev_plan_steps_changed (below), which makes the plan
  * again from the steps as they are; FLATGFA_CHECK_NO_CLAIM=1 in the environment (read when a plan
  * is made; a debugging aid, three more reads of the steps per call) re-derives those facts before

@@ -1137,7 +1137,7 @@ __device__ __forceinline__ void accum_body(const AccArgs &A) {
         }
         uint32_t *c = A.counts + (size_t)win * A.n_slots + sl;
         uint32_t v = *c;
-        *c = 0u;
+        if (!A.keep) *c = 0u;  // (a call on kept records reads the plan's kept copy, which the next such call reads again)
         // where the sub-bucket starts (counted from wbase) and how much room it has
         uint32_t start = sl * A.cap, room = A.cap;
         if (A.pk) {

@@ -292,7 +292,29 @@ struct flatgfa_dev_plan {
     const char *run_off = "";          // ... and why not
     bool run_show = false;             // the description says which (plans the image is meant for by size, or the hook set)
     int run_hook = -1;                 // FLATGFA_RUN_IMAGE as it was when the plan was made (0, 1; -1: unset)
+    // Pass 1's records, kept across calls: the plan's scratch holds the records, `taken` and the kept
+    // cursors of a complete image call, enqueued on the plan's stream ahead of whatever comes next -- the next image call
+    // runs pass 2 alone.  Set by plan_fast_call behind an image call; dropped by every other call through the bucketed
+    // kernels, by plan_grow, with the plan's scratch (steps_changed), and by a status that reads anything but zero.
+    bool records_kept = false;
+    bool keep_records = true;          // FLATGFA_KEEP_RECORDS=0 as it was when the plan was made: every image call runs pass 1
 };
+
+// Every call of a plan through the bucketed kernels: it says whether the scratch holds an image call's records, and takes
+// note of what the call leaves there (any pass 1 but k_scan_runs writes other records into the same buckets).
+static int plan_fast_call(flatgfa_dev_plan_t *pl, uint32_t *depth_out, uint32_t *uniq_out, hipStream_t stream, const PathSums *ps = nullptr) {
+    RecordsUse ru;
+    ru.use = pl->keep_records && pl->records_kept;
+    pl->records_kept = false;
+    const int rc = fast_seg_depth(pl->fast, pl->g, depth_out, uniq_out, pl->status, stream, ps, &ru);
+    pl->records_kept = rc == FLATGFA_OK && pl->keep_records && ru.from_image;
+    return rc;
+}
+// ... and every change of its sub-buckets' room: the bucket array is another one behind it
+static bool plan_grow(flatgfa_dev_plan_t *pl, bool ahead_of_need = false) {
+    pl->records_kept = false;
+    return fast_plan_grow(&pl->fast, ahead_of_need);
+}
 
 // The Infinity Cache (256 MiB on MI355X) is one per device: what the plans of a process keep resident in it is
 // budgeted per device, first come first served, and given back when a plan is destroyed.
@@ -565,13 +587,28 @@ static void run_poll(flatgfa_dev_plan_t *pl, bool wait, bool may_start, hipStrea
         if (room > pl->fast.cap) {
             (void)hipDeviceSynchronize();
             for (int k = 0; k < 3 && room > pl->fast.cap && pl->fast.eligible && !pl->fast.cap_forced; ++k)
-                if (!fast_plan_grow(&pl->fast)) { pl->fast.eligible = true; break; }  // (a plan that cannot grow keeps k_scan and its buckets)
+                if (!plan_grow(pl)) { pl->fast.eligible = true; break; }  // (a plan that cannot grow keeps k_scan and its buckets)
             if (room > pl->fast.cap) { give_up("room"); return; }
         }
         // plain reads (they allocate in the Infinity Cache) while image, records and results fit what the steps' claim is budgeted against
         const int64_t traffic = (int64_t)run_image_bytes(pl->run->img) + 8ll * (int64_t)pl->g.n_segs + 8ll * (int64_t)pl->fast.est_records;
         const char *mall = getenv("FLATGFA_MALL_MB");
         const bool nt = traffic > (244ll << 20) || (mall && strtoull(mall, nullptr, 10) == 0);
+        // (the kept cursors: without them the plan reads the image as ever and keeps nothing)
+        pl->records_kept = false;
+        // (zeroed, and the zeroes there before any call: k_scan_runs writes the cursors of the workgroups it runs -- fewer
+        // than sub-buckets where the plan has fewer items -- and pass 2 reads every sub-bucket's)
+        if (pl->keep_records && !pl->fast.counts_kept) {
+            const size_t bytes = (size_t)pl->fast.n_win * pl->fast.n_slots * 4;
+            if (hipMalloc(&pl->fast.counts_kept, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                pl->fast.counts_kept = nullptr;
+            } else if (hipMemset(pl->fast.counts_kept, 0, bytes) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+                (void)hipGetLastError();
+                (void)hipFree(pl->fast.counts_kept);
+                pl->fast.counts_kept = nullptr;
+            }
+        }
         run_image_install(&pl->fast, pl->run->img, pl->run_item_ent, nt);
         pl->run_state = 3;
     }
@@ -679,7 +716,7 @@ struct TrialOutputs {
     uint32_t *depth, *uniq;
 };
 static int bucketed_query(flatgfa_dev_plan_t *pl, const TrialOutputs &out) {
-    return fast_seg_depth(pl->fast, pl->g, out.depth, out.uniq, pl->status, nullptr);
+    return plan_fast_call(pl, out.depth, out.uniq, nullptr);
 }
 
 // An even layout -- every sub-bucket as deep as the fullest -- that had to grow to gigabytes (paths that run along
@@ -722,13 +759,13 @@ static bool size_buckets(flatgfa_dev_plan_t *pl, const TrialOutputs &out, uint32
             *first_st |= st & 1u;
             *complete = !(st & (4u | 16u));
             if (!(st & 4u)) break;  // (an out-of-range id is reported by the query that meets it)
-            (void)fast_plan_grow(&pl->fast);
+            (void)plan_grow(pl);
         }
         plan_tick("sizing query");
         {   // ... and with headroom: k_scan deals its items to the workgroups as they come, so another call may
             // fill a sub-bucket that was half full this time to the brim (see flatgfa_dev_status)
             uint32_t fullest = 0;
-            if (hipMemcpy(&fullest, pl->status + 2, 4, hipMemcpyDeviceToHost) == hipSuccess && fullest && pl->fast.eligible) (void)fast_plan_grow(&pl->fast, true);
+            if (hipMemcpy(&fullest, pl->status + 2, 4, hipMemcpyDeviceToHost) == hipSuccess && fullest && pl->fast.eligible) (void)plan_grow(pl, true);
             (void)hipMemset(pl->status, 0, 12);
         }
         plan_tick("headroom");
@@ -908,6 +945,8 @@ static bool plan_build_fast(flatgfa_dev_plan_t *pl, uint32_t *first_depth, uint3
     // ... and so is the run-length image of the steps (run_poll), for the plans the rule gives one (FLATGFA_RUN_IMAGE=0|1: none / whatever the size)
     const char *hook = test_hook("FLATGFA_RUN_IMAGE");
     pl->run_hook = hook ? (hook[0] == '1' ? 1 : 0) : -1;
+    const char *keep = test_hook("FLATGFA_KEEP_RECORDS");  // (0: every image call runs pass 1)
+    pl->keep_records = !(keep && keep[0] == '0');
     return true;
 }
 
@@ -983,6 +1022,7 @@ static void plan_release_fast(flatgfa_dev_plan_t *pl, bool steps_changed = false
     pl->marks.clear();
     run_release(pl, steps_changed);
     release_cache_claim(pl);
+    pl->records_kept = false;
     fast_plan_destroy(&pl->fast);
 }
 
@@ -1066,7 +1106,7 @@ extern "C" int flatgfa_dev_seg_depth(flatgfa_dev_plan_t *pl, uint32_t *depth_out
             const int rc = fast_check_plan_facts(pl->fast, g, pl->hb.data(), pl->he.data(), pl->status, stream);
             if (rc) return rc;
         }
-        const int rc = fast_seg_depth(pl->fast, g, depth_out, uniq_out, pl->status, stream);
+        const int rc = plan_fast_call(pl, depth_out, uniq_out, stream);
         if (rc == FLATGFA_OK) run_start_behind(pl, stream);
         return rc;
     }
@@ -1122,7 +1162,7 @@ static int path_depth_all_enqueue(flatgfa_dev_plan_t *pl, uint32_t *depth_out, u
     if (use_fast && fast_plan_want_path_sums(&pl->fast)) {
         // pass 2 adds up the paths k_scan walked; the wave-per-path kernels' paths take the gather kernel
         const PathSums ps{length_out, weighted_out, true};
-        int rc = fast_seg_depth(pl->fast, g, depth_out, nullptr, pl->status, stream, &ps);
+        int rc = plan_fast_call(pl, depth_out, nullptr, stream, &ps);
         if (rc) return rc;
         if (pl->fast.n_other) rc = path_sums_launch(pl, pl->fast.other_ids, pl->fast.n_other, depth_out, length_out, weighted_out, 1u, stream);
         return rc;
@@ -1132,7 +1172,7 @@ static int path_depth_all_enqueue(flatgfa_dev_plan_t *pl, uint32_t *depth_out, u
         FGFA_HIP_OR(hipMemsetAsync(length_out, 0, (size_t)g.n_paths * 8, stream), return FLATGFA_ERR_HIP);
         FGFA_HIP_OR(hipMemsetAsync(weighted_out, 0, (size_t)g.n_paths * 8, stream), return FLATGFA_ERR_HIP);
     }
-    int rc = use_fast ? fast_seg_depth(pl->fast, g, depth_out, nullptr, pl->status, stream)
+    int rc = use_fast ? plan_fast_call(pl, depth_out, nullptr, stream)
                       : atomic_seg_depth(pl, depth_out, nullptr, stream);
     if (rc) return rc;
     if (!pl->all_ids) {
@@ -1190,6 +1230,9 @@ extern "C" int flatgfa_dev_status(flatgfa_dev_plan_t *pl, void *stream_) {
         FGFA_HIP_OR(hipMemcpyAsync(st3, pl->status, 12, hipMemcpyDeviceToHost, stream), return FLATGFA_ERR_HIP);
         FGFA_HIP_OR(hipStreamSynchronize(stream), return FLATGFA_ERR_HIP);
         const uint32_t st = st3[0];
+        // (a flag, or a sub-bucket more than half full: the next image call runs pass 1 again -- on buckets that may have grown
+        // here, and raising again what a call on kept records cannot, an out-of-range id among the steps)
+        if (st3[0] || st3[2]) pl->records_kept = false;
         const uint32_t n_calls = pl->calls_since_status;
         if (attempt == 0) {
             pl->calls_since_status = 0;
@@ -1201,7 +1244,7 @@ extern "C" int flatgfa_dev_status(flatgfa_dev_plan_t *pl, void *stream_) {
             // twice as much when two of a workgroup's items meet in a window.  Make room now (no call
             // is in flight), not when a call enqueued among others has already run out.
             FGFA_HIP_OR(hipMemsetAsync(pl->status + 2, 0, 4, stream), return FLATGFA_ERR_HIP);
-            if (!(st & (4u | 16u)) && pl->fast.eligible) (void)fast_plan_grow(&pl->fast, true);  // (a plan at its limit stays as it is)
+            if (!(st & (4u | 16u)) && pl->fast.eligible) (void)plan_grow(pl, true);  // (a plan at its limit stays as it is)
         }
         if (!st) return FLATGFA_OK;
         FGFA_HIP_OR(hipMemsetAsync(pl->status, 0, 4, stream), return FLATGFA_ERR_HIP);
@@ -1237,11 +1280,11 @@ extern "C" int flatgfa_dev_status(flatgfa_dev_plan_t *pl, void *stream_) {
             return FLATGFA_ERR_HIP;
         }
         int rc;
-        const bool grown = !(st & 16u) && fast_plan_grow(&pl->fast);  // (a full hand-back list is not a matter of bucket room)
+        const bool grown = !(st & 16u) && plan_grow(pl);  // (a full hand-back list is not a matter of bucket room)
         if (st & 16u) pl->fast.eligible = false;  // (later calls take the atomic kernels right away)
         if (!grown) pl->last_fast = false;
         if (pl->last_len) rc = path_depth_all_enqueue(pl, pl->last_depth, pl->last_len, pl->last_weighted, stream, grown);
-        else if (grown) rc = fast_seg_depth(pl->fast, pl->g, pl->last_depth, pl->last_uniq, pl->status, stream);
+        else if (grown) rc = plan_fast_call(pl, pl->last_depth, pl->last_uniq, stream);
         else rc = atomic_seg_depth(pl, pl->last_depth, pl->last_uniq, stream);
         if (rc) return rc;
     }
@@ -1279,7 +1322,8 @@ extern "C" int flatgfa_dev_plan_describe(flatgfa_dev_plan_t *pl, char *out, int 
             if (pl->run_state == 3) {  // (its size in MB, the steps it was made of, the plans that hold it now, how k_scan_runs reads it)
                 std::lock_guard<std::mutex> lk(g_run_mu);
                 s += " run_image=" + std::to_string((run_image_bytes(pl->run->img) + (1u << 20) - 1) >> 20) + " run_image_steps=" + std::to_string(pl->run->n_steps) +
-                     " run_image_plans=" + std::to_string(pl->run->users) + " run_image_reads=" + (f.run_nt ? "nt" : "plain");
+                     " run_image_plans=" + std::to_string(pl->run->users) + " run_image_reads=" + (f.run_nt ? "nt" : "plain") +
+                     " records=" + (pl->keep_records && f.counts_kept ? "kept" : "rewritten");  // (pass 1 once per run of image calls, or in every call)
             } else {
                 s += std::string(" run_image=off(") + (pl->run_state < 0 ? pl->run_off : "pending") + ")";
             }

@@ -473,7 +473,7 @@ int alloc_buckets(FastPlan *fp, uint64_t want_cap) {
 }  // namespace
 
 static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t *depth_out, uint32_t *uniq_out,
-                     uint32_t *status, hipStream_t stream, const PathSums *ps, bool count_only);
+                     uint32_t *status, hipStream_t stream, const PathSums *ps, bool count_only, RecordsUse *records = nullptr);
 static thread_local uint32_t t_scan_workgroups = 0;  // fast_plan_create's `scan_workgroups`, for the ranges it makes
 static thread_local bool t_prefer_packed = false;    // ... and its `prefer_packed`
 
@@ -1733,14 +1733,14 @@ void fast_plan_destroy(FastPlan *fp) {
     for (void *p : {(void *)fp->counts, (void *)fp->counts0, (void *)fp->buckets, (void *)fp->dir, (void *)fp->islot, (void *)fp->lists_slab,
                     (void *)fp->items, (void *)fp->short_items,
                     (void *)fp->medium_items, (void *)fp->tiny_items, (void *)fp->rev_steps, (void *)fp->work_counter, (void *)fp->other_ids, (void *)fp->psum_part,
-                    (void *)fp->pair_part, (void *)fp->pair_flag, (void *)fp->taken, (void *)fp->pk_off, (void *)fp->pk_base, (void *)fp->pk, (void *)fp->cflags})
+                    (void *)fp->pair_part, (void *)fp->pair_flag, (void *)fp->taken, (void *)fp->pk_off, (void *)fp->pk_base, (void *)fp->pk, (void *)fp->cflags, (void *)fp->counts_kept})
         if (p) (void)hipFree(p);
     *fp = FastPlan();
 }
 
 // One range of the graph: the outputs are the range's own stretch of the result vectors.
 static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t *depth_out, uint32_t *uniq_out,
-                     uint32_t *status, hipStream_t stream, const PathSums *ps, bool count_only) {
+                     uint32_t *status, hipStream_t stream, const PathSums *ps, bool count_only, RecordsUse *records) {
     if (ps && (uniq_out || fp.wb != 12 || !g.seg_len || !fp.psum_part || fp.n_range != g.n_segs)) {
         set_error("fast_seg_depth: path sums ride on seg_depth with 4096-segment windows only");
         return FLATGFA_ERR_ARG;
@@ -1810,7 +1810,7 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
                fp.work_counter, scan_skip ? 0u : fp.max_back, depth_out, uniq_out, status, fp.dbg,
                reinterpret_cast<const uint4 *>(fp.items), g.seg_len, ps ? reinterpret_cast<ulonglong2 *>(fp.psum_part) : nullptr,
                fp.fat_off, fp.fat_woff, fp.acc_parts, tagged ? fp.n_shared : 0u, nullptr, fp.pair_part, fp.pair_flag, fp.accumulate ? 1u : 0u, test_hook("FLATGFA_NO_PLAIN") ? nullptr : fp.taken, fp.taken ? fp.taken + fp.n_slots : nullptr,
-               fp.packed ? reinterpret_cast<const uint2 *>(fp.pk) : nullptr};  // (FLATGFA_NO_PLAIN: measurements)
+               fp.packed ? reinterpret_cast<const uint2 *>(fp.pk) : nullptr, 0u};  // (FLATGFA_NO_PLAIN: measurements)
 #ifdef FGFA_MEASURE
     if (const char *sk = test_hook("FLATGFA_ACC_SKIP")) aa.dbg = (uint32_t)strtoul(sk, nullptr, 10);  // (diagnostic: pass 2 without its revisit counts 128 / depth 256 / claims 64 / words behind the first 1024)
 #endif
@@ -1861,14 +1861,22 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
             if (hipMemsetAsync(ps->weighted_out, 0, (size_t)g.n_paths * 8, stream) != hipSuccess) return FLATGFA_ERR_HIP;
         }
     }
-    if (grid) {
+    // (a tagged call of a plan with the steps' run-length image installed reads that: no plan that is given one has dense
+    // pass 1, packed buckets, ranges, marks or wave-per-path lists)
+    const bool from_image = grid && tagged && fp.run_ent && fp.run_item_ent && !count_only && !fp.dense && !fp.packed && !sa.ranged && !sa.cflags && !has_pre && !fp.dbg;
+    // ... and where the records of the image call before this one are still in the scratch (RecordsUse: the handle knows), it
+    // would write the same records into the same slots: pass 1 is left out, pass 2 reads the kept cursors and leaves them.
+    const bool kept = from_image && records && records->use && fp.counts_kept;
+    if (records) records->from_image = from_image && fp.counts_kept;
+    if (kept) {
+        aa.counts = fp.counts_kept;
+        aa.keep = 1u;
+    }
+    if (grid && !kept) {
         if (fp.acc_parts > 1 && !fp.accumulate && !count_only) {  // (a later group of paths adds to what is there)
             sa.zero_a = depth_out;
             sa.zero_b = uniq_out;
         }
-        // (a tagged call of a plan with the steps' run-length image installed reads that: no plan that is given one has dense
-        // pass 1, packed buckets, ranges, marks or wave-per-path lists)
-        const bool from_image = tagged && fp.run_ent && fp.run_item_ent && !count_only && !fp.dense && !fp.packed && !sa.ranged && !sa.cflags && !has_pre && !fp.dbg;
         ProfScope pscope(from_image ? "k_scan_runs" : fp.dense ? "k_scan_dense" : "k_scan", stream);
         if (from_image) {
             launch_scan_runs(fp, sa, grid, stream);
@@ -1878,7 +1886,7 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
         }
     }
     if (count_only) return hipGetLastError() == hipSuccess ? FLATGFA_OK : FLATGFA_ERR_HIP;  // (the counting call of a packed plan: pass 1 alone)
-    if (fp.acc_parts > 1 && !grid && !fp.accumulate) {  // the window's workgroups add to the outputs: cleared by k_scan, or here when it does not run
+    if (fp.acc_parts > 1 && (!grid || kept) && !fp.accumulate) {  // the window's workgroups add to the outputs: cleared by k_scan, or here when it does not run
         ProfScope pscope("memset_outputs", stream);
         if (hipMemsetAsync(depth_out, 0, (size_t)fp.n_range * 4, stream) != hipSuccess) return FLATGFA_ERR_HIP;
         if (uniq_out && hipMemsetAsync(uniq_out, 0, (size_t)fp.n_range * 4, stream) != hipSuccess) return FLATGFA_ERR_HIP;
@@ -1961,8 +1969,9 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
 }
 
 int fast_seg_depth(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t *depth_out, uint32_t *uniq_out,
-                   uint32_t *status, hipStream_t stream, const PathSums *ps) {
-    int rc = run_range(fp, g, depth_out, uniq_out, status, stream, ps, false);
+                   uint32_t *status, hipStream_t stream, const PathSums *ps, RecordsUse *records) {
+    if (records) records->from_image = false;
+    int rc = run_range(fp, g, depth_out, uniq_out, status, stream, ps, false, records);  // (a plan with further ranges is given no image)
     for (uint32_t r = 0; r < fp.n_more && rc == FLATGFA_OK; ++r) {
         const FastPlan &q = fp.more[r];
         rc = run_range(q, g, depth_out + q.seg_base, uniq_out ? uniq_out + q.seg_base : nullptr, status, stream, nullptr, false);

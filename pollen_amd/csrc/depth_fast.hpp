@@ -130,6 +130,17 @@ struct FastPlan {
     const void *run_item_ent = nullptr;  // uint2[n_items] the entries each item reads
     uint32_t run_n_ent = 0;
     bool run_nt = false;                 // the entries are read past the caches (they do not fit the Infinity Cache beside the records)
+    // u32[n_win * n_slots] the cursors k_scan_runs left, a second time: pass 2 zeroes `counts` behind every call, a call that
+    // runs on the records of the image call before it (RecordsUse) reads these and leaves them.  nullptr: records are never kept.
+    uint32_t *counts_kept = nullptr;
+};
+
+// What a plan's handle tells a call about the records in the plan's scratch, and what the call tells it back.  k_scan_runs'
+// deal of the items is fixed and so is the image, so an image call writes the same records into the same slots as the image
+// call before it: where nothing else has written to the scratch since (the handle's business), pass 1 is left out.
+struct RecordsUse {
+    bool use = false;         // in: buckets, `taken` and counts_kept are those of a complete image call of this plan
+    bool from_image = false;  // out: this call was an image call of a plan with counts_kept -- they are (still) there behind it
 };
 
 // A plan's ranges and path groups, one after the other: the first plan itself, then more[0 .. n_more).  `Plan` is FastPlan or
@@ -222,8 +233,9 @@ struct PathSums {
 // Allocates (once) the scratch `ps` needs; false = not possible for this plan.
 bool fast_plan_want_path_sums(FastPlan *fp);
 // Enqueues the kernels.  uniq_out may be NULL (seg_depth); `ps` only with uniq_out == NULL and
-// after fast_plan_want_path_sums.
+// after fast_plan_want_path_sums.  `records`: see RecordsUse; nullptr = pass 1 runs, and the caller must take its
+// scratch for overwritten.
 int fast_seg_depth(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t *depth_out, uint32_t *uniq_out,
-                   uint32_t *status, hipStream_t stream, const PathSums *ps = nullptr);
+                   uint32_t *status, hipStream_t stream, const PathSums *ps = nullptr, RecordsUse *records = nullptr);
 
 }  // namespace fgfa_dev

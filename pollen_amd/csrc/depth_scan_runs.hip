@@ -153,6 +153,7 @@ struct RunScanArgs {
     const uint2 *ent;       // the image's entries
     const uint2 *item_ent;  // [n_items] which of them each item reads
     uint32_t n_ent;
+    uint32_t *counts_kept;  // [n_win][n_slots] a second copy of the cursors this call leaves (FastPlan::counts_kept), or null
 };
 
 struct RunsWave {
@@ -160,7 +161,7 @@ struct RunsWave {
 };
 
 constexpr int kRunsWide = 4;  // chunks of 64 entries a wave takes at a time
-// The kernel needs 17 KB of LDS and 49 registers: two of its workgroups fit a CU, and where the dispatcher puts two on one, both
+// The kernel needs 17 KB of LDS and 50 registers: two of its workgroups fit a CU, and where the dispatcher puts two on one, both
 // run at half speed -- with a fixed deal nobody takes their items off them.  It asks for more than half a CU's LDS instead:
 // one workgroup per CU, as k_scan (cfg-L, three calls in flight, same box: 0.0704-0.0747 -> 0.0687-0.0702 ms per call).
 #ifndef FGFA_RUNS_LDS_MIN
@@ -324,7 +325,11 @@ __global__ __launch_bounds__(kThreads) void k_scan_runs(const ScanArgs A, const 
         er = next_er;
     }
     __syncthreads();
-    for (uint32_t wdw = threadIdx.x; wdw < A.n_win; wdw += kThreads) A.counts[(size_t)wdw * A.n_slots + blockIdx.x] = bcur[wdw];
+    // (the cursors twice: pass 2 zeroes `counts` as it reads them, the kept copy stays for the calls that run pass 2 alone)
+    for (uint32_t wdw = threadIdx.x; wdw < A.n_win; wdw += kThreads) {
+        A.counts[(size_t)wdw * A.n_slots + blockIdx.x] = bcur[wdw];
+        if (R.counts_kept) R.counts_kept[(size_t)wdw * A.n_slots + blockIdx.x] = bcur[wdw];
+    }
     if (threadIdx.x == 0) {
         A.taken[blockIdx.x] = rr;
         if (run_item_of(rr, blockIdx.x, gridDim.x) < n_items) atomicOr(A.status, kStBackOverflow);  // (out of private tags with items left: the plan's rule keeps such plans away)
@@ -530,7 +535,7 @@ void launch_scan_runs(const FastPlan &fp, const ScanArgs &sa, uint32_t grid, hip
             return good;
         });
     }
-    const RunScanArgs ra{reinterpret_cast<const uint2 *>(fp.run_ent), reinterpret_cast<const uint2 *>(fp.run_item_ent), fp.run_n_ent};
+    const RunScanArgs ra{reinterpret_cast<const uint2 *>(fp.run_ent), reinterpret_cast<const uint2 *>(fp.run_item_ent), fp.run_n_ent, fp.counts_kept};
     if (sa.big && fp.run_nt) hipLaunchKernelGGL((k_scan_runs<true, true>), g, b, lds, stream, sa, ra);
     else if (sa.big) hipLaunchKernelGGL((k_scan_runs<true, false>), g, b, lds, stream, sa, ra);
     else if (fp.run_nt) hipLaunchKernelGGL((k_scan_runs<false, true>), g, b, lds, stream, sa, ra);
