@@ -148,11 +148,13 @@ def five_calls(plan, n_segs, want, runs=1, uniq=True):
     return prof
 
 
-def plan_of(pools):
+def plan_of(pools, seg_len=False):
+    """The graph on the device (with the segments' lengths: `seg_len`), a plan for it, the number of segments."""
     from pollen_amd.device import DepthPlan, DeviceGraph
     n_segs = len(pools.segs)
     begins, ends = spans_of(pools)
-    graph = DeviceGraph(pools.steps, begins, ends, n_segs)
+    lens = np.ascontiguousarray(pools.seg_lens(), dtype=np.uint32) if seg_len else None
+    graph = DeviceGraph(pools.steps, begins, ends, n_segs, lens)
     return graph, DepthPlan(graph), n_segs
 
 
