@@ -43,7 +43,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <queue>
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
@@ -53,6 +52,8 @@
 #include <vector>
 
 #include "depth_fast_kernels.hpp"
+#include "depth_plan_host.hpp"
+#include "device_scan.hpp"
 #include "temp_arena.hpp"
 #include "host_copy.hpp"
 #include "prof.hpp"
@@ -488,6 +489,192 @@ static inline bool measure_switch(const char *name) {
 #endif
 }
 
+// The test hooks a range's plan looks at (tests and measurements: they change which kernels run, never what they
+// count), read once per range: the values as given where a stage parses them, the plain switches as booleans.
+struct RangeHooks {
+    const char *wb = test_hook("FLATGFA_WB");                      // 11, 12 or 13: the widths pass 2 has builds for; anything else is not a width
+    const char *scan_wgs = test_hook("FLATGFA_SCAN_WGS");          // pass 1's persistent workgroups
+    const char *short_max = test_hook("FLATGFA_SHORT_MAX");
+    const char *count_pieces = test_hook("FLATGFA_COUNT_PIECES");
+    const char *piece_steps = test_hook("FLATGFA_PIECE_STEPS");
+    const char *acc_parts = test_hook("FLATGFA_ACC_PARTS");
+    const char *tag_limit = test_hook("FLATGFA_TAG_LIMIT");        // fewer tags per workgroup
+    const char *bucket_cap = test_hook("FLATGFA_BUCKET_CAP");      // force the overflow route
+    const char *packed_ask = test_hook("FLATGFA_PACKED_ASK");      // small graphs ask the counting call too
+    const char *dense = test_hook("FLATGFA_DENSE");
+    const char *acc_slots = test_hook("FLATGFA_ACC_SLOTS");
+    const char *acc_own = test_hook("FLATGFA_ACC_OWN");
+    bool claim_all = false;                                         // FLATGFA_NO_CLAIM=0: every path and item claims, monotone or not
+    bool tagged_off = false;                                        // FLATGFA_TAGGED=0 keeps the directory
+    bool short_any = test_hook("FLATGFA_SHORT_ANY") != nullptr;    // let k_scan_short find out and hand back
+    bool no_tiny = test_hook("FLATGFA_NO_TINY") != nullptr;        // tiny paths go to k_scan_short as before
+    bool tag_mean_only = test_hook("FLATGFA_TAG_MEAN_ONLY") != nullptr;
+    bool marks_off = test_hook("FLATGFA_NO_CLAIM_BLOCKS_OFF") != nullptr;
+    bool marks_always = test_hook("FLATGFA_NO_CLAIM_BLOCKS_MIN") != nullptr;  // asks for the marks regardless of what they may gain
+    RangeHooks() {
+        const char *nc = test_hook("FLATGFA_NO_CLAIM"), *t = test_hook("FLATGFA_TAGGED");
+        claim_all = nc && nc[0] == '0';
+        tagged_off = t && t[0] == '0';
+    }
+};
+
+// hipMalloc and staged_copy of a vector
+template <class P, class T>
+static bool upload(P **dst, const Vec<T> &v) {
+    FAST_TRY(hipMalloc(dst, v.size() * sizeof(T)));
+    FAST_TRY(staged_copy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, nullptr));
+    return true;
+}
+
+// The even layout: `cap` records (four at least) for every sub-bucket.  1 = allocated, 0 = not to be had (the plan stays
+// ineligible; the caller's destroy releases what was allocated), -1 = a HIP error.
+static int even_buckets(FastPlan *fp, uint64_t cap) {
+    const int rc = alloc_buckets(fp, std::max<uint64_t>(cap, 4));
+    if (rc == 1) fp->bucket_records = ((uint64_t)fp->n_win * fp->n_slots + fp->n_slots) * (uint64_t)fp->cap;
+    return rc;
+}
+
+// Which kernel walks a path depends on how many runs it has: short paths must fit the run queue,
+// paths with at most kMediumRuns runs are walked wave by wave too, by pairs of waves that share a
+// bigger hash set (k_scan_short's medium variant).  The counts come from a one-off kernel.
+struct RunFacts {
+    Vec<uint32_t> runs, runs_down, mono, ext;  // (ext: six facts per path, see k_count_runs; for up to 2^18 paths)
+};
+static bool count_runs(const flatgfa_dev_graph_t &g, const uint32_t *hb, const uint32_t *he, uint32_t n_cus, const RangeHooks &hooks, RunFacts *out) {
+    // (counted over the spans this plan walks -- a plan may be given others than the graph's own)
+    DeviceMem tmp;
+    uint32_t *d_runs = nullptr;
+    const size_t np = g.n_paths;
+    const bool want_ext = np <= (1u << 18) && !measure_switch("FLATGFA_NO_ITEM_DIRS");
+    // (device layout: [runs | runs_down | mono | ext x 6 | begin | end], np words each: one copy in, one copy out)
+    const size_t n_out = want_ext ? 9 : 3;
+    FAST_TRY(tmp.alloc(&d_runs, np * (n_out + 2)));
+    Vec<uint32_t> spans(2 * np);
+    std::copy(hb, hb + np, spans.begin());
+    std::copy(he, he + np, spans.begin() + (ptrdiff_t)np);
+    FAST_TRY(staged_copy(d_runs + n_out * np, spans.data(), np * 8, hipMemcpyHostToDevice, nullptr));
+    // (few long paths: several pieces each, so that the kernel fills the chip -- the pieces add to cleared words)
+    uint32_t pieces = 1;
+    if (want_ext && np < n_cus * 8u && g.n_steps / np >= (1u << 16)) pieces = std::min<uint32_t>((n_cus * 8u + (uint32_t)np - 1u) / (uint32_t)np, 4096u);
+    if (hooks.count_pieces) pieces = want_ext ? (uint32_t)std::min(std::max(1, atoi(hooks.count_pieces)), 4096) : 1u;
+    if (pieces > 1) FAST_TRY(hipMemsetAsync(d_runs, 0, n_out * np * 4, nullptr));
+    hipLaunchKernelGGL(k_count_runs, dim3(std::min<uint32_t>(g.n_paths, n_cus * 8u), pieces), dim3(256), 0, nullptr, g.steps,
+                       d_runs + n_out * np, d_runs + (n_out + 1) * np, g.n_paths, g.n_steps, d_runs, d_runs + np, d_runs + 2 * np,
+                       want_ext ? d_runs + 3 * np : nullptr);
+    Vec<uint32_t> got(n_out * np);
+    FAST_TRY(staged_copy(got.data(), d_runs, n_out * np * 4, hipMemcpyDeviceToHost, nullptr));
+    out->runs.assign(got.begin(), got.begin() + (ptrdiff_t)np);
+    out->runs_down.assign(got.begin() + (ptrdiff_t)np, got.begin() + (ptrdiff_t)(2 * np));
+    out->mono.assign(got.begin() + (ptrdiff_t)(2 * np), got.begin() + (ptrdiff_t)(3 * np));
+    if (want_ext) out->ext.assign(got.begin() + (ptrdiff_t)(3 * np), got.end());
+    if (pieces > 1) {  // (no one piece knows: a path is monotone when all of its pairs ascend or all of them descend)
+        for (size_t p = 0; p < np; ++p) {
+            const uint32_t pairs = he[p] > hb[p] ? he[p] - hb[p] - 1u : 0u;
+            out->mono[p] = (he[p] > hb[p] && (out->ext[6 * p] == pairs || out->ext[6 * p + 1] == pairs)) ? 1u : 0u;
+        }
+    }
+    if (hooks.claim_all) std::fill(out->mono.begin(), out->mono.end(), 0u);
+    return true;
+}
+
+// The segment each of the whole paths starts at: what the counting kernel saw, or k_first_ids.
+static bool first_ids(const flatgfa_dev_graph_t &g, const Vec<uint4> &whole, const Vec<uint32_t> &ext, Vec<uint32_t> *first) {
+    const size_t n = whole.size();
+    first->assign(n, 0u);
+    if (!ext.empty()) {  // (the counting kernel looked already)
+        for (size_t i = 0; i < n; ++i) (*first)[i] = ext[6 * (size_t)whole[i].w + 4];
+        return true;
+    }
+    Vec<uint32_t> at(n);
+    for (size_t i = 0; i < n; ++i) at[i] = whole[i].x;
+    DeviceMem tmp;
+    uint32_t *d_at = nullptr;
+    FAST_TRY(tmp.alloc(&d_at, n * 2));
+    FAST_TRY(staged_copy(d_at, at.data(), n * 4, hipMemcpyHostToDevice, nullptr));
+    hipLaunchKernelGGL(k_first_ids, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, nullptr, g.steps, d_at, (uint32_t)n, d_at + n);
+    FAST_TRY(staged_copy(first->data(), d_at + n, n * 4, hipMemcpyDeviceToHost, nullptr));
+    return true;
+}
+
+// The reversed copies of the paths a wave-per-path kernel reads backwards (fp->rev_steps), made here once.
+static bool reverse_copies(const flatgfa_dev_graph_t &g, const Vec<uint4> &rev_list, uint64_t rev_len, FastPlan *fp) {
+    fp->n_rev_steps = (uint32_t)(rev_len + 1024);  // (a block is read whole)
+    FAST_TRY(hipMalloc(&fp->rev_steps, (size_t)fp->n_rev_steps * 4));
+    FAST_TRY(hipMemset(fp->rev_steps, 0, (size_t)fp->n_rev_steps * 4));
+    DeviceMem tmp;
+    uint4 *d_list = nullptr;
+    FAST_TRY(tmp.alloc(&d_list, rev_list.size()));
+    FAST_TRY(staged_copy(d_list, rev_list.data(), rev_list.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr));
+    hipLaunchKernelGGL(k_reverse_copy, dim3(std::min<uint32_t>((uint32_t)rev_list.size(), fp->n_cus * 8u)), dim3(256), 0, nullptr,
+                       g.steps, d_list, (uint32_t)rev_list.size(), fp->rev_steps);
+    FAST_TRY(hipDeviceSynchronize());
+    return true;
+}
+
+// k_item_dirs over the items on the device: which way each runs (items[].z), the two counts, and the no-claim bit -- of whole
+// paths the kernel's, of the pieces of split paths the host's (mark_noclaim_pieces); fp->n_noclaim says how many carry it.
+static bool item_dirs(const flatgfa_dev_graph_t &g, FastPlan *fp, bool claim_all, ItemFacts *facts) {
+    const size_t bytes = (size_t)fp->n_items * sizeof(uint4);
+    uint4 *d_items = reinterpret_cast<uint4 *>(fp->items);
+    DeviceMem tmp;
+    unsigned long long *d_counts = nullptr, counted[2] = {0, 0};
+    FAST_TRY(tmp.alloc(&d_counts, 2));
+    FAST_TRY(hipMemset(d_counts, 0, 16));
+    uint4 *d_mono = nullptr;
+    if (fp->n_shared && !claim_all) FAST_TRY(tmp.alloc(&d_mono, fp->n_items));
+    hipLaunchKernelGGL(k_item_dirs, dim3(std::min<uint32_t>(fp->n_items, fp->n_cus * 8u)), dim3(256), 0, nullptr, g.steps, d_items, fp->n_items, d_counts, d_mono);
+    FAST_TRY(staged_copy(counted, d_counts, 16, hipMemcpyDeviceToHost, nullptr));
+    facts->records = counted[0];
+    facts->against = counted[1];
+    Vec<uint4> items;  // as the kernel left them
+    if (d_mono || claim_all) {
+        items.resize(fp->n_items);
+        FAST_TRY(staged_copy(items.data(), d_items, bytes, hipMemcpyDeviceToHost, nullptr));
+    }
+    if (claim_all) {
+        for (uint4 &it : items) it.z &= ~kItemNoClaim;
+        FAST_TRY(staged_copy(d_items, items.data(), bytes, hipMemcpyHostToDevice, nullptr));
+        return true;
+    }
+    if (d_mono) {
+        Vec<uint4> mono(fp->n_items);
+        FAST_TRY(staged_copy(mono.data(), d_mono, bytes, hipMemcpyDeviceToHost, nullptr));
+        if (mark_noclaim_pieces(&items, mono, fp->n_shared)) FAST_TRY(staged_copy(d_items, items.data(), bytes, hipMemcpyHostToDevice, nullptr));
+    } else {  // how many there are (flatgfa_dev_plan_describe: no_claim_items)
+        items.resize(fp->n_items);
+        FAST_TRY(staged_copy(items.data(), d_items, bytes, hipMemcpyDeviceToHost, nullptr));
+    }
+    for (const uint4 &it : items) fp->n_noclaim += it.z >> 31;
+    return true;
+}
+
+// The counting call of packed buckets: k_scan alone, every sub-bucket without room (all records go to a sink), the
+// items dealt in the fixed order every later call uses.  Its cursors (*cnt) are the layout; *st is its status word.
+static bool counting_call(const flatgfa_dev_graph_t &g, FastPlan *fp, Vec<uint32_t> *cnt, uint32_t *st) {
+    const size_t row = (size_t)fp->n_win + 1, slots = (size_t)fp->n_win * fp->n_slots;
+    DeviceMem tmp;
+    uint32_t *d_status = nullptr;
+    FAST_TRY(hipMalloc(&fp->pk_off, row * fp->n_slots * 4));
+    FAST_TRY(hipMemset(fp->pk_off, 0, row * fp->n_slots * 4));
+    FAST_TRY(hipMalloc(&fp->pk_base, (size_t)fp->n_slots * 8));
+    FAST_TRY(hipMemset(fp->pk_base, 0, (size_t)fp->n_slots * 8));
+    FAST_TRY(hipMalloc(&fp->buckets, 4096));
+    FAST_TRY(tmp.alloc(&d_status, 64));
+    FAST_TRY(hipMemset(d_status, 0, 256));
+    fp->packed = true;
+    fp->cap = 0;
+    fp->eligible = true;
+    fp->lds_bytes_scan = scan_lds_bytes(fp->nwp, true, true);
+    const int rc = run_range(*fp, g, nullptr, nullptr, d_status, nullptr, nullptr, true);
+    fp->eligible = false;
+    cnt->resize(slots);
+    FAST_TRY(rc == FLATGFA_OK ? hipDeviceSynchronize() : hipErrorUnknown);
+    FAST_TRY(staged_copy(cnt->data(), fp->counts, slots * 4, hipMemcpyDeviceToHost, nullptr));
+    FAST_TRY(hipMemset(fp->counts, 0, slots * 4));
+    FAST_TRY(staged_copy(st, d_status, 4, hipMemcpyDeviceToHost, nullptr));
+    return true;
+}
+
 // The plan of one range of segments, [seg_base, seg_base + n_range): the whole graph, or one of
 // the ranges of a graph beyond 16 M segments.
 static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const uint32_t *he, FastPlan *fp, uint32_t seg_base,
@@ -495,13 +682,14 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
     *fp = FastPlan();
     fp->seg_base = seg_base;
     fp->n_range = n_range;
+    const RangeHooks hooks;
     const bool ranged = seg_base != 0 || n_range != g.n_segs;
     // Windows of 4096 segments up to 4 M segments, of 8192 beyond (pass 2 keeps a window's
     // difference array and per-path bitsets in LDS).
     uint32_t wb = g.n_segs <= 1024u * 4096u ? 12u : 13u;
     if (force_wb) wb = force_wb;  // (fast_plan_create: 4096-segment windows on a larger graph, for the sake of its split paths)
-    if (const char *f = test_hook("FLATGFA_WB")) {  // (11, 12 or 13: the widths pass 2 has builds for; anything else is not a width)
-        const uint32_t asked = (uint32_t)strtoul(f, nullptr, 10);
+    if (hooks.wb) {
+        const uint32_t asked = (uint32_t)strtoul(hooks.wb, nullptr, 10);
         if (asked >= 11u && asked <= 13u) wb = asked;
     }
     const uint32_t n_win = (uint32_t)(((uint64_t)n_range + (1u << wb) - 1) >> wb);
@@ -513,7 +701,7 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
     // Pass 1's persistent workgroups: one per CU -- or fewer for a plan that is one lane of a pipeline (calls in flight:
     // flatgfa_dev_pipeline_create), where the CUs it leaves are another call's.  FLATGFA_SCAN_WGS=n: tests, measurements.
     if (t_scan_workgroups) fp->n_slots = std::max(8u, std::min<uint32_t>(fp->n_cus, t_scan_workgroups));
-    if (const char *f = test_hook("FLATGFA_SCAN_WGS")) fp->n_slots = std::max(8u, std::min<uint32_t>(fp->n_cus, (uint32_t)strtoul(f, nullptr, 10)));
+    if (hooks.scan_wgs) fp->n_slots = std::max(8u, std::min<uint32_t>(fp->n_cus, (uint32_t)strtoul(hooks.scan_wgs, nullptr, 10)));
     if (fp->n_slots > kMaxSlots) return true;
     fp->n_win = n_win;
     fp->wb = wb;
@@ -528,250 +716,40 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
     // last block would reach beyond the step array.  Those kernels address at most 256 windows
     // of 4096 segments.
     uint64_t short_max = (fp->dbg || ranged || wb != kShortWinBits || n_win > kShortMaxWin || g.n_segs > kShortMaxSegs) ? 0 : kShortMax;  // (the wave-per-path kernels know nothing of ranges)
-    if (const char *forced = test_hook("FLATGFA_SHORT_MAX")) short_max = std::min<uint64_t>(short_max, strtoull(forced, nullptr, 10));
-    // Which kernel walks a path depends on how many runs it has: short paths must fit the run queue,
-    // paths with at most kMediumRuns runs are walked wave by wave too, by pairs of waves that share a
-    // bigger hash set (k_scan_short's medium variant).  The counts come from a one-off kernel.
-    Vec<uint32_t> runs, runs_down, mono, ext;  // (ext: six facts per path, see k_count_runs; for up to 2^18 paths)
-    if (short_max) {
-        // (counted over the spans this plan walks -- a plan may be given others than the graph's own)
-        uint32_t *d_runs = nullptr;
-        const size_t np = g.n_paths;
-        const bool want_ext = np <= (1u << 18) && !measure_switch("FLATGFA_NO_ITEM_DIRS");
-        // (device layout: [runs | runs_down | mono | ext x 6 | begin | end], np words each: one copy in, one copy out)
-        const size_t n_out = want_ext ? 9 : 3;
-        FAST_TRY(hipMalloc(&d_runs, np * (n_out + 2) * 4));
-        Vec<uint32_t> spans(2 * np);
-        std::copy(hb, hb + np, spans.begin());
-        std::copy(he, he + np, spans.begin() + (ptrdiff_t)np);
-        hipError_t e = staged_copy(d_runs + n_out * np, spans.data(), np * 8, hipMemcpyHostToDevice, nullptr);
-        if (e != hipSuccess) {
-            (void)hipFree(d_runs);
-            FAST_TRY(e);
-        }
-        // (few long paths: several pieces each, so that the kernel fills the chip -- the pieces add to cleared words)
-        uint32_t pieces = 1;
-        if (want_ext && np < fp->n_cus * 8u && g.n_steps / np >= (1u << 16)) pieces = std::min<uint32_t>((fp->n_cus * 8u + (uint32_t)np - 1u) / (uint32_t)np, 4096u);
-        if (const char *forced = test_hook("FLATGFA_COUNT_PIECES")) pieces = want_ext ? (uint32_t)std::min(std::max(1, atoi(forced)), 4096) : 1u;
-        if (pieces > 1) {
-            e = hipMemsetAsync(d_runs, 0, n_out * np * 4, nullptr);
-            if (e != hipSuccess) {
-                (void)hipFree(d_runs);
-                FAST_TRY(e);
-            }
-        }
-        hipLaunchKernelGGL(k_count_runs, dim3(std::min<uint32_t>(g.n_paths, fp->n_cus * 8u), pieces), dim3(256), 0, nullptr, g.steps,
-                           d_runs + n_out * np, d_runs + (n_out + 1) * np, g.n_paths, g.n_steps, d_runs, d_runs + np, d_runs + 2 * np,
-                           want_ext ? d_runs + 3 * np : nullptr);
-        Vec<uint32_t> out(n_out * np);
-        e = staged_copy(out.data(), d_runs, n_out * np * 4, hipMemcpyDeviceToHost, nullptr);
-        (void)hipFree(d_runs);
-        FAST_TRY(e);
-        runs.assign(out.begin(), out.begin() + (ptrdiff_t)np);
-        runs_down.assign(out.begin() + (ptrdiff_t)np, out.begin() + (ptrdiff_t)(2 * np));
-        mono.assign(out.begin() + (ptrdiff_t)(2 * np), out.begin() + (ptrdiff_t)(3 * np));
-        if (want_ext) ext.assign(out.begin() + (ptrdiff_t)(3 * np), out.end());
-        if (pieces > 1) {  // (no one piece knows: a path is monotone when all of its pairs ascend or all of them descend)
-            for (size_t p = 0; p < np; ++p) {
-                const uint32_t pairs = he[p] > hb[p] ? he[p] - hb[p] - 1u : 0u;
-                mono[p] = (he[p] > hb[p] && (ext[6 * p] == pairs || ext[6 * p + 1] == pairs)) ? 1u : 0u;
-            }
-        }
-        // (FLATGFA_NO_CLAIM=0: every path claims, monotone or not -- tests and measurements)
-        if (const char *nc = test_hook("FLATGFA_NO_CLAIM"); nc && nc[0] == '0') std::fill(mono.begin(), mono.end(), 0u);
-    }
+    if (hooks.short_max) short_max = std::min<uint64_t>(short_max, strtoull(hooks.short_max, nullptr, 10));
+    RunFacts facts;
+    if (short_max && !count_runs(g, hb, he, fp->n_cus, hooks, &facts)) return false;
     plan_tick("range: k_count_runs + its copies");
-    const bool short_any = test_hook("FLATGFA_SHORT_ANY") != nullptr;  // tests: let k_scan_short find out and hand back
-    const bool no_rev = measure_switch("FLATGFA_NO_REVERSED_COPIES");
-    // A wave-per-path kernel only knows runs that go up.  A path that walks the ids downwards (a
-    // contig on the reverse strand) has far fewer runs when it is read backwards, and the order of a
-    // path's steps does not matter to the counts: such a path is walked from a reversed copy of its
-    // steps, made here once (rev_steps; every copy starts at a multiple of 16).
-    // (the *_mono lists: paths that walk the ids strictly one way -- the wave-per-path kernels skip their claims)
-    Vec<uint4> items, short_items, medium_items, short_rev, medium_rev, whole, rev_list, tiny_items;
-    Vec<uint4> short_mono, medium_mono, short_rev_mono, medium_rev_mono, tiny_mono;
-    const bool no_tiny = test_hook("FLATGFA_NO_TINY") != nullptr;  // (measurements, tests: tiny paths go to k_scan_short as before)
-    uint64_t rev_len = 0;
-    for (uint32_t p = 0; p < g.n_paths; ++p) {
-        const uint64_t b = hb[p], e = he[p], n = e - b;
-        if (n == 0) continue;
-        const bool in_reach = ((e + 15) & ~15ull) <= g.n_steps;  // the last block must not read past the step array
-        const bool down = short_max && !no_rev && runs_down[p] < runs[p] && rev_len + n + 2048 < 0xFFFFFFFFull;
-        const uint32_t rn = short_max ? (down ? runs_down[p] : runs[p]) : 0u;
-        const bool is_tiny = n <= std::min<uint64_t>(short_max, kTinyMax) && !no_tiny;  // (k_scan_tiny: a wave holds the whole path)
-        const bool is_short = !is_tiny && n <= short_max && (down || in_reach) && (rn + 16 <= kQCap || short_any);
-        const bool is_medium = !is_tiny && !is_short && short_max && (down || in_reach) && rn <= kMediumRuns;
-        const bool mn = short_max && mono[p] != 0u;
-        if (is_tiny) {
-            (mn ? tiny_mono : tiny_items).push_back(make_uint4((uint32_t)b, (uint32_t)e, kNoSlot, p));
-        } else if ((is_short || is_medium) && down) {
-            const uint32_t at = (uint32_t)rev_len;
-            rev_list.push_back(make_uint4((uint32_t)b, (uint32_t)e, at, p));
-            (is_short ? (mn ? short_rev_mono : short_rev) : (mn ? medium_rev_mono : medium_rev)).push_back(make_uint4(at, at + (uint32_t)n, kNoSlot, p));
-            rev_len += (n + 15) & ~15ull;
-        } else if (is_short) {
-            (mn ? short_mono : short_items).push_back(make_uint4((uint32_t)b, (uint32_t)e, kNoSlot, p));
-        } else if (is_medium) {
-            (mn ? medium_mono : medium_items).push_back(make_uint4((uint32_t)b, (uint32_t)e, kNoSlot, p));
-        } else {
-            whole.push_back(make_uint4((uint32_t)b, (uint32_t)e, kNoSlot, p));
-        }
-    }
-    // Paths of equal length -- the ties of the sort below -- are walked in the order of where they
-    // start: k_scan's workgroups take the items one after the other, so neighbours in the list go to
-    // different workgroups, and it is the paths that start near each other that meet in a window.  A
-    // sub-bucket then holds one path's records of its window, not those of the five or six that
-    // chance gave one workgroup (the capacity every sub-bucket gets is the fullest one's, §2).
-    if (whole.size() > 1 && !measure_switch("FLATGFA_KEEP_PATH_ORDER")) {
-        Vec<uint32_t> at(whole.size()), first(whole.size(), 0u);
-        if (!ext.empty()) {  // (the counting kernel looked already)
-            for (size_t i = 0; i < whole.size(); ++i) first[i] = ext[6 * (size_t)whole[i].w + 4];
-        } else {
-        for (size_t i = 0; i < whole.size(); ++i) at[i] = whole[i].x;
-        uint32_t *d_at = nullptr;
-        FAST_TRY(hipMalloc(&d_at, whole.size() * 8));
-        hipError_t e = staged_copy(d_at, at.data(), whole.size() * 4, hipMemcpyHostToDevice, nullptr);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_first_ids, dim3((uint32_t)((whole.size() + 255) / 256)), dim3(256), 0, nullptr, g.steps, d_at, (uint32_t)whole.size(),
-                               d_at + whole.size());
-            e = staged_copy(first.data(), d_at + whole.size(), whole.size() * 4, hipMemcpyDeviceToHost, nullptr);
-        }
-        (void)hipFree(d_at);
-        FAST_TRY(e);
-        }
-        Vec<uint32_t> order(whole.size());
-        std::iota(order.begin(), order.end(), 0u);
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return first[a] < first[b]; });
-        Vec<uint4> sorted(whole.size());
-        for (size_t i = 0; i < whole.size(); ++i) sorted[i] = whole[order[i]];
-        whole.swap(sorted);
+    PathClasses classes = classify_paths({hb, he, g.n_paths, g.n_steps, short_max, facts.runs.data(), facts.runs_down.data(), facts.mono.data(),
+                                          hooks.short_any, measure_switch("FLATGFA_NO_REVERSED_COPIES"), hooks.no_tiny});
+    if (classes.whole.size() > 1 && !measure_switch("FLATGFA_KEEP_PATH_ORDER")) {
+        Vec<uint32_t> first;
+        if (!first_ids(g, classes.whole, facts.ext, &first)) return false;
+        order_whole_paths(&classes.whole, first);
     }
     plan_tick("range: paths classified, k_first_ids, sorted");
-    if (!rev_list.empty()) {
-        fp->n_rev_steps = (uint32_t)(rev_len + 1024);  // (a block is read whole)
-        FAST_TRY(hipMalloc(&fp->rev_steps, (size_t)fp->n_rev_steps * 4));
-        FAST_TRY(hipMemset(fp->rev_steps, 0, (size_t)fp->n_rev_steps * 4));
-        uint4 *d_list = nullptr;
-        FAST_TRY(hipMalloc(&d_list, rev_list.size() * sizeof(uint4)));
-        hipError_t e = staged_copy(d_list, rev_list.data(), rev_list.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_reverse_copy, dim3(std::min<uint32_t>((uint32_t)rev_list.size(), fp->n_cus * 8u)), dim3(256), 0, nullptr,
-                               g.steps, d_list, (uint32_t)rev_list.size(), fp->rev_steps);
-            e = hipDeviceSynchronize();
-        }
-        (void)hipFree(d_list);
-        FAST_TRY(e);
-    }
-    // k_scan's work items: whole paths, except that a path longer than `piece` steps is cut into
-    // equal pieces, so that graphs with few long paths still fill the chip.  The workgroups take the
-    // items, longest first, in a fixed snake order (item_of): with a hundred paths of a million steps
-    // and pieces of N / (2 CUs), three pieces fall to some workgroups and two to most (+28 % on the
-    // longest).  So the deal is played through on the host for a few piece sizes, every item charged
-    // a few blocks' worth for its turnaround, and the size with the shortest longest hand is taken
-    // (the largest such size: for 1000 paths of 100 k steps, no cutting at all).
-    // (z: bit 0 = the item walks the ids downwards, set by k_item_dirs; from bit 1 up, 1 + the
-    // ordinal of the split path the item is a piece of, or 0 for a whole path)
-    const auto cut = [&](uint64_t piece, Vec<uint4> *out) -> uint32_t {
-        uint32_t n_split = 0;
-        for (const uint4 &w : whole) {
-            const uint64_t b = w.x, n = (uint64_t)w.y - w.x;
-            const uint32_t k = (uint32_t)((n + piece - 1) / piece);
-            const uint32_t z = k > 1 ? (++n_split) << 1 : 0u;
-            for (uint32_t j = 0; j < k; ++j)
-                out->push_back(make_uint4((uint32_t)(b + n * j / k), (uint32_t)(b + n * (j + 1) / k), z, w.w));
-        }
-        return n_split;
-    };
-    const auto longer = [](const uint4 &a, const uint4 &b) { return a.y - a.x > b.y - b.x; };
-    uint64_t piece = 0;
-    if (const char *forced = test_hook("FLATGFA_PIECE_STEPS")) {
-        piece = (std::max<uint64_t>(256, strtoull(forced, nullptr, 10)) + 255) & ~255ull;
-    } else {
-        constexpr uint64_t kTurnaround = 8192;  // steps a workgroup could have walked while it changes items
-        uint64_t long_steps = 0;
-        for (const uint4 &w : whole) long_steps += w.y - w.x;
-        uint64_t best = ~0ull;
-        for (const uint32_t twice_m : {4u, 5u, 6u, 8u, 10u, 12u, 16u, 20u, 24u}) {  // pieces of N / (m CUs), m = 2 .. 12
-            uint64_t cand = std::max<uint64_t>(32768, (2 * long_steps + (uint64_t)twice_m * fp->n_slots - 1) / ((uint64_t)twice_m * fp->n_slots));
-            cand = (cand + 255) & ~255ull;
-            Vec<uint4> trial;
-            cut(cand, &trial);
-            std::stable_sort(trial.begin(), trial.end(), longer);
-            Vec<uint64_t> hand(fp->n_slots, 0);
-            for (size_t i = 0; i < trial.size(); ++i) {
-                const size_t round = i / fp->n_slots, pos = i % fp->n_slots;
-                hand[(round & 1) ? fp->n_slots - 1 - pos : pos] += (uint64_t)(trial[i].y - trial[i].x) + kTurnaround;
-            }
-            const uint64_t longest = *std::max_element(hand.begin(), hand.end());
-            if (longest + longest / 64 < best) {  // smaller pieces have to win by more than 1.5 %
-                best = longest;
-                piece = cand;
-            }
-            if (cand == 32768) break;
-        }
-        // Cutting has a price beyond the turnaround where pass 2 cannot give all split paths a bitset
-        // of their own kind -- none at all with 8192-segment windows, 128 with smaller ones: the plan
-        // then takes smaller windows, more ranges, or walks the paths in groups (fast_plan_create).  A
-        // graph of thousands of paths rarely needs its long ones cut: k_scan's workgroups take the
-        // items longest first as they get to them, and if whole paths dealt that way (to the least
-        // loaded workgroup each) leave the longest hand within a tenth of the best cut's, they stay whole.
-        if (piece && !measure_switch("FLATGFA_KEEP_CUTS")) {
-            Vec<uint4> trial;
-            const uint32_t n_split = cut(piece, &trial);
-            if (n_split > (wb <= 12 ? kMaxShared : 0u)) {
-                Vec<uint64_t> lens;
-                for (const uint4 &w : whole) lens.push_back((uint64_t)w.y - w.x);
-                std::sort(lens.begin(), lens.end(), std::greater<uint64_t>());
-                std::priority_queue<uint64_t, Vec<uint64_t>, std::greater<uint64_t>> hands;
-                for (uint32_t i = 0; i < fp->n_slots; ++i) hands.push(0);
-                uint64_t longest = 0;
-                for (const uint64_t n : lens) {
-                    const uint64_t h = hands.top() + n + kTurnaround;
-                    hands.pop();
-                    hands.push(h);
-                    longest = std::max(longest, h);
-                }
-                if (longest <= best + best / 10) piece = ~0ull >> 1;  // (longer than any path)
-            }
-        }
-    }
-    fp->n_shared = cut(piece ? piece : 32768, &items);
-    std::stable_sort(items.begin(), items.end(), longer);
+    if (!classes.rev_list.empty() && !reverse_copies(g, classes.rev_list, classes.rev_len, fp)) return false;
+    // Long paths are cut into equal pieces, so that graphs with few long paths still fill the chip.
+    Vec<uint4> items;
+    const uint64_t piece = hooks.piece_steps ? (std::max<uint64_t>(256, strtoull(hooks.piece_steps, nullptr, 10)) + 255) & ~255ull
+                                             : choose_piece(classes.whole, fp->n_slots, wb, measure_switch("FLATGFA_KEEP_CUTS"));
+    fp->n_shared = make_items(classes.whole, piece, &items);
     plan_tick("range: the deal played through, items cut");
-    // A wave-per-path list: the paths read from the graph's steps, then those read from their reversed copies; of
-    // either kind the ones that need no claim lie next to the boundary, so that one stretch of the list names them
-    // all: [claim][no claim | no claim, reversed][claim, reversed], each part longest first.
-    const auto lay_out = [&](Vec<uint4> *fwd, Vec<uint4> *fwd_mono, Vec<uint4> *rev_mono, Vec<uint4> *rev,
-                             uint32_t *n_rev, uint32_t *mono_lo, uint32_t *mono_n) {
-        for (Vec<uint4> *v : {fwd, fwd_mono, rev_mono, rev}) std::stable_sort(v->begin(), v->end(), longer);
-        *mono_lo = (uint32_t)fwd->size();
-        *mono_n = (uint32_t)(fwd_mono->size() + rev_mono->size());
-        *n_rev = (uint32_t)(rev_mono->size() + rev->size());
-        for (Vec<uint4> *v : {fwd_mono, rev_mono, rev}) fwd->insert(fwd->end(), v->begin(), v->end());
-    };
-    lay_out(&short_items, &short_mono, &short_rev_mono, &short_rev, &fp->n_short_rev, &fp->short_mono_lo, &fp->short_mono_n);
-    lay_out(&medium_items, &medium_mono, &medium_rev_mono, &medium_rev, &fp->n_medium_rev, &fp->medium_mono_lo, &fp->medium_mono_n);
-    fp->tiny_mono_lo = (uint32_t)tiny_items.size();
-    fp->tiny_mono_n = (uint32_t)tiny_mono.size();
-    tiny_items.insert(tiny_items.end(), tiny_mono.begin(), tiny_mono.end());
+    const Vec<uint4> &short_items = classes.shorts.items, &medium_items = classes.mediums.items, &tiny_items = classes.tiny.items;
+    fp->n_short_rev = classes.shorts.n_rev, fp->short_mono_lo = classes.shorts.mono_lo, fp->short_mono_n = classes.shorts.mono_n;
+    fp->n_medium_rev = classes.mediums.n_rev, fp->medium_mono_lo = classes.mediums.mono_lo, fp->medium_mono_n = classes.mediums.mono_n;
+    fp->tiny_mono_lo = classes.tiny.mono_lo, fp->tiny_mono_n = classes.tiny.mono_n;
     fp->n_items = (uint32_t)items.size();
     fp->n_short = (uint32_t)short_items.size();
     fp->n_medium = (uint32_t)medium_items.size();
     fp->n_tiny = (uint32_t)tiny_items.size();
-    {
-        const auto steps_of = [](const Vec<uint4> &v) {
-            uint64_t n = 0;
-            for (const uint4 &d : v) n += d.y - d.x;
-            return n;
-        };
-        fp->class_steps[0] = steps_of(items);
-        fp->class_steps[1] = steps_of(short_items);
-        fp->class_steps[2] = steps_of(medium_items);
-        fp->class_steps[3] = steps_of(tiny_items);
-    }
+    fp->class_steps[0] = steps_of(items);
+    fp->class_steps[1] = steps_of(short_items);
+    fp->class_steps[2] = steps_of(medium_items);
+    fp->class_steps[3] = steps_of(tiny_items);
     if (items.empty() && short_items.empty() && medium_items.empty() && tiny_items.empty()) return true;
     fp->max_back = std::min<uint32_t>(fp->n_short, kMaxHandBack);
-    fp->exact_short = !short_any;  // the run counts the lists were made from are exact: nothing is handed back
+    fp->exact_short = !hooks.short_any;  // the run counts the lists were made from are exact: nothing is handed back
     fp->dstride = fp->n_items + fp->max_back + 1;
     // The directory (one cursor pair per item and window) must stay small next to the steps.
     if ((uint64_t)fp->dstride * n_win * 8 > std::max<uint64_t>(64ull << 20, g.n_steps * 2)) {
@@ -782,156 +760,30 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
     // CUs, several that share the window's paths and sub-buckets and add their counts up (1000
     // paths over 100 k segments: 25 workgroups took 0.48 ms where 250 take 0.06).
     fp->acc_parts = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({16, fp->n_cus / n_win, (g.n_steps / n_win + (32u << 10) - 1) >> 15}));  // a workgroup per 32 k steps: a wave's walk is a chain of dependent round trips, a microsecond per 64 records
-    if (const char *f = test_hook("FLATGFA_ACC_PARTS")) fp->acc_parts = std::max(1u, std::min(64u, (uint32_t)strtoul(f, nullptr, 10)));
-    const uint32_t acc_waves = fp->acc_parts * kAccWaves;
-    // Tagged calls (records say whose they are; see kTagShift): every workgroup's items -- the handed-back
-    // ones included -- must have tags of their own next to the split paths', and pass 2 needs LDS for a
-    // bitset per split path (none to spare with 8192-segment windows; a window shared by several
-    // workgroups cannot share bitsets).  FLATGFA_TAGGED=0 keeps the directory (tests, measurements).
+    if (hooks.acc_parts) fp->acc_parts = std::max(1u, std::min(64u, (uint32_t)strtoul(hooks.acc_parts, nullptr, 10)));
     {
-        const uint32_t grid = (fp->n_short || fp->n_medium || fp->n_tiny) ? fp->n_slots : std::min<uint32_t>(fp->n_items, fp->n_slots);
-        const uint64_t per_wg = grid ? ((uint64_t)fp->n_items + fp->max_back + grid - 1) / grid : 0;
-        const char *t = test_hook("FLATGFA_TAGGED");
-        const uint32_t shared_cap = wb <= 12 ? kMaxShared : 0u;
-        const bool base_ok = !fp->dbg && !(t && t[0] == '0') && (fp->n_shared == 0 || fp->acc_parts == 1);
-        const bool taggable = base_ok && fp->n_shared <= shared_cap;
-        // A workgroup's private tags: what the split paths leave of the 512 (FLATGFA_TAG_LIMIT: fewer, tests).
-        // k_scan deals the items out as its workgroups get to them, so it is not the mean that has to
-        // fit but the most any workgroup takes: the deal is played through here (its first two items
-        // are fixed, every further one goes to whoever is done first), with some room to spare --
-        // a workgroup that does run out of tags stops taking items (k_scan) and the others go on.
-        uint32_t limit = fp->n_shared + 1u < kTagCount ? kTagCount - 1u - fp->n_shared : 0u;  // (the highest tag says "no claim")
-        if (const char *f = test_hook("FLATGFA_TAG_LIMIT")) limit = std::min<uint32_t>(limit, std::max(2u, (uint32_t)strtoul(f, nullptr, 10)));
-        fp->tag_limit = limit;
-        uint64_t most = per_wg;
-        if (taggable && grid && per_wg <= limit && fp->n_items + fp->max_back > 2ull * grid && !test_hook("FLATGFA_TAG_MEAN_ONLY")) {
-            constexpr uint64_t kTurn = 2048;  // steps' worth an item costs beyond its steps
-            std::priority_queue<std::pair<uint64_t, uint32_t>, Vec<std::pair<uint64_t, uint32_t>>, std::greater<std::pair<uint64_t, uint32_t>>> hands;
-            Vec<uint32_t> taken(grid, 0u);
-            for (uint32_t i = 0; i < grid; ++i) {
-                uint64_t h = 0;
-                for (uint32_t k = 0; k < 2; ++k)
-                    if (i + k * grid < fp->n_items) h += (uint64_t)(items[i + k * grid].y - items[i + k * grid].x) + kTurn, taken[i] += 1;
-                hands.push({h, i});
-            }
-            for (uint64_t j = 2ull * grid; j < (uint64_t)fp->n_items + fp->max_back; ++j) {
-                const uint64_t n = j < fp->n_items ? (uint64_t)(items[j].y - items[j].x) : kShortMax;
-                auto [h, i] = hands.top();
-                hands.pop();
-                taken[i] += 1;
-                hands.push({h + n + kTurn, i});
-            }
-            most = *std::max_element(taken.begin(), taken.end());
-            most += most / 4;  // (the workgroups do not run at one speed)
-        }
-        fp->tagged = taggable && per_wg <= limit && most <= limit;
-        // what fast_plan_create may do about a plan that is not: walk the paths in groups (fewer items, fewer
-        // split paths per group), or take 4096-segment windows (pass 2 then has LDS for split paths' bitsets)
-        fp->too_many_items = base_ok && !fp->tagged && fp->acc_parts == 1 && !fp->n_short && !fp->n_medium && !fp->n_tiny && (taggable || (wb <= 12 && fp->n_shared > shared_cap));
-        fp->want_wb12 = base_ok && !fp->tagged && wb == 13 && fp->n_shared > 0 && fp->acc_parts == 1;
+        const TagVerdict v = tag_verdict(items, {fp->n_slots, wb, fp->acc_parts, fp->max_back, fp->n_shared, fp->n_short || fp->n_medium || fp->n_tiny, fp->dbg != 0,
+                                                 hooks.tagged_off, hooks.tag_limit ? std::max(1u, (uint32_t)strtoul(hooks.tag_limit, nullptr, 10)) : 0u, hooks.tag_mean_only});
+        fp->tagged = v.tagged;
+        fp->tag_limit = v.tag_limit;
+        fp->too_many_items = v.too_many_items;
+        fp->want_wb12 = v.want_wb12;
         if (!fp->tagged && n_win > kMaxWin) {  // so many windows only without cursor snapshots: the caller cuts smaller ranges
-            const bool many = fp->too_many_items, w12 = fp->want_wb12;
             fast_plan_destroy(fp);
-            fp->too_many_items = many;
-            fp->want_wb12 = w12;
+            fp->too_many_items = v.too_many_items;
+            fp->want_wb12 = v.want_wb12;
             return true;
         }
     }
-    // Pass 2 walks k_scan's items grouped by path (the pieces of a split path share a bitset),
-    // each of its waves a contiguous stretch of the list: paths are dealt to the waves longest
-    // first, each to the wave with the least steps so far.
     {
-        Vec<Vec<uint32_t>> by_path;  // item indices per path that has items
-        Vec<uint64_t> path_steps;
-        Vec<int64_t> slot_of(g.n_paths, -1);
-        for (uint32_t j = 0; j < fp->n_items; ++j) {
-            const uint32_t p = items[j].w;
-            if (slot_of[p] < 0) {
-                slot_of[p] = (int64_t)by_path.size();
-                by_path.emplace_back();
-                path_steps.push_back(0);
-            }
-            by_path[(size_t)slot_of[p]].push_back(j);
-            path_steps[(size_t)slot_of[p]] += items[j].y - items[j].x;
-        }
-        Vec<uint32_t> order(by_path.size());
-        std::iota(order.begin(), order.end(), 0u);
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return path_steps[a] > path_steps[b]; });
-        // A path with more than half a wave's even share of the steps would hold its wave up (four
-        // paths of 25 M steps: four waves busy out of sixteen, pass 2 2.6 times slower).  Such
-        // paths go to the window's workgroups whole -- to the one with the least so far -- and
-        // their pieces to its sixteen waves in turn; the others are dealt to single waves as before.
-        uint64_t total_steps = 0;
-        for (uint64_t v : path_steps) total_steps += v;
-        const uint64_t fat_min = total_steps / (2ull * acc_waves) + 1;
-        Vec<Vec<uint32_t>> per_wave(acc_waves), fat_of_part(fp->acc_parts);
-        Vec<uint64_t> load(acc_waves, 0), part_load(fp->acc_parts, 0);
-        for (uint32_t gi : order) {
-            if (path_steps[gi] < fat_min || by_path[gi].size() < kAccWaves / 2 || measure_switch("FLATGFA_NO_FAT_PATHS")) continue;  // (fewer pieces than half the waves: better one wave busy all the time than three)
-            const uint32_t q = (uint32_t)(std::min_element(part_load.begin(), part_load.end()) - part_load.begin());
-            part_load[q] += path_steps[gi];
-            fat_of_part[q].push_back(gi);
-        }
-        for (uint32_t q = 0; q < fp->acc_parts; ++q)
-            for (uint32_t wv = 0; wv < kAccWaves; ++wv) load[q * kAccWaves + wv] = part_load[q] / kAccWaves;
-        std::vector<bool> is_fat(by_path.size(), false);
-        for (const auto &v : fat_of_part)
-            for (uint32_t gi : v) is_fat[gi] = true;
-        for (uint32_t gi : order) {
-            if (is_fat[gi]) continue;
-            const uint32_t wv = (uint32_t)(std::min_element(load.begin(), load.end()) - load.begin());
-            load[wv] += path_steps[gi] + 64;
-            bool first = true;
-            for (uint32_t j : by_path[gi]) {
-                per_wave[wv].push_back(j | (first ? 0x80000000u : 0u));
-                first = false;
-            }
-        }
-        Vec<uint32_t> elist, wave_off(acc_waves + 1, 0);
-        for (uint32_t wv = 0; wv < acc_waves; ++wv) {
-            wave_off[wv] = (uint32_t)elist.size();
-            elist.insert(elist.end(), per_wave[wv].begin(), per_wave[wv].end());
-        }
-        wave_off[acc_waves] = (uint32_t)elist.size();
-        Vec<uint32_t> fat_off(fp->acc_parts + 1, 0), fat_woff;
-        for (uint32_t q = 0; q < fp->acc_parts; ++q) {
-            fat_off[q] = fp->n_fat;
-            for (uint32_t gi : fat_of_part[q]) {
-                const Vec<uint32_t> &its = by_path[gi];
-                for (uint32_t wv = 0; wv < kAccWaves; ++wv) {
-                    fat_woff.push_back((uint32_t)elist.size());
-                    bool first = true;
-                    for (size_t k = wv; k < its.size(); k += kAccWaves) {
-                        elist.push_back(its[k] | (first ? 0x80000000u : 0u));
-                        first = false;
-                    }
-                }
-                fat_woff.push_back((uint32_t)elist.size());
-                fp->n_fat += 1;
-            }
-        }
-        fat_off[fp->acc_parts] = fp->n_fat;
-        // k_scan leaves an item's cursors and sub-bucket at the item's place in this order
-        Vec<uint32_t> perm(fp->n_items + 1, 0);
-        for (size_t at = 0; at < elist.size(); ++at) perm[elist[at] & 0x7FFFFFFFu] = (uint32_t)at | (elist[at] & 0x80000000u);
-        // (the five lists in one allocation and one copy, every one on a 256-byte boundary: an allocation and a copy each cost a
-        // tenth of what the first answer costs)
-        const auto padded = [](size_t words) { return (words + 63) & ~(size_t)63; };
-        const size_t o_fat_off = 0, o_fat_woff = o_fat_off + padded(fat_off.size()), o_perm = o_fat_woff + padded(fat_woff.size() + 1),
-                     o_elist = o_perm + padded(perm.size()), o_wave_off = o_elist + padded(elist.size() + 1), total_words = o_wave_off + padded(wave_off.size());
-        Vec<uint32_t> slab(total_words, 0u);
-        std::copy(fat_off.begin(), fat_off.end(), slab.begin() + (ptrdiff_t)o_fat_off);
-        std::copy(fat_woff.begin(), fat_woff.end(), slab.begin() + (ptrdiff_t)o_fat_woff);
-        std::copy(perm.begin(), perm.end(), slab.begin() + (ptrdiff_t)o_perm);
-        std::copy(elist.begin(), elist.end(), slab.begin() + (ptrdiff_t)o_elist);
-        std::copy(wave_off.begin(), wave_off.end(), slab.begin() + (ptrdiff_t)o_wave_off);
-        FAST_TRY(hipMalloc(&fp->lists_slab, total_words * 4));
-        FAST_TRY(staged_copy(fp->lists_slab, slab.data(), total_words * 4, hipMemcpyHostToDevice, nullptr));
-        fp->fat_off = fp->lists_slab + o_fat_off;
-        fp->fat_woff = fp->lists_slab + o_fat_woff;
-        fp->perm = fp->lists_slab + o_perm;
-        fp->elist = fp->lists_slab + o_elist;
-        fp->wave_off = fp->lists_slab + o_wave_off;
+        const Pass2Lists lists = pass2_lists(items, g.n_paths, fp->acc_parts, measure_switch("FLATGFA_NO_FAT_PATHS"));
+        fp->n_fat = lists.n_fat;
+        if (!upload(&fp->lists_slab, lists.slab)) return false;
+        fp->fat_off = fp->lists_slab + lists.o_fat_off;
+        fp->fat_woff = fp->lists_slab + lists.o_fat_woff;
+        fp->perm = fp->lists_slab + lists.o_perm;
+        fp->elist = fp->lists_slab + lists.o_elist;
+        fp->wave_off = fp->lists_slab + lists.o_wave_off;
     }
     plan_tick("range: pass 2 lists made and uploaded");
     // Worst case is one record per step (plus one per block and window crossing) for k_scan and
@@ -944,8 +796,8 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
     uint64_t cap = (std::min<uint64_t>(g.n_steps, walked) + slots - 1) / slots;
     if (ranged) cap = (uint64_t)((double)cap * n_range / g.n_segs) + 1;  // a range sees its share of the runs
     cap = cap + cap / 4 + 256;
-    if (const char *forced = test_hook("FLATGFA_BUCKET_CAP")) {  // tests: force the overflow route
-        cap = strtoull(forced, nullptr, 10);
+    if (hooks.bucket_cap) {
+        cap = strtoull(hooks.bucket_cap, nullptr, 10);
         fp->cap_forced = true;
     }
     // Packed buckets (below, once the items are on the device): where an even share for every sub-bucket would take
@@ -969,14 +821,10 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
         want_packed = can_pack && strtol(f, nullptr, 10) != 0;
         ask_first = false;
     }
-    if (const char *f = test_hook("FLATGFA_PACKED_ASK")) ask_first = can_pack && !want_packed && strtol(f, nullptr, 10) != 0;  // (tests: small graphs ask too)
+    if (hooks.packed_ask) ask_first = can_pack && !want_packed && strtol(hooks.packed_ask, nullptr, 10) != 0;
     want_packed = want_packed || ask_first;
-    if (!want_packed) {
-        const int rc = alloc_buckets(fp, std::max<uint64_t>(cap, 4));
-        if (rc < 0) return false;
-        if (rc == 0) return true;  // not eligible; the caller's destroy releases what was allocated
-        fp->bucket_records = (slots + fp->n_slots) * (uint64_t)fp->cap;
-    }
+    if (!want_packed)
+        if (const int rc = even_buckets(fp, cap); rc <= 0) return rc == 0;
     FAST_TRY(hipMalloc(&fp->counts, slots * 4));
     FAST_TRY(hipMemset(fp->counts, 0, slots * 4));
     FAST_TRY(hipMalloc(&fp->taken, ((size_t)fp->n_slots + 1) * 4));
@@ -990,99 +838,19 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
     FAST_TRY(hipMemset(fp->islot, 0, (size_t)fp->dstride * 4));
     plan_tick("range: buckets, cursors, directory allocated and cleared");
     FAST_TRY(hipMalloc(&fp->items, (items.size() + fp->max_back + 1) * sizeof(uint4)));
-    // No path cut into pieces, and the counting kernel's facts at hand: an item is a whole path, and what k_item_dirs would find
-    // out about it -- which way it mostly runs, whether it runs strictly one way, how many records it makes, how many of its
-    // steps go against its grain -- is known (that kernel's read of the steps is then left out).
-    const bool derived = !ext.empty() && fp->n_shared == 0 && !items.empty() && !measure_switch("FLATGFA_NO_ITEM_DIRS");
-    unsigned long long derived_counts[2] = {0, 0};
-    uint32_t derived_noclaim = 0;
-    if (derived) {
-        const char *nc0 = test_hook("FLATGFA_NO_CLAIM");
-        const bool no_claim0 = !(nc0 && nc0[0] == '0');
-        for (uint4 &it : items) {
-            const uint32_t *x = &ext[6 * (size_t)it.w];
-            const uint32_t n = it.y - it.x, pairs = n - 1u;  // (an item has at least one step)
-            const uint32_t state = (x[0] == pairs ? 1u : 0u) | (x[1] == pairs ? 2u : 0u);
-            it.z = (it.z & ~1u) | (x[3] > x[2] ? 1u : 0u);
-            if (state && no_claim0) {
-                it.z |= kItemNoClaim;
-                derived_noclaim += 1;
-            }
-            derived_counts[0] += (unsigned long long)n - std::max(x[2], x[3]);
-            derived_counts[1] += std::min(x[0], x[1]);
-        }
-    }
     if (!items.empty()) {
+        // What is to be known of the items -- which way each mostly runs, whether it runs strictly one way, how many records they
+        // make, how many of their steps go against the grain: from the counting kernel's facts where no path is cut (k_item_dirs'
+        // read of the steps is then left out), else from k_item_dirs.
+        const bool look = !measure_switch("FLATGFA_NO_ITEM_DIRS");  // (measurement builds: every item taken as running upwards)
+        const bool derived = look && !facts.ext.empty() && fp->n_shared == 0;
+        ItemFacts known;
+        if (derived) known = item_facts_from_ext(&items, facts.ext, hooks.claim_all);
         FAST_TRY(staged_copy(fp->items, items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr));
-        if (!measure_switch("FLATGFA_NO_ITEM_DIRS")) {  // (measurement builds: every item taken as running upwards)
-            unsigned long long *d_runs64 = nullptr, runs64 = 0, item_steps = 0, counted[2] = {0, 0};
-            // (FLATGFA_NO_CLAIM=0: every item claims, monotone or not -- tests and measurements)
-            const char *nc_env = test_hook("FLATGFA_NO_CLAIM");
-            const bool no_claim = !(nc_env && nc_env[0] == '0');
-            if (derived) {
-                counted[0] = derived_counts[0];
-                counted[1] = derived_counts[1];
-                runs64 = counted[0];
-                fp->n_noclaim = derived_noclaim;
-            } else {
-            FAST_TRY(hipMalloc(&d_runs64, 16));
-            FAST_TRY(hipMemset(d_runs64, 0, 16));
-            uint4 *d_mono = nullptr;
-            if (fp->n_shared && no_claim) FAST_TRY(hipMalloc(&d_mono, (size_t)fp->n_items * sizeof(uint4)));
-            hipLaunchKernelGGL(k_item_dirs, dim3(std::min<uint32_t>(fp->n_items, fp->n_cus * 8u)), dim3(256), 0, nullptr, g.steps,
-                               reinterpret_cast<uint4 *>(fp->items), fp->n_items, d_runs64, d_mono);
-            hipError_t e = staged_copy(counted, d_runs64, 16, hipMemcpyDeviceToHost, nullptr);
-            runs64 = counted[0];
-            (void)hipFree(d_runs64);
-            // The pieces of a split path: the path never meets a segment twice when every piece runs strictly one way,
-            // all of them the same way, and each piece starts beyond (below) where the piece before it ended.
-            Vec<uint4> dev_items;
-            if (e == hipSuccess && (d_mono || !no_claim)) {
-                dev_items.resize(items.size());
-                e = staged_copy(dev_items.data(), fp->items, items.size() * sizeof(uint4), hipMemcpyDeviceToHost, nullptr);
-            }
-            if (e == hipSuccess && !no_claim) {
-                for (uint4 &it : dev_items) it.z &= ~kItemNoClaim;
-                e = staged_copy(fp->items, dev_items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr);
-            } else if (e == hipSuccess && d_mono) {
-                Vec<uint4> mono(items.size());
-                e = staged_copy(mono.data(), d_mono, items.size() * sizeof(uint4), hipMemcpyDeviceToHost, nullptr);
-                if (e == hipSuccess) {
-                    Vec<Vec<uint32_t>> pieces(fp->n_shared);
-                    for (uint32_t j = 0; j < fp->n_items; ++j) {
-                        const uint32_t sh = (dev_items[j].z & ~kItemNoClaim) >> 1;
-                        if (sh) pieces[sh - 1].push_back(j);
-                    }
-                    bool any = false;
-                    for (Vec<uint32_t> &pc : pieces) {
-                        std::sort(pc.begin(), pc.end(), [&](uint32_t a, uint32_t b) { return dev_items[a].x < dev_items[b].x; });
-                        uint32_t way = 3u;  // the ways all pieces so far can be read: 1 upwards, 2 downwards
-                        for (size_t k = 0; k < pc.size() && way; ++k) {
-                            way &= mono[pc[k]].x;
-                            if (k) {
-                                const uint32_t last = mono[pc[k - 1]].z, first = mono[pc[k]].y;
-                                way &= (first > last ? 1u : 0u) | (first < last ? 2u : 0u);
-                            }
-                        }
-                        if (way && !pc.empty()) {
-                            for (uint32_t j : pc) dev_items[j].z |= kItemNoClaim;
-                            any = true;
-                        }
-                    }
-                    if (any) e = staged_copy(fp->items, dev_items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr);
-                }
-            }
-            if (d_mono) (void)hipFree(d_mono);
-            FAST_TRY(e);
-            if (no_claim) {  // how many there are (flatgfa_dev_plan_describe: no_claim_items)
-                if (dev_items.empty()) {
-                    dev_items.resize(items.size());
-                    FAST_TRY(staged_copy(dev_items.data(), fp->items, items.size() * sizeof(uint4), hipMemcpyDeviceToHost, nullptr));
-                }
-                for (const uint4 &it : dev_items) fp->n_noclaim += it.z >> 31;
-            }
-            }  // (!derived)
-            for (const uint4 &it : items) item_steps += it.y - it.x;
+        if (look) {
+            if (derived) fp->n_noclaim = known.n_noclaim;
+            else if (!item_dirs(g, fp, hooks.claim_all, &known)) return false;
+            const uint64_t item_steps = fp->class_steps[0];
             fp->item_steps = item_steps;
             // Items of paths that do not qualify as a whole: the stretches of them that lie in windows their path enters once
             // and walks one way (k_visit_bits, k_chunk_flags) -- k_scan gives the records of such blocks the no-claim tag too.
@@ -1091,15 +859,15 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
             // stream (fast_marks_start) and installs them between two later calls.  (Buckets laid out to the count too: a mark
             // rides on top of the ids of a whole block, and a block's first step starts a run in every build of k_scan -- the
             // marked build makes the records the counting call saw.)
-            fp->marks_wanted = no_claim && fp->tagged && !ranged && fp->n_noclaim < fp->n_items && !test_hook("FLATGFA_NO_CLAIM_BLOCKS_OFF") &&
+            fp->marks_wanted = !hooks.claim_all && fp->tagged && !ranged && fp->n_noclaim < fp->n_items && !hooks.marks_off &&
                                (((uint64_t)g.n_paths * n_win + 15) / 16 + 1) * 4 <= (256ull << 20);
             // ... and not worth looking for where the walks turn round all the time: a step against its item's grain spoils the
             // window it lies in, and with sixteen of them to a block of 1024 steps next to no block is left clean (the benchmark's
             // random walks: forty-five a block, one chunk in a thousand qualifies; a walk with a tandem repeat every 6400 steps: one
-            // in six blocks has any).  FLATGFA_NO_CLAIM_BLOCKS_MIN (tests) asks for the marks regardless.
-            if (fp->marks_wanted && counted[1] * 64 >= item_steps && !test_hook("FLATGFA_NO_CLAIM_BLOCKS_MIN")) fp->marks_wanted = false;
-            fp->est_records = runs64;
-            fp->narrow_emit = runs64 * 8 < item_steps;  // (long runs: see mode_wide)
+            // in six blocks has any).
+            if (fp->marks_wanted && known.against * 64 >= item_steps && !hooks.marks_always) fp->marks_wanted = false;
+            fp->est_records = known.records;
+            fp->narrow_emit = known.records * 8 < item_steps;  // (long runs: see mode_wide)
             plan_tick("range: items uploaded, k_item_dirs");
             // more than three records for four steps: not worth looking for runs (k_scan_dense)
             const bool can = !fp->dbg && dense_lds_bytes(fp->nwp) + 64 <= kLdsLimit;
@@ -1107,37 +875,22 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
             // ids jump about; steps that stay in one window make its LDS atomics queue on one
             // address.  Sized for the dense form (one record per step is the most either makes),
             // then timed both ways by the plan's creator.
-            fp->dense_maybe = can && runs64 * 2 > item_steps;
+            fp->dense_maybe = can && known.records * 2 > item_steps;
             fp->dense = fp->dense_maybe;
         }
-        if (const char *f = test_hook("FLATGFA_DENSE")) {  // tests, measurements
-            fp->dense = !fp->dbg && strtol(f, nullptr, 10) != 0 && dense_lds_bytes(fp->nwp) + 64 <= kLdsLimit;
+        if (hooks.dense) {  // tests, measurements
+            fp->dense = !fp->dbg && strtol(hooks.dense, nullptr, 10) != 0 && dense_lds_bytes(fp->nwp) + 64 <= kLdsLimit;
             fp->dense_maybe = false;
         }
     }
-    if (!short_items.empty()) {
-        FAST_TRY(hipMalloc(&fp->short_items, short_items.size() * sizeof(uint4)));
-        FAST_TRY(staged_copy(fp->short_items, short_items.data(), short_items.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr));
-    }
-    if (!medium_items.empty()) {
-        FAST_TRY(hipMalloc(&fp->medium_items, medium_items.size() * sizeof(uint4)));
-        FAST_TRY(staged_copy(fp->medium_items, medium_items.data(), medium_items.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr));
-    }
-    if (!tiny_items.empty()) {
-        FAST_TRY(hipMalloc(&fp->tiny_items, tiny_items.size() * sizeof(uint4)));
-        FAST_TRY(staged_copy(fp->tiny_items, tiny_items.data(), tiny_items.size() * sizeof(uint4), hipMemcpyHostToDevice, nullptr));
-    }
-    {
-        Vec<uint32_t> other;
-        for (const uint4 &it : short_items) other.push_back(it.w);
-        for (const uint4 &it : medium_items) other.push_back(it.w);
-        for (const uint4 &it : tiny_items) other.push_back(it.w);
-        fp->n_other = (uint32_t)other.size();
-        if (!other.empty()) {
-            FAST_TRY(hipMalloc(&fp->other_ids, other.size() * 4));
-            FAST_TRY(staged_copy(fp->other_ids, other.data(), other.size() * 4, hipMemcpyHostToDevice, nullptr));
-        }
-    }
+    Vec<uint32_t> other;
+    for (const Vec<uint4> *list : {&short_items, &medium_items, &tiny_items})
+        for (const uint4 &it : *list) other.push_back(it.w);
+    fp->n_other = (uint32_t)other.size();
+    if (!short_items.empty() && !upload(&fp->short_items, short_items)) return false;
+    if (!medium_items.empty() && !upload(&fp->medium_items, medium_items)) return false;
+    if (!tiny_items.empty() && !upload(&fp->tiny_items, tiny_items)) return false;
+    if (!other.empty() && !upload(&fp->other_ids, other)) return false;
     // (the attribute belongs to the kernel, not to the plan: set once per device by the translation unit that holds it)
     if (!path_kernels_setup() || !scan_kernels_setup() || !accum_kernels_setup()) return false;
     FAST_TRY(hipMalloc(&fp->work_counter, 256));
@@ -1167,9 +920,9 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
         const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(fp->n_items, 1u), fp->n_slots);
         const bool can8 = fp->tagged && wb == 12 && fp->n_shared <= 64 && fp->acc_parts == 1;
         fp->acc_slots = can8 && (uint64_t)fp->n_items + fp->max_back > 4ull * grid ? 8u : kTagSlots;
-        if (const char *f = test_hook("FLATGFA_ACC_SLOTS")) fp->acc_slots = can8 && strtol(f, nullptr, 10) == 8 ? 8u : kTagSlots;
+        if (hooks.acc_slots) fp->acc_slots = can8 && strtol(hooks.acc_slots, nullptr, 10) == 8 ? 8u : kTagSlots;
         if (fp->acc_slots == 8) fp->acc_pair = false;
-        if (const char *f = test_hook("FLATGFA_ACC_OWN")) fp->acc_own = strtol(f, nullptr, 10) != 0;  // tests, measurements
+        if (hooks.acc_own) fp->acc_own = strtol(hooks.acc_own, nullptr, 10) != 0;  // tests, measurements
     }
     if (fp->acc_pair) {
         FAST_TRY(hipMalloc(&fp->pair_part, (size_t)n_win * 2 * 2 * (1u << wb) * 4));
@@ -1179,94 +932,37 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
     if (fp->dense || fp->dense_maybe) fp->can_pack = false;
     if (want_packed && (fp->dense || fp->dense_maybe)) {  // (pass 1 by partition keeps the even layout)
         want_packed = false;
-        const int rc = alloc_buckets(fp, std::max<uint64_t>(cap, 4));
-        if (rc < 0) return false;
-        if (rc == 0) return true;
-        fp->bucket_records = (slots + fp->n_slots) * (uint64_t)fp->cap;
+        if (const int rc = even_buckets(fp, cap); rc <= 0) return rc == 0;
     }
     if (want_packed) {
-        // The counting call: k_scan alone, every sub-bucket without room (all records go to a sink), the
-        // items dealt in the fixed order every later call uses.  Its cursors are the layout.
-        const size_t row = (size_t)n_win + 1;
-        uint32_t *d_status = nullptr;
-        FAST_TRY(hipMalloc(&fp->pk_off, row * fp->n_slots * 4));
-        FAST_TRY(hipMemset(fp->pk_off, 0, row * fp->n_slots * 4));
-        FAST_TRY(hipMalloc(&fp->pk_base, (size_t)fp->n_slots * 8));
-        FAST_TRY(hipMemset(fp->pk_base, 0, (size_t)fp->n_slots * 8));
-        FAST_TRY(hipMalloc(&fp->buckets, 4096));
-        FAST_TRY(hipMalloc(&d_status, 256));
-        FAST_TRY(hipMemset(d_status, 0, 256));
-        fp->packed = true;
-        fp->cap = 0;
-        fp->eligible = true;
         const uint32_t lds_even = fp->lds_bytes_scan;
-        fp->lds_bytes_scan = scan_lds_bytes(fp->nwp, true, true);
-        const int rc = run_range(*fp, g, nullptr, nullptr, d_status, nullptr, nullptr, true);
-        Vec<uint32_t> cnt(slots);
-        hipError_t e = rc == FLATGFA_OK ? hipDeviceSynchronize() : hipErrorUnknown;
-        if (e == hipSuccess) e = staged_copy(cnt.data(), fp->counts, slots * 4, hipMemcpyDeviceToHost, nullptr);
-        if (e == hipSuccess) e = hipMemset(fp->counts, 0, slots * 4);
+        Vec<uint32_t> cnt;
         uint32_t st = 0;
-        if (e == hipSuccess) e = staged_copy(&st, d_status, 4, hipMemcpyDeviceToHost, nullptr);
-        (void)hipFree(d_status);
-        fp->eligible = false;
-        FAST_TRY(e);
+        if (!counting_call(g, fp, &cnt, &st)) return false;
         if (st & kStBounds) {  // (an id out of range: the atomic kernels report it; no layout to be had)
             fp->packed = false;
             fp->lds_bytes_scan = lds_even;
             return true;
         }
         plan_tick("range: packed buckets: the counting call");
-        const bool countable = !(st & kStBackOverflow);  // (blocks without any runs do not fit a packed call's queues: the even layout)
-        Vec<uint32_t> off(row * fp->n_slots);
-        Vec<uint64_t> base(fp->n_slots);
-        Vec<uint2> pk(slots);
-        uint64_t total = 0, deepest = 0;
-        bool fits = true;
-        for (uint32_t gq = 0; gq < fp->n_slots; ++gq) {
-            uint64_t o = 0;
-            base[gq] = total;
-            for (uint32_t wq = 0; wq < n_win; ++wq) {
-                const uint64_t room = ((uint64_t)cnt[(size_t)wq * fp->n_slots + gq] + 3) & ~3ull;  // (sub-buckets start on 16 bytes: pass 2 reads four records at a time)
-                off[gq * row + wq] = (uint32_t)o;
-                pk[(size_t)wq * fp->n_slots + gq] = make_uint2((uint32_t)(total + o), (uint32_t)room);
-                deepest = std::max(deepest, room);
-                o += room;
-            }
-            off[gq * row + n_win] = (uint32_t)o;  // the region's sink
-            o += 64;
-            fits = fits && o < (1ull << 30);      // (a region's byte offsets take 32 bits)
-            total += o;
-        }
-        fits = fits && countable && total < (1ull << 32);
-        // (three times the deepest: a call deals the items as they come, so its fullest sub-bucket is not the counted one, and
-        // what ends up more than half full is doubled for headroom -- flatgfa_dev_plan_create; twice the deepest was kept even,
-        // doubled there, and made again packed after all)
-        if (fits && ask_first && (slots + fp->n_slots) * std::max<uint64_t>(3 * deepest, 4) * 4 <= even_limit) {
-            fits = false;  // the even layout can be had: kept (its k_scan deals the items as they come and keeps one table less in LDS)
-            cap = std::max<uint64_t>(cap, 3 * deepest);
-        }
+        const PackedLayout l = packed_layout(cnt, n_win, fp->n_slots, !(st & kStBackOverflow), ask_first, even_limit, cap);
         (void)hipFree(fp->buckets);
         fp->buckets = nullptr;
-        if (!fits) {  // (not the case this layout is for: the even one, if it can be had)
+        if (!l.fits) {  // (not the case this layout is for: the even one, if it can be had)
             fp->packed = false;
             fp->lds_bytes_scan = lds_even;
             (void)hipFree(fp->pk_off);
             (void)hipFree(fp->pk_base);
             fp->pk_off = nullptr;
             fp->pk_base = nullptr;
-            const int rc2 = alloc_buckets(fp, std::max<uint64_t>(cap, 4));
-            if (rc2 < 0) return false;
-            if (rc2 == 0) return true;
-            fp->bucket_records = (slots + fp->n_slots) * (uint64_t)fp->cap;
+            if (const int rc = even_buckets(fp, l.cap); rc <= 0) return rc == 0;
         } else {
-            FAST_TRY(hipMalloc(&fp->buckets, std::max<uint64_t>(total, 64) * 4));
-            FAST_TRY(staged_copy(fp->pk_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, nullptr));
-            FAST_TRY(staged_copy(fp->pk_base, base.data(), base.size() * 8, hipMemcpyHostToDevice, nullptr));
-            FAST_TRY(hipMalloc(&fp->pk, slots * sizeof(uint2)));
-            FAST_TRY(staged_copy(fp->pk, pk.data(), slots * sizeof(uint2), hipMemcpyHostToDevice, nullptr));
-            fp->cap = (uint32_t)std::max<uint64_t>(deepest, 4);  // (what describe() reports: the deepest sub-bucket)
-            fp->bucket_records = total;
+            FAST_TRY(hipMalloc(&fp->buckets, std::max<uint64_t>(l.total, 64) * 4));
+            FAST_TRY(staged_copy(fp->pk_off, l.off.data(), l.off.size() * 4, hipMemcpyHostToDevice, nullptr));
+            FAST_TRY(staged_copy(fp->pk_base, l.base.data(), l.base.size() * 8, hipMemcpyHostToDevice, nullptr));
+            if (!upload(&fp->pk, l.pk)) return false;
+            fp->cap = (uint32_t)std::max<uint64_t>(l.deepest, 4);  // (what describe() reports: the deepest sub-bucket)
+            fp->bucket_records = l.total;
         }
         plan_tick("range: packed buckets: laid out, allocated, tables uploaded");
     }
@@ -1274,15 +970,42 @@ static bool create_range(const flatgfa_dev_graph_t &g, const uint32_t *hb, const
     return true;
 }
 
-// The plans of all segment ranges for one set of path spans, appended to `plans`.  *all: every one
-// of them is eligible; *many: one of them is kept from tagged calls by its number of items alone.
-static bool append_ranges(const flatgfa_dev_graph_t &g, const uint32_t *hb, const uint32_t *he, uint32_t max_win, uint32_t force_wb,
-                          std::vector<FastPlan> *plans, bool *all, bool *many, bool *want12 = nullptr, uint32_t n_groups = 1) {
+// The ranges of one attempt at a plan -- all segment ranges for one set of path spans, or for each of its path groups --
+// destroyed unless the plan adopts them.  all: every one of them is eligible; many: one of them is kept from tagged
+// calls by its number of items alone; want12: ... or by its split paths' bitsets alone.
+struct Ranges {
+    std::vector<FastPlan> plans;
+    bool all = true, many = false, want12 = false;
+    Ranges() = default;
+    Ranges(const Ranges &) = delete;
+    Ranges &operator=(const Ranges &) = delete;
+    ~Ranges() { clear(); }
+    void clear() {
+        for (FastPlan &q : plans) fast_plan_destroy(&q);
+        plans.clear();
+        all = true, many = want12 = false;
+    }
+    bool all_tagged() const {
+        return all && std::all_of(plans.begin(), plans.end(), [](const FastPlan &q) { return q.tagged; });
+    }
+    void adopt(FastPlan *fp) {
+        *fp = plans[0];
+        fp->n_more = (uint32_t)plans.size() - 1;
+        fp->more = fp->n_more ? new FastPlan[fp->n_more] : nullptr;
+        size_t k = 0;
+        for_each_range(*fp, [&](FastPlan &q) { if (k++) q = plans[k - 1]; });
+        plans.clear();
+    }
+};
+
+// The plans of all segment ranges for one set of path spans, appended to `out`.
+static bool append_ranges(const flatgfa_dev_graph_t &g, const uint32_t *hb, const uint32_t *he, uint32_t max_win, uint32_t force_wb, Ranges *out,
+                          uint32_t n_groups = 1) {
     uint64_t max_range = (uint64_t)max_win << (force_wb ? force_wb : 13u);
     if (const char *f = test_hook("FLATGFA_RANGE_SEGS")) max_range = std::max<uint64_t>(8192, strtoull(f, nullptr, 10) & ~8191ull);  // tests
     const uint32_t n_ranges = (uint32_t)((g.n_segs + max_range - 1) / max_range);
     if (n_ranges > 64) {
-        *all = false;
+        out->all = false;
         return true;
     }
     const uint32_t per = (uint32_t)((((uint64_t)g.n_segs + n_ranges - 1) / n_ranges + 8191) & ~8191ull);
@@ -1293,29 +1016,24 @@ static bool append_ranges(const flatgfa_dev_graph_t &g, const uint32_t *hb, cons
             fast_plan_destroy(&q);
             return false;
         }
-        *many = *many || q.too_many_items;
-        if (want12) *want12 = *want12 || q.want_wb12;
-        plans->push_back(q);
+        out->many = out->many || q.too_many_items;
+        out->want12 = out->want12 || q.want_wb12;
+        out->plans.push_back(q);
         if (!q.eligible) {  // all ranges or none
-            *all = false;
+            out->all = false;
             break;
         }
     }
     return true;
 }
 
-static void destroy_plans(std::vector<FastPlan> *plans) {
-    for (FastPlan &q : *plans) fast_plan_destroy(&q);
-    plans->clear();
-}
-
-static void adopt_plans(std::vector<FastPlan> *plans, FastPlan *fp) {
-    *fp = (*plans)[0];
-    fp->n_more = (uint32_t)plans->size() - 1;
-    fp->more = fp->n_more ? new FastPlan[fp->n_more] : nullptr;
-    size_t k = 0;
-    for_each_range(*fp, [&](FastPlan &q) { if (k++) q = (*plans)[k - 1]; });
-    plans->clear();
+// The ranges made again with windows of 2^wb segments: they take `cur`'s place when they are one tagged plan that `accept`s.
+template <class Accept>
+static bool try_other_windows(const flatgfa_dev_graph_t &g, const uint32_t *hb, const uint32_t *he, uint32_t wb, Ranges *cur, Accept accept) {
+    Ranges alt;
+    if (!append_ranges(g, hb, he, kMaxWinTagged, wb, &alt)) return false;
+    if (alt.all && !alt.many && alt.plans.size() == 1 && alt.plans[0].eligible && alt.plans[0].tagged && accept(alt.plans[0])) cur->plans.swap(alt.plans);
+    return true;
 }
 
 static bool fast_plan_create_impl(const flatgfa_dev_graph_t &g, const uint32_t *hb, const uint32_t *he, FastPlan *fp);
@@ -1354,6 +1072,8 @@ static bool fast_plan_create_impl(const flatgfa_dev_graph_t &g, const uint32_t *
         groups_ok = want_groups != 0;
         want_groups = std::max(1u, std::min(64u, want_groups));
     }
+    const bool range_segs_given = test_hook("FLATGFA_RANGE_SEGS") != nullptr;
+    const bool windows_free = !test_hook("FLATGFA_WB") && !range_segs_given;  // (no test has fixed the windows or the ranges)
     Vec<uint32_t> busy;  // the paths that have steps
     for (uint32_t p = 0; p < g.n_paths; ++p)
         if (he[p] > hb[p]) busy.push_back(p);
@@ -1369,38 +1089,20 @@ static bool fast_plan_create_impl(const flatgfa_dev_graph_t &g, const uint32_t *
     bool tried_wb12 = false;
     for (size_t ti = 0; ti < tries.size(); ++ti) {
         const uint32_t max_win = tries[ti].max_win, force_wb = tries[ti].force_wb;
-        std::vector<FastPlan> plans;
-        bool all = true, many = false, want12 = false;
+        Ranges cur;  // (gone at the end of the try unless adopted)
         if (want_groups == 1) {
-            if (!append_ranges(g, hb, he, max_win, force_wb, &plans, &all, &many, &want12)) {
-                destroy_plans(&plans);
-                return false;
-            }
-            bool all_tagged = all;
-            for (const FastPlan &q : plans) all_tagged = all_tagged && q.tagged;
-            if (want12 && !all_tagged && !force_wb && !tried_wb12 && !test_hook("FLATGFA_WB") && !test_hook("FLATGFA_RANGE_SEGS")) {
+            if (!append_ranges(g, hb, he, max_win, force_wb, &cur)) return false;
+            const bool all_tagged = cur.all_tagged();
+            if (cur.want12 && !all_tagged && !force_wb && !tried_wb12 && windows_free) {
                 tried_wb12 = true;
                 tries.push_back({kMaxWinTagged, 12u});  // next; if that does not yield a tagged plan either, this try comes again
                 tries.push_back({max_win, 0u});
-                destroy_plans(&plans);
                 continue;
             }
-            if (force_wb && !all_tagged && !many) {  // (the smaller windows were for tags' sake only)
-                destroy_plans(&plans);
-                continue;
-            }
-            if (all && !(many && groups_ok)) {
-                // 4096-segment windows on a graph that would get 8192-segment ones, where pass 2 has use for the LDS they
-                // free: a pass-1 workgroup that takes dozens of claiming items leaves every sub-bucket with dozens of
-                // tags, and pass 2 hands its four private bitsets on all the time -- with the smaller windows it has
-                // eight (16 000 paths of 100 k steps on 16 M segments: pass 2 2.14 -> 1.81 ms, pass 1 pays 0.1 for twice
-                // the windows; with eight items per workgroup, or items that claim nothing, it is a loss: NOTES R5.12).
-                const auto wants_small_windows = [&](const FastPlan &q) {
-                    return q.eligible && q.tagged && q.wb == 13 && !q.n_more && g.n_segs <= (uint64_t)kMaxWinTagged << 12 && !test_hook("FLATGFA_WB") &&
-                           !test_hook("FLATGFA_RANGE_SEGS") && q.n_items >= 16ull * q.n_slots && 2ull * q.n_noclaim < q.n_items && q.n_shared <= 64 &&
-                           q.est_records / q.n_win >= 32768;
-                };
-                // ... and the other way round: 8192-segment windows on a graph of two to four million segments.  Pass 2 pays a fixed
+            if (force_wb && !all_tagged && !cur.many) continue;  // (the smaller windows were for tags' sake only)
+            if (cur.all && !(cur.many && groups_ok)) {
+                const bool one_plan = !force_wb && windows_free && cur.plans.size() == 1 && cur.plans[0].eligible && cur.plans[0].tagged && !cur.plans[0].n_more;
+                // 8192-segment windows on a graph of two to four million segments.  Pass 2 pays a fixed
                 // part per window (its arrays cleared, 256 sub-buckets opened, the scan and the store: 15 us of a workgroup's time
                 // whatever the records), and 4096-segment windows are two to four per CU there; with half as many, twice as wide,
                 // cfg-L's walks on 4 M segments take 0.186 -> 0.162 ms (`k_accum` 85 -> 67 us, `k_scan` 97 -> 92: NOTES R6.9).  Only where
@@ -1408,98 +1110,70 @@ static bool fast_plan_create_impl(const flatgfa_dev_graph_t &g, const uint32_t *
                 // pass-1 workgroup: 2000 contigs on 4 M segments lose 17 % of pass 2 that way), split paths' shared bitsets, the
                 // wave-per-path kernels' records (they know 4096-segment windows only).
                 const auto wants_wide_windows = [&](const FastPlan &q) {
-                    return q.eligible && q.tagged && q.wb == 12 && !q.n_more && !q.packed && !test_hook("FLATGFA_WB") && !test_hook("FLATGFA_RANGE_SEGS") &&
-                           q.n_win >= 2u * q.n_cus && q.acc_slots == kTagSlots && q.acc_parts == 1 && q.n_shared == 0 && !q.n_short && !q.n_medium && !q.n_tiny &&
-                           (uint64_t)q.n_items <= 4ull * q.n_slots && !q.dense && !q.dense_maybe;
+                    return q.wb == 12 && !q.packed && q.n_win >= 2u * q.n_cus && q.acc_slots == kTagSlots && q.acc_parts == 1 && q.n_shared == 0 && !q.n_short &&
+                           !q.n_medium && !q.n_tiny && (uint64_t)q.n_items <= 4ull * q.n_slots && !q.dense && !q.dense_maybe;
                 };
-                if (!force_wb && plans.size() == 1 && wants_wide_windows(plans[0])) {
-                    std::vector<FastPlan> alt;
-                    bool a_all = true, a_many = false;
-                    if (!append_ranges(g, hb, he, kMaxWinTagged, 13u, &alt, &a_all, &a_many)) {
-                        destroy_plans(&alt);
-                        destroy_plans(&plans);
-                        return false;
-                    }
-                    if (a_all && !a_many && alt.size() == 1 && alt[0].eligible && alt[0].tagged && alt[0].n_shared == 0 && !alt[0].packed) {
-                        destroy_plans(&plans);
-                        plans.swap(alt);
-                    } else {
-                        destroy_plans(&alt);
-                    }
-                }
-                if (!force_wb && plans.size() == 1 && wants_small_windows(plans[0])) {
-                    std::vector<FastPlan> alt;
-                    bool a_all = true, a_many = false;
-                    if (!append_ranges(g, hb, he, kMaxWinTagged, 12u, &alt, &a_all, &a_many)) {
-                        destroy_plans(&alt);
-                        destroy_plans(&plans);
-                        return false;
-                    }
-                    if (a_all && !a_many && alt.size() == 1 && alt[0].eligible && alt[0].tagged && alt[0].acc_slots == 8) {
-                        destroy_plans(&plans);
-                        plans.swap(alt);
-                    } else {
-                        destroy_plans(&alt);
-                    }
-                }
-                adopt_plans(&plans, fp);
+                if (one_plan && wants_wide_windows(cur.plans[0]) &&
+                    !try_other_windows(g, hb, he, 13u, &cur, [](const FastPlan &a) { return a.n_shared == 0 && !a.packed; }))
+                    return false;
+                // ... and the other way round, 4096-segment windows on a graph that would get 8192-segment ones, where pass 2 has use
+                // for the LDS they free: a pass-1 workgroup that takes dozens of claiming items leaves every sub-bucket with dozens of
+                // tags, and pass 2 hands its four private bitsets on all the time -- with the smaller windows it has
+                // eight (16 000 paths of 100 k steps on 16 M segments: pass 2 2.14 -> 1.81 ms, pass 1 pays 0.1 for twice
+                // the windows; with eight items per workgroup, or items that claim nothing, it is a loss: NOTES R5.12).
+                const auto wants_small_windows = [&](const FastPlan &q) {
+                    return q.wb == 13 && g.n_segs <= (uint64_t)kMaxWinTagged << 12 && q.n_items >= 16ull * q.n_slots && 2ull * q.n_noclaim < q.n_items &&
+                           q.n_shared <= 64 && q.est_records / q.n_win >= 32768;
+                };
+                if (one_plan && wants_small_windows(cur.plans[0]) && !try_other_windows(g, hb, he, 12u, &cur, [](const FastPlan &a) { return a.acc_slots == 8; }))
+                    return false;
+                cur.adopt(fp);
                 return true;
             }
         } else {
-            many = true;
+            cur.many = true;
         }
-        if (many && groups_ok && busy.size() >= 2) {
+        if (cur.many && groups_ok && busy.size() >= 2) {
             // an even share of the paths per group; more groups while some group still has too many items (long paths are cut into pieces)
             uint32_t hint_items = (uint32_t)busy.size(), hint_slots = 256;
-            if (!plans.empty() && plans[0].n_slots) {
-                hint_slots = plans[0].n_slots;
-                hint_items = std::max<uint32_t>(hint_items, plans[0].n_items);
+            if (!cur.plans.empty() && cur.plans[0].n_slots) {
+                hint_slots = cur.plans[0].n_slots;
+                hint_items = std::max<uint32_t>(hint_items, cur.plans[0].n_items);
             }
-            destroy_plans(&plans);
+            cur.clear();
             uint32_t n_groups = std::max<uint32_t>(want_groups, (uint32_t)((hint_items + 384ull * hint_slots - 1) / (384ull * hint_slots)));
             n_groups = std::max(n_groups, 2u);
             for (; n_groups <= 64 && n_groups <= busy.size(); n_groups *= 2) {
-                bool g_all = true, g_many = false, hip_ok = true;
+                Ranges grp;
                 Vec<uint32_t> hbk(g.n_paths), hek(g.n_paths);
-                for (uint32_t k = 0; k < n_groups && g_all && hip_ok; ++k) {
+                for (uint32_t k = 0; k < n_groups && grp.all; ++k) {
                     const size_t lo = busy.size() * k / n_groups, hi = busy.size() * (k + 1) / n_groups;
                     for (uint32_t p = 0; p < g.n_paths; ++p) hbk[p] = hek[p] = hb[p];  // (a path outside the group: no steps)
                     for (size_t i = lo; i < hi; ++i) hek[busy[i]] = he[busy[i]];
-                    const size_t first = plans.size();
-                    hip_ok = append_ranges(g, hbk.data(), hek.data(), max_win, force_wb, &plans, &g_all, &g_many, nullptr, n_groups);
-                    for (size_t i = first; i < plans.size(); ++i) {
-                        plans[i].accumulate = k > 0;
-                        g_all = g_all && plans[i].tagged;  // (a group is only worth it tagged)
+                    const size_t first = grp.plans.size();
+                    if (!append_ranges(g, hbk.data(), hek.data(), max_win, force_wb, &grp, n_groups)) return false;
+                    for (size_t i = first; i < grp.plans.size(); ++i) {
+                        grp.plans[i].accumulate = k > 0;
+                        grp.all = grp.all && grp.plans[i].tagged;  // (a group is only worth it tagged)
                     }
                 }
-                if (!hip_ok) {
-                    destroy_plans(&plans);
-                    return false;
-                }
-                if (g_all && !plans.empty()) {
-                    adopt_plans(&plans, fp);
+                if (grp.all && !grp.plans.empty()) {
+                    grp.adopt(fp);
                     fp->n_groups = n_groups;
                     return true;
                 }
-                destroy_plans(&plans);
-                if (!g_many) break;  // (something else stands in the way)
+                if (!grp.many) break;  // (something else stands in the way)
             }
             if (force_wb) continue;  // (the smaller windows were for tags' sake only)
             // no luck: the plan the whole path set gets
-            all = true;
-            many = false;
-            if (!append_ranges(g, hb, he, max_win, force_wb, &plans, &all, &many)) {
-                destroy_plans(&plans);
-                return false;
-            }
-            if (all) {
-                adopt_plans(&plans, fp);
+            if (!append_ranges(g, hb, he, max_win, force_wb, &cur)) return false;
+            if (cur.all) {
+                cur.adopt(fp);
                 return true;
             }
         }
-        destroy_plans(&plans);
         if (ti + 1 == tries.size() && max_win == kMaxWinTagged && !force_wb) {
-            const uint64_t max_range = test_hook("FLATGFA_RANGE_SEGS") ? 0 : (uint64_t)max_win << 13;
+            const uint64_t max_range = range_segs_given ? 0 : (uint64_t)max_win << 13;
             const uint64_t n_ranges = max_range ? (g.n_segs + max_range - 1) / max_range : 1;
             if (((uint64_t)g.n_segs + 8191) / 8192 > kMaxWin * n_ranges) tries.push_back({kMaxWin, 0u});  // (else the smaller cut-off would make the same ranges)
         }

@@ -32,6 +32,24 @@ int device_cu_count(int device);
 // FLATGFA_TIMING=1: prints what the calling thread spent since its last tick (the device drained first), to stderr; `what` == nullptr restarts the clock
 void plan_tick(const char *what);
 
+// ---- what the plan decides by (depth_plan_host.hpp); the kernels' own constants are in depth_fast_kernels.hpp ----
+constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+constexpr uint32_t kAccWaves = 16;         // waves of a pass-2 workgroup
+constexpr uint32_t kShortMax = 2048;       // steps; longer paths go through k_scan (or the medium variant)
+constexpr uint32_t kTinyMax = 128;         // steps: a wave holds the whole path (k_scan_tiny)
+#ifndef FGFA_QCAP
+#define FGFA_QCAP 416
+#endif
+constexpr uint32_t kQCap = FGFA_QCAP;  // at least 64 left over + up to 257 from sixteen lanes of a block; a short path has at most kQCap - 16 runs, hence bitset words: its 512-entry hash set must not fill up
+constexpr uint32_t kMediumRuns = 1500;
+constexpr uint32_t kMaxHandBack = 4096;    // short paths k_scan_short may hand back to k_scan per call
+constexpr uint32_t kTagCount = 512;        // tags a record can carry (depth_fast_kernels.hpp: kTagShift)
+constexpr uint32_t kItemNoClaim = 0x80000000u;  // items[].z: the item's path is strictly monotone in the segment ids
+constexpr uint32_t kTagSlots = 4;
+constexpr uint32_t kMaxShared = 128;      // bitsets of split paths pass 2 has LDS for (4096-segment windows)
+constexpr uint32_t kMaxWin = 2048;        // windows per launch (LDS tables: the cursors and their snapshots per item)
+constexpr uint32_t kMaxWinTagged = 4096;  // ... of a plan whose calls are always tagged: k_scan keeps no snapshots then
+
 struct FastPlan {
     bool eligible = false;
     bool cap_forced = false;   // FLATGFA_BUCKET_CAP (tests): the capacity must not grow

@@ -4,7 +4,8 @@
 //   depth_scan_runs.hip   pass 1 from the run-length image of the steps: k_scan_runs, and the kernels that make the image
 //   depth_scan_paths.hip  pass 1 for short paths: k_scan_short / k_scan_medium / k_scan_tiny (a wave per path)
 //   depth_accum.hip       pass 2: k_accum, k_path_reduce
-//   depth_fast.hip        the plan (which kernel walks which path, the scratch) and the launches
+//   depth_fast.hip        the plan (which kernel walks which path, the scratch) and the launches; what it decides on
+//                         the host is in depth_plan_host.hpp, the constants it decides by in depth_fast.hpp
 // DESIGN.md section 3 is the long version.  Constants, inline device functions and plain structs only (the same in every
 // translation unit that includes it).
 #pragma once
@@ -20,10 +21,9 @@ namespace fgfa_dev {
 
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
-constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 constexpr uint32_t kMaxSlots = 1024;  // sub-buckets per window (= workgroups of pass 1) k_accum can stage
 constexpr int kAccThreads = 1024;
-constexpr uint32_t kAccWaves = kAccThreads / 64;
+static_assert(kAccThreads == 64 * (int)kAccWaves, "pass 2's workgroup is the waves the plan deals to");
 constexpr uint32_t kLdsLimit = 160 * 1024;
 // status word bits (flatgfa_dev_status)
 constexpr uint32_t kStBounds = 1u, kStDebug = 2u, kStOverflow = 4u, kStInternal = 8u, kStBackOverflow = 16u, kStStale = 32u;  // (32: FLATGFA_CHECK_NO_CLAIM=1 found the step values changed behind the plan)  // (16: more short paths handed back than the list holds: larger buckets would not help, the atomic kernels complete the call)  // (8: an invariant between the two passes did not hold -- a bug, reported as an error rather than as counts)
@@ -41,7 +41,6 @@ constexpr uint32_t kCutMask = UNIQ ? 31u : kRunSpan - 1u;
 constexpr uint32_t kShortWinBits = 12;
 constexpr uint32_t kShortMaxWin = 256;     // LDS cursor table entries of k_scan_short
 constexpr uint32_t kShortMaxSegs = 1u << 20;
-constexpr uint32_t kShortMax = 2048;       // steps; longer paths go through k_scan (or the medium variant)
 constexpr uint32_t kDummyBase = 1u << 20;  // ids from here up stand in for steps outside the path (never emitted)
 constexpr int kShortHash = 9;              // per-wave hash set of 512 (bitset word index + 1, bits) pairs
 // The medium-path variant: hash sets of 2048 entries, for paths whose run count (known to the plan) fits
@@ -57,8 +56,6 @@ constexpr uint32_t kQPaired = 328;  // a paired wave's run queue: 64 left over +
 #define FGFA_SHORT_WAVES 16
 #endif
 constexpr int kShortWaves = FGFA_SHORT_WAVES;  // waves of a k_scan_short workgroup (measurements: fewer = lower occupancy)
-constexpr uint32_t kMediumRuns = 1500;
-constexpr uint32_t kMaxHandBack = 4096;    // short paths k_scan_short may hand back to k_scan per call
 
 // ---- tagged records ----
 // A record of k_scan is (window-relative first segment) | (length - 1) << wb.  In a *tagged* call it
@@ -80,15 +77,11 @@ constexpr uint32_t kMaxHandBack = 4096;    // short paths k_scan_short may hand 
 //                  true for it: its records count for depth and for unique depth alike, pass 2 applies them
 //                  without a bitset, and the item needs neither a private slot nor a shared one.  The plan
 //                  finds these items when it is made (k_item_dirs; items[].z bit 31).
-constexpr uint32_t kTagShift = 23, kTagCount = 1u << (32 - kTagShift);
+constexpr uint32_t kTagShift = 23;
+static_assert(kTagCount == 1u << (32 - kTagShift), "the tag is what the shift leaves of a record");
 constexpr uint32_t kTagNoClaim = kTagCount - 1u;
-constexpr uint32_t kItemNoClaim = 0x80000000u;  // items[].z: the item's path is strictly monotone in the segment ids
-constexpr uint32_t kTagSlots = 4;
-constexpr uint32_t kMaxShared = 128;      // bitsets of split paths pass 2 has LDS for (4096-segment windows)
 
 // ---- k_scan ----
-constexpr uint32_t kMaxWin = 2048;        // windows per launch (LDS tables: the cursors and their snapshots per item)
-constexpr uint32_t kMaxWinTagged = 4096;  // ... of a plan whose calls are always tagged: k_scan keeps no snapshots then
 constexpr uint32_t kInvalid = 0xFFFFFFFFu;  // queue entry that starts no run (terminates the one before it)
 constexpr uint32_t kQ2 = 64 + 1024 + 8;   // queue entries per wave: what is left over + one all-starts block
 
@@ -500,12 +493,7 @@ struct AccTimer {
 };
 
 // ---- the wave-per-path kernels' queues and tables (the plan sorts the paths by what fits them) ----
-#ifndef FGFA_QCAP
-#define FGFA_QCAP 416
-#endif
-constexpr uint32_t kQCap = FGFA_QCAP;  // at least 64 left over + up to 257 from sixteen lanes of a block; a short path has at most kQCap - 16 runs, hence bitset words: its 512-entry hash set must not fill up
 constexpr uint32_t kPCap = 96;   // parked claims (two words each): 31 left over + up to 64 from one chunk
-constexpr uint32_t kTinyMax = 128;   // steps
 #ifndef FGFA_TINY_BITS
 #define FGFA_TINY_BITS 8
 #endif

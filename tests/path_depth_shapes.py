@@ -54,6 +54,7 @@ def source_constants() -> Dict[str, int]:
         assert m, pat
         return int(m.group(1))
     acc, dev, fast, kh = text("depth_accum.hip"), text("depth_device.hip"), text("depth_fast.hip"), text("depth_fast_kernels.hpp")
+    ph = text("depth_fast.hpp")  # (the constants the plan decides by)
     assert re.search(r"k_accum<false, 12, true>", text("depth_fast.hip") + acc), "the fused build: depth only, 4096-segment windows, PSUM"
     assert re.search(r"constexpr int kPer = kW / kAccThreads;", acc)
     assert re.search(r"for \(uint32_t wdw = lane; wdw < n_win; wdw \+= 64u\)", acc)
@@ -68,7 +69,7 @@ def source_constants() -> Dict[str, int]:
         "SUM_THREADS": one(r"constexpr int kSumThreads = (\d+);", dev), "BATCH": one(r"constexpr int kBatch = (\d+);", dev),
         "MAX_SPLIT": one(r"split = std::max<uint32_t>\(1u, std::min<uint32_t>\((\d+)u, \(uint32_t\)\(pl->n_cus \* \d+\) / n_ids\)\);", dev),
         "JOBS_PER_CU": one(r"split = std::max<uint32_t>\(1u, std::min<uint32_t>\(\d+u, \(uint32_t\)\(pl->n_cus \* (\d+)\) / n_ids\)\);", dev),
-        "SHORT_MAX": one(r"constexpr uint32_t kShortMax = (\d+);", kh), "TINY_MAX": one(r"constexpr uint32_t kTinyMax = (\d+);", kh),
+        "SHORT_MAX": one(r"constexpr uint32_t kShortMax = (\d+);", ph), "TINY_MAX": one(r"constexpr uint32_t kTinyMax = (\d+);", ph),
         "SHORT_MAX_SEGS": 1 << one(r"constexpr uint32_t kShortMaxSegs = 1u << (\d+);", kh),
     }
 
