@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/flatgfa.h"
+#include "depth_call_host.hpp"
 #include "depth_fast.hpp"
 #include "temp_arena.hpp"
 #include "host_copy.hpp"
@@ -1090,22 +1091,27 @@ static int atomic_seg_depth(flatgfa_dev_plan_t *pl, uint32_t *depth_out, uint32_
     return FLATGFA_OK;
 }
 
+// What every node-depth call of the handle starts with: the side jobs' results are installed, the call is noted as the one
+// flatgfa_dev_status can run again, and (FLATGFA_CHECK_NO_CLAIM=1) the plan's facts about the steps are looked at again.
+static int begin_depth_call(flatgfa_dev_plan_t *pl, uint32_t *depth, uint32_t *uniq, uint64_t *len, uint64_t *weighted, hipStream_t stream) {
+    marks_poll(pl, false, true);  // (the per-block no-claim marks and the run-length image, once they are there: installed between two calls)
+    pl->last_fast = pl->fast.eligible;
+    pl->last_depth = depth;
+    pl->last_uniq = uniq;
+    pl->last_len = len;
+    pl->last_weighted = weighted;
+    pl->calls_since_status += 1;
+    if (!pl->check_facts || !pl->fast.eligible) return FLATGFA_OK;
+    return fast_check_plan_facts(pl->fast, pl->g, pl->hb.data(), pl->he.data(), pl->status, stream);
+}
+
 extern "C" int flatgfa_dev_seg_depth(flatgfa_dev_plan_t *pl, uint32_t *depth_out, uint32_t *uniq_out, void *stream_) {
     if (!pl || (!depth_out && pl->g.n_segs)) { set_error("dev_seg_depth: NULL argument"); return FLATGFA_ERR_ARG; }
     hipStream_t stream = (hipStream_t)stream_;
     const flatgfa_dev_graph_t &g = pl->g;
     if (g.n_segs == 0) return FLATGFA_OK;
-    marks_poll(pl, false, true);  // (the per-block no-claim marks and the run-length image, once they are there: installed between two calls)
-    pl->last_fast = pl->fast.eligible;
-    pl->last_depth = depth_out;
-    pl->last_uniq = uniq_out;
-    pl->last_len = pl->last_weighted = nullptr;
-    pl->calls_since_status += 1;
+    if (const int rc = begin_depth_call(pl, depth_out, uniq_out, nullptr, nullptr, stream)) return rc;
     if (pl->fast.eligible) {
-        if (pl->check_facts) {
-            const int rc = fast_check_plan_facts(pl->fast, g, pl->hb.data(), pl->he.data(), pl->status, stream);
-            if (rc) return rc;
-        }
         const int rc = plan_fast_call(pl, depth_out, uniq_out, stream);
         if (rc == FLATGFA_OK) run_start_behind(pl, stream);
         return rc;
@@ -1198,17 +1204,7 @@ extern "C" int flatgfa_dev_path_depth_all(flatgfa_dev_plan_t *pl, uint32_t *dept
         FGFA_HIP_OR(hipMemsetAsync(weighted_out, 0, (size_t)g.n_paths * 8, (hipStream_t)stream_), return FLATGFA_ERR_HIP);
         return FLATGFA_OK;
     }
-    marks_poll(pl, false, true);
-    pl->last_fast = pl->fast.eligible;
-    pl->last_depth = depth_out;
-    pl->last_uniq = nullptr;
-    pl->last_len = length_out;
-    pl->last_weighted = weighted_out;
-    pl->calls_since_status += 1;
-    if (pl->check_facts && pl->fast.eligible) {
-        const int rc = fast_check_plan_facts(pl->fast, g, pl->hb.data(), pl->he.data(), pl->status, (hipStream_t)stream_);
-        if (rc) return rc;
-    }
+    if (const int rc = begin_depth_call(pl, depth_out, nullptr, length_out, weighted_out, (hipStream_t)stream_)) return rc;
     return path_depth_all_enqueue(pl, depth_out, length_out, weighted_out, (hipStream_t)stream_, true);
 }
 
@@ -1220,8 +1216,19 @@ extern "C" int flatgfa_dev_path_overlaps(flatgfa_dev_plan_t *pl, const uint32_t 
                                           (hipStream_t)stream_);
 }
 
-// Status word bits set by the kernels: 1 = an id was out of range, 2 = a diagnostic mode's
-// sentinel, 4 = a record did not fit its sub-bucket (depth_fast.hip).
+// The last node-depth call ran out of sub-bucket room, so its outputs are incomplete: run
+// it again with four times the room, or -- when the plan cannot grow, or the hand-back list was full, which is not
+// a matter of bucket room -- through the atomic kernels.  The scratch cleans itself in pass 2, whatever was dropped.
+static int redo_last_call(flatgfa_dev_plan_t *pl, bool atomic, hipStream_t stream) {
+    const bool grown = !atomic && plan_grow(pl);
+    if (atomic) pl->fast.eligible = false;  // (later calls take the atomic kernels right away)
+    if (!grown) pl->last_fast = false;
+    if (pl->last_len) return path_depth_all_enqueue(pl, pl->last_depth, pl->last_len, pl->last_weighted, stream, grown);
+    if (grown) return plan_fast_call(pl, pl->last_depth, pl->last_uniq, stream);
+    return atomic_seg_depth(pl, pl->last_depth, pl->last_uniq, stream);
+}
+
+// Status word bits set by the kernels: depth_fast.hpp (kSt*); what a word asks for: status_verdict (depth_call_host.hpp).
 extern "C" int flatgfa_dev_status(flatgfa_dev_plan_t *pl, void *stream_) {
     if (!pl) return FLATGFA_ERR_ARG;
     hipStream_t stream = (hipStream_t)stream_;
@@ -1238,55 +1245,43 @@ extern "C" int flatgfa_dev_status(flatgfa_dev_plan_t *pl, void *stream_) {
             pl->calls_since_status = 0;
             marks_poll(pl, false);  // (no call is in flight: if the marks' job is done, what it found is installed -- it is never waited for here)
         }
+        const StatusAction act = status_verdict(st3, n_calls, attempt, pl->last_fast, pl->last_depth != nullptr);
         if (st3[2]) {
             // A call filled a sub-bucket more than half: k_scan deals its items to the workgroups as they
             // come, so a later call may fill it differently -- on a graph whose paths run along it,
             // twice as much when two of a workgroup's items meet in a window.  Make room now (no call
             // is in flight), not when a call enqueued among others has already run out.
             FGFA_HIP_OR(hipMemsetAsync(pl->status + 2, 0, 4, stream), return FLATGFA_ERR_HIP);
-            if (!(st & (4u | 16u)) && pl->fast.eligible) (void)plan_grow(pl, true);  // (a plan at its limit stays as it is)
+            if (act.grow_ahead && pl->fast.eligible) (void)plan_grow(pl, true);  // (a plan at its limit stays as it is)
         }
-        if (!st) return FLATGFA_OK;
-        FGFA_HIP_OR(hipMemsetAsync(pl->status, 0, 4, stream), return FLATGFA_ERR_HIP);
-        if (st & 1u) {
+        if (st) FGFA_HIP_OR(hipMemsetAsync(pl->status, 0, 4, stream), return FLATGFA_ERR_HIP);
+        switch (act.verdict) {
+        case StatusVerdict::fine: return FLATGFA_OK;
+        case StatusVerdict::bounds:
             set_error("a step refers to a segment id (or a query to a path id) that is out of range");
             return FLATGFA_ERR_BOUNDS;
-        }
-        if (st & 32u) {  // (kStStale: FLATGFA_CHECK_NO_CLAIM=1)
+        case StatusVerdict::stale:  // (kStStale: FLATGFA_CHECK_NO_CLAIM=1)
             set_error("the step values changed behind the plan (a path it found strictly monotone no longer is, a no-claim mark or a reversed copy no longer holds): "
                       "call flatgfa_dev_plan_steps_changed, or make the plan again");
             return FLATGFA_ERR_STALE_PLAN;
-        }
-        if (st & 8u) {  // (depth_fast.hip: kStInternal)
+        case StatusVerdict::internal: {  // (kStInternal)
             char what[512] = "";
             (void)flatgfa_dev_plan_describe(pl, what, (int)sizeof what);
             set_error("node depth: internal error (the records of pass 1 were not in the order pass 2 relies on); status words " + std::to_string(st3[0]) + " " +
                       std::to_string(st3[1]) + " " + std::to_string(st3[2]) + ", " + std::to_string(n_calls) + " call(s) since the last status; plan: " + what);
             return FLATGFA_ERR_HIP;
         }
-        if (!(st & (4u | 16u))) return FLATGFA_OK;
-        if (attempt == 0 && n_calls > 1) {
-            // Several calls were enqueued since the last status and (at least) one of them ran out of
-            // scratch room: which one is not recorded, and only the last one's outputs are known here.
+        case StatusVerdict::several_calls:
             set_error("node depth: a call ran out of scratch room (the steps changed behind the plan?) and " + std::to_string(n_calls) +
                       " calls were enqueued since the last flatgfa_dev_status: call it after every call to have such a call completed (status words " + std::to_string(st3[0]) + " " + std::to_string(st3[2]) + ")");
             return FLATGFA_ERR_HIP;
-        }
-        // The last node-depth call ran out of sub-bucket room, so its outputs are incomplete: run
-        // it again with four times the room, or -- when the plan cannot grow -- through the
-        // atomic kernels.  The scratch cleans itself in pass 2, whatever was dropped.
-        if (!pl->last_fast || !pl->last_depth || attempt > 8) {
+        case StatusVerdict::unresolved:
             set_error("node depth: scratch overflow could not be resolved");
             return FLATGFA_ERR_HIP;
+        case StatusVerdict::redo_grown:
+        case StatusVerdict::redo_atomic:
+            if (const int rc = redo_last_call(pl, act.verdict == StatusVerdict::redo_atomic, stream)) return rc;
         }
-        int rc;
-        const bool grown = !(st & 16u) && plan_grow(pl);  // (a full hand-back list is not a matter of bucket room)
-        if (st & 16u) pl->fast.eligible = false;  // (later calls take the atomic kernels right away)
-        if (!grown) pl->last_fast = false;
-        if (pl->last_len) rc = path_depth_all_enqueue(pl, pl->last_depth, pl->last_len, pl->last_weighted, stream, grown);
-        else if (grown) rc = plan_fast_call(pl, pl->last_depth, pl->last_uniq, stream);
-        else rc = atomic_seg_depth(pl, pl->last_depth, pl->last_uniq, stream);
-        if (rc) return rc;
     }
 }
 
@@ -1299,14 +1294,16 @@ extern "C" int flatgfa_dev_plan_describe(flatgfa_dev_plan_t *pl, char *out, int 
     if (!f.eligible) {
         s = "path=atomic (k_depth_scan / k_depth_uniq_path)";
     } else {
-        const bool alone = (f.n_short || f.n_medium || f.n_tiny) && f.n_items == 0 && f.exact_short;  // (k_scan's launch is left out)
-        s = "path=bucketed pass1=" + std::string(alone ? "" : f.dense ? "k_scan_dense+" : "k_scan+") + (f.n_short ? "k_scan_short+" : "") + (f.n_medium ? "k_scan_medium+" : "") + (f.n_tiny ? "k_scan_tiny+" : "");
+        // (what a seg_depth call with no hook set launches: is k_scan's launch left out; which build of it runs -- said of a plan of one range)
+        const CallShape shape = decide_call(f, {pl->g.n_segs, pl->g.seg_len != nullptr}, CallWants(), CallHooks(), false);
+        const bool two_chunks = scan_mode(f, shape).mode == kModePlainNarrow && !f.n_more;
+        s = "path=bucketed pass1=" + std::string(shape.scan_skip ? "" : f.dense ? "k_scan_dense+" : "k_scan+") + (f.n_short ? "k_scan_short+" : "") + (f.n_medium ? "k_scan_medium+" : "") + (f.n_tiny ? "k_scan_tiny+" : "");
         s.pop_back();
         s += std::string("") +
             " pass2=" + (f.tagged ? (f.n_shared ? "tagged(shared bitsets)" : f.acc_pair ? "tagged(two workgroups per window)" : "tagged") : (f.big_groups ? "directory(one-item shortcut)" : "directory")) +
             " windows=" + std::to_string(f.n_win) + "x" + std::to_string(1u << f.wb) + " ranges=" + std::to_string((f.n_more + 1) / f.n_groups) +
             (f.n_groups > 1 ? " path_groups=" + std::to_string(f.n_groups) : std::string()) +
-            (f.narrow_emit && f.tagged && !f.packed && !f.dense && !f.cflags && !f.n_more ? " emit=two_chunks" : "") +
+            (two_chunks ? " emit=two_chunks" : "") +
             " scan_workgroups=" + std::to_string(f.n_slots) + " workgroups_per_window=" + std::to_string(f.acc_parts) + " items=" + std::to_string(f.n_items) + (f.acc_own ? " bitset_owners=tracked" : "") + " no_claim_items=" + std::to_string(f.n_noclaim) + (f.n_flag_chunks ? " no_claim_chunks=" + std::to_string(f.n_flag_chunks) : std::string()) + " no_claim_paths=" + std::to_string(f.short_mono_n + f.medium_mono_n + f.tiny_mono_n) + " split_paths=" + std::to_string(f.n_shared) +
             " short_paths=" + std::to_string(f.n_short) + " medium_paths=" + std::to_string(f.n_medium) + " tiny_paths=" + std::to_string(f.n_tiny) +
             " steps=" + std::to_string(f.class_steps[0]) + "/" + std::to_string(f.class_steps[1]) + "/" + std::to_string(f.class_steps[2]) + "/" + std::to_string(f.class_steps[3]) +  // (by k_scan / short / medium / tiny)

@@ -53,6 +53,7 @@
 
 #include "depth_fast_kernels.hpp"
 #include "depth_plan_host.hpp"
+#include "depth_call_diag.hpp"
 #include "device_scan.hpp"
 #include "temp_arena.hpp"
 #include "host_copy.hpp"
@@ -1412,30 +1413,11 @@ void fast_plan_destroy(FastPlan *fp) {
     *fp = FastPlan();
 }
 
-// One range of the graph: the outputs are the range's own stretch of the result vectors.
-static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t *depth_out, uint32_t *uniq_out,
-                     uint32_t *status, hipStream_t stream, const PathSums *ps, bool count_only, RecordsUse *records) {
-    if (ps && (uniq_out || fp.wb != 12 || !g.seg_len || !fp.psum_part || fp.n_range != g.n_segs)) {
-        set_error("fast_seg_depth: path sums ride on seg_depth with 4096-segment windows only");
-        return FLATGFA_ERR_ARG;
-    }
-    const uint32_t stride = fp.n_slots * fp.cap;
-    const bool has_pre = fp.n_short || fp.n_medium || fp.n_tiny;
-    // one persistent workgroup per CU; k_scan may be handed short paths back, so it gets a full grid when there are any
-    // (and whenever the wave-per-path kernels ran: it saves their cursors for pass 2)
-    // -- unless it has no items of its own and nothing can come back (the run counts of the lists are
-    // exact): then the launch is left out, every record is one of the wave-per-path kernels', and a
-    // path that does not fit after all (steps changed behind the plan) raises kStBackOverflow.
-    const bool scan_skip = has_pre && fp.n_items == 0 && fp.exact_short && !fp.dbg && !test_hook("FLATGFA_SCAN_ALWAYS");
-    const uint32_t grid = scan_skip ? 0u : has_pre ? fp.n_slots : std::min<uint32_t>(fp.n_items, fp.n_slots);
-    ScanArgs sa;
-    sa.zero_a = sa.zero_b = nullptr;
-    sa.zero_c = sa.zero_d = nullptr;
-    sa.n_zero64 = 0;
-    sa.path_begin = sa.path_end = nullptr;
-    sa.rev_steps = nullptr;
+// Pass 1's arguments, as k_scan sees them: the wave-per-path launches take a copy with their own list in it, and who zeroes
+// what (zero_a .. zero_d) is filled in behind those.
+static ScanArgs scan_args(const FastPlan &fp, const flatgfa_dev_graph_t &g, const CallShape &s, uint32_t *status, unsigned long long *tprof) {
+    ScanArgs sa{};
     sa.n_fwd = ~0u;
-    sa.mono_lo = sa.mono_n = 0u;
     sa.steps = g.steps;
     sa.n_steps = g.n_steps;
     sa.items = reinterpret_cast<uint4 *>(fp.items);
@@ -1445,13 +1427,13 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
     sa.n_segs = fp.n_range;
     sa.seg_base = fp.seg_base;
     sa.n_total = g.n_segs;
-    sa.ranged = (fp.seg_base != 0 || fp.n_range != g.n_segs) ? 1u : 0u;
+    sa.ranged = s.ranged ? 1u : 0u;
     sa.n_win = fp.n_win;
     sa.n_slots = fp.n_slots;
     sa.wb = fp.wb;
     sa.nwp = fp.nwp;
-    sa.has_pre = has_pre ? 1u : 0u;
-    sa.max_back = scan_skip ? 0u : fp.max_back;
+    sa.has_pre = s.has_pre ? 1u : 0u;
+    sa.max_back = s.max_back;
     sa.work_counter = fp.work_counter;
     sa.counts = fp.counts;
     sa.counts0 = fp.counts0;
@@ -1461,113 +1443,144 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
     sa.perm = fp.perm;
     sa.dstride = fp.dstride;
     sa.cap = fp.cap;
-    sa.stride = stride;
-    sa.sink = fp.n_win * stride;
-    sa.big = ((uint64_t)fp.n_win + 1) * stride >= (1ull << 30) ? 1u : 0u;
+    sa.stride = fp.n_slots * fp.cap;
+    sa.sink = fp.n_win * sa.stride;
+    sa.big = s.big ? 1u : 0u;
     sa.status = status;
     sa.dbg = fp.dbg;
-    // Tagged: k_scan's records name their items, pass 2 walks whole sub-buckets.  Path sums ride on
-    // the directory walk (an item's records have to be found again once the window's depth is final).
-    const bool tagged = fp.tagged && !ps;
-    sa.tagged = tagged ? 1u : 0u;
+    sa.tagged = s.tagged ? 1u : 0u;
     sa.tag_limit = std::max(2u, fp.tag_limit);
     sa.taken = fp.taken;
     sa.mall_steps = fp.mall_steps;
-    sa.cflags = tagged ? fp.cflags : nullptr;
+    sa.cflags = s.cflags ? fp.cflags : nullptr;
     sa.pk_off = fp.pk_off;
     sa.pk_base = fp.pk_base;
-    if (fp.packed && !tagged) { set_error("fast_seg_depth: a plan with packed buckets runs tagged calls only"); return FLATGFA_ERR_ARG; }
-    sa.tprof = nullptr;
-    if (test_hook("FLATGFA_SCAN_TIME") && hipMalloc(&sa.tprof, kTprofRow * 8 * (size_t)fp.n_slots) == hipSuccess) (void)hipMemset(sa.tprof, 0, kTprofRow * 8 * (size_t)fp.n_slots);
-    AccArgs aa{fp.n_range, fp.n_win, fp.n_slots, fp.cap, fp.counts, fp.counts0, scan_skip ? 2u : has_pre ? 1u : 0u, fp.buckets,
-               reinterpret_cast<const uint2 *>(fp.dir), fp.islot, fp.dstride, fp.elist, fp.wave_off, fp.n_items,
-               fp.work_counter, scan_skip ? 0u : fp.max_back, depth_out, uniq_out, status, fp.dbg,
-               reinterpret_cast<const uint4 *>(fp.items), g.seg_len, ps ? reinterpret_cast<ulonglong2 *>(fp.psum_part) : nullptr,
-               fp.fat_off, fp.fat_woff, fp.acc_parts, tagged ? fp.n_shared : 0u, nullptr, fp.pair_part, fp.pair_flag, fp.accumulate ? 1u : 0u, test_hook("FLATGFA_NO_PLAIN") ? nullptr : fp.taken, fp.taken ? fp.taken + fp.n_slots : nullptr,
-               fp.packed ? reinterpret_cast<const uint2 *>(fp.pk) : nullptr, 0u};  // (FLATGFA_NO_PLAIN: measurements)
-#ifdef FGFA_MEASURE
-    if (const char *sk = test_hook("FLATGFA_ACC_SKIP")) aa.dbg = (uint32_t)strtoul(sk, nullptr, 10);  // (diagnostic: pass 2 without its revisit counts 128 / depth 256 / claims 64 / words behind the first 1024)
-#endif
-    const size_t tprof_words = (size_t)fp.n_win * fp.acc_parts * kAccWaves * 16;
-    if (test_hook("FLATGFA_ACC_TIME") && uniq_out && hipMalloc(&aa.tprof, tprof_words * 4) != hipSuccess) aa.tprof = nullptr;
-    // The wave-per-path kernels: the paths read from the graph's steps, then those read from their
-    // reversed copies (a handed-back one is walked by k_scan from the graph's own steps).
-    if (fp.n_short && hipMemsetAsync(fp.work_counter, 0, 4, stream) != hipSuccess) return FLATGFA_ERR_HIP;
-    if (fp.n_tiny) {  // paths a wave holds whole (at most 128 steps)
+    sa.tprof = tprof;
+    return sa;
+}
+
+// Pass 2's, in the struct's order of fields.
+static AccArgs acc_args(const FastPlan &fp, const flatgfa_dev_graph_t &g, const CallShape &s, const CallHooks &hooks, uint32_t *depth_out, uint32_t *uniq_out,
+                        uint32_t *status, bool psum, uint32_t *tprof) {
+    AccArgs aa{};
+    aa.n_segs = fp.n_range;
+    aa.n_win = fp.n_win;
+    aa.n_slots = fp.n_slots;
+    aa.cap = fp.cap;
+    aa.counts = s.kept ? fp.counts_kept : fp.counts;
+    aa.counts0 = fp.counts0;
+    aa.has_pre = s.has_pre2;
+    aa.buckets = fp.buckets;
+    aa.dir = reinterpret_cast<const uint2 *>(fp.dir);
+    aa.islot = fp.islot;
+    aa.dstride = fp.dstride;
+    aa.elist = fp.elist;
+    aa.wave_off = fp.wave_off;
+    aa.n_items = fp.n_items;
+    aa.work_counter = fp.work_counter;
+    aa.max_back = s.max_back;
+    aa.depth_out = depth_out;
+    aa.uniq_out = uniq_out;
+    aa.status = status;
+    aa.dbg = fp.dbg;
+    if (hooks.acc_skip) aa.dbg = (uint32_t)strtoul(hooks.acc_skip, nullptr, 10);  // (measurement builds: pass 2 without its revisit counts 128 / depth 256 / claims 64 / words behind the first 1024)
+    aa.items = reinterpret_cast<const uint4 *>(fp.items);
+    aa.seg_len = g.seg_len;
+    aa.psum_part = psum ? reinterpret_cast<ulonglong2 *>(fp.psum_part) : nullptr;
+    aa.fat_off = fp.fat_off;
+    aa.fat_woff = fp.fat_woff;
+    aa.parts = fp.acc_parts;
+    aa.n_shared = s.tagged ? fp.n_shared : 0u;
+    aa.tprof = tprof;
+    aa.pair_part = fp.pair_part;
+    aa.pair_flag = fp.pair_flag;
+    aa.accumulate = fp.accumulate ? 1u : 0u;
+    aa.taken = hooks.no_plain ? nullptr : fp.taken;  // (FLATGFA_NO_PLAIN: measurements)
+    aa.fullest = fp.taken ? fp.taken + fp.n_slots : nullptr;
+    aa.pk = fp.packed ? reinterpret_cast<const uint2 *>(fp.pk) : nullptr;
+    aa.keep = s.kept ? 1u : 0u;
+    return aa;
+}
+
+// The wave-per-path kernels: paths a wave holds whole (at most 128 steps), then the short and the medium ones -- of either first
+// those read from the graph's steps, then (from n_fwd on in the list) those read from their reversed copies; a handed-back
+// one is walked by k_scan from the graph's own steps.
+static void launch_wave_lists(const FastPlan &fp, const flatgfa_dev_graph_t &g, const ScanArgs &sa, const CallShape &s, bool uniq, hipStream_t stream) {
+    const struct {
+        const void *items;
+        uint32_t n, n_rev, mono_lo, mono_n, grid;
+        int kind;  // 0: k_scan_tiny, 1: k_scan_short, 2: its medium build
+        const char *name[2];
+    } lists[3] = {{fp.tiny_items, fp.n_tiny, 0u, fp.tiny_mono_lo, fp.tiny_mono_n, s.grid_tiny, 0, {"k_scan_tiny<depth>", "k_scan_tiny<uniq>"}},
+                  {fp.short_items, fp.n_short, fp.n_short_rev, fp.short_mono_lo, fp.short_mono_n, s.grid_short, 1, {"k_scan_short<depth>", "k_scan_short<uniq>"}},
+                  {fp.medium_items, fp.n_medium, fp.n_medium_rev, fp.medium_mono_lo, fp.medium_mono_n, s.grid_medium, 2, {"k_scan_medium<depth>", "k_scan_medium<uniq>"}}};
+    for (const auto &l : lists) {
+        if (!l.n) continue;
         ScanArgs sk = sa;
-        sk.short_items = reinterpret_cast<const uint4 *>(fp.tiny_items);
-        sk.n_short = fp.n_tiny;
-        sk.mono_lo = fp.tiny_mono_lo;
-        sk.mono_n = fp.tiny_mono_n;
-        const uint32_t kgrid = std::min<uint32_t>((fp.n_tiny + kWaves - 1) / kWaves, fp.n_slots);
-        ProfScope pscope(uniq_out ? "k_scan_tiny<uniq>" : "k_scan_tiny<depth>", stream);
-        launch_scan_tiny(fp, sk, uniq_out != nullptr, kgrid, stream);
-    }
-    for (int medium = 0; medium < 2; ++medium) {
-        const uint32_t n_all = medium ? fp.n_medium : fp.n_short, n_rev = medium ? fp.n_medium_rev : fp.n_short_rev;
-        const uint4 *list = reinterpret_cast<const uint4 *>(medium ? fp.medium_items : fp.short_items);
-        {
-            const uint32_t n = n_all;
-            if (!n) continue;
-            ScanArgs sk = sa;
-            sk.short_items = list;
-            sk.n_short = n;
-            sk.n_fwd = n_all - n_rev;  // (the reversed ones lie behind the others in the list)
-            sk.mono_lo = medium ? fp.medium_mono_lo : fp.short_mono_lo;
-            sk.mono_n = medium ? fp.medium_mono_n : fp.short_mono_n;
+        sk.short_items = reinterpret_cast<const uint4 *>(l.items);
+        sk.n_short = l.n;
+        sk.mono_lo = l.mono_lo;
+        sk.mono_n = l.mono_n;
+        if (l.kind) {
+            sk.n_fwd = l.n - l.n_rev;  // (the reversed ones lie behind the others in the list)
             sk.rev_steps = fp.rev_steps;
             sk.path_begin = g.path_begin;
             sk.path_end = g.path_end;
-            const uint32_t per_wg = medium ? (kMediumPaired ? kMediumWaves / 2 : kMediumWaves) : kShortWaves;  // paths a workgroup walks at a time
-            const uint32_t kgrid = std::min<uint32_t>((n + per_wg - 1) / per_wg, fp.n_slots);
-            ProfScope pscope(medium ? (uniq_out ? "k_scan_medium<uniq>" : "k_scan_medium<depth>") : (uniq_out ? "k_scan_short<uniq>" : "k_scan_short<depth>"), stream);
-            launch_scan_short(fp, sk, medium != 0, uniq_out != nullptr, kgrid, stream);
         }
+        ProfScope pscope(l.name[uniq], stream);
+        if (l.kind) launch_scan_short(fp, sk, l.kind == 2, uniq, l.grid, stream);
+        else launch_scan_tiny(fp, sk, uniq, l.grid, stream);
     }
-    if (ps && ps->clear) {  // the sums k_path_reduce adds to start at zero: k_scan's first act, or two memsets when it does not run
-        if (grid) {
-            sa.zero_c = (unsigned long long *)ps->len_out;
-            sa.zero_d = (unsigned long long *)ps->weighted_out;
-            sa.n_zero64 = g.n_paths;
-        } else {
-            ProfScope pscope("memset_path_sums", stream);
-            if (hipMemsetAsync(ps->len_out, 0, (size_t)g.n_paths * 8, stream) != hipSuccess) return FLATGFA_ERR_HIP;
-            if (hipMemsetAsync(ps->weighted_out, 0, (size_t)g.n_paths * 8, stream) != hipSuccess) return FLATGFA_ERR_HIP;
-        }
+}
+
+// One range of the graph: the outputs are the range's own stretch of the result vectors.
+static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t *depth_out, uint32_t *uniq_out,
+                     uint32_t *status, hipStream_t stream, const PathSums *ps, bool count_only, RecordsUse *records) {
+    CallHooks hooks;
+    hooks.scan_always = test_hook("FLATGFA_SCAN_ALWAYS") != nullptr;
+    hooks.scan_time = test_hook("FLATGFA_SCAN_TIME");
+    hooks.no_plain = test_hook("FLATGFA_NO_PLAIN") != nullptr;
+    hooks.acc_time = test_hook("FLATGFA_ACC_TIME") != nullptr;
+#ifdef FGFA_MEASURE  // (a switch that makes the results wrong by construction exists in measurement builds only)
+    hooks.acc_skip = test_hook("FLATGFA_ACC_SKIP");
+#endif
+    const bool uniq = uniq_out != nullptr;
+    const CallShape s = decide_call(fp, {g.n_segs, g.seg_len != nullptr}, {uniq, ps != nullptr, ps && ps->clear, count_only}, hooks, records && records->use);
+    if (s.refusal) { set_error(s.refusal); return FLATGFA_ERR_ARG; }
+    if (records) records->from_image = s.from_image && fp.counts_kept;
+    const ScanTimeDiag scan_time(hooks.scan_time, fp.n_slots);
+    const AccTimeDiag acc_time(hooks.acc_time && uniq, (size_t)fp.n_win * fp.acc_parts * kAccWaves * 16);
+    ScanArgs sa = scan_args(fp, g, s, status, scan_time.buf);
+    AccArgs aa = acc_args(fp, g, s, hooks, depth_out, uniq_out, status, ps != nullptr, acc_time.buf);
+    if (fp.n_short && hipMemsetAsync(fp.work_counter, 0, 4, stream) != hipSuccess) return FLATGFA_ERR_HIP;
+    launch_wave_lists(fp, g, sa, s, uniq, stream);
+    // What pass 2 (several workgroups per window) and k_path_reduce add to starts at zero: k_scan's first act, or memsets where it does not run.
+    if (s.sums == Zeroes::k_scan) {
+        sa.zero_c = (unsigned long long *)ps->len_out;
+        sa.zero_d = (unsigned long long *)ps->weighted_out;
+        sa.n_zero64 = g.n_paths;
+    } else if (s.sums == Zeroes::memset) {
+        ProfScope pscope("memset_path_sums", stream);
+        if (hipMemsetAsync(ps->len_out, 0, (size_t)g.n_paths * 8, stream) != hipSuccess) return FLATGFA_ERR_HIP;
+        if (hipMemsetAsync(ps->weighted_out, 0, (size_t)g.n_paths * 8, stream) != hipSuccess) return FLATGFA_ERR_HIP;
     }
-    // (a tagged call of a plan with the steps' run-length image installed reads that: no plan that is given one has dense
-    // pass 1, packed buckets, ranges, marks or wave-per-path lists)
-    const bool from_image = grid && tagged && fp.run_ent && fp.run_item_ent && !count_only && !fp.dense && !fp.packed && !sa.ranged && !sa.cflags && !has_pre && !fp.dbg;
-    // ... and where the records of the image call before this one are still in the scratch (RecordsUse: the handle knows), it
-    // would write the same records into the same slots: pass 1 is left out, pass 2 reads the kept cursors and leaves them.
-    const bool kept = from_image && records && records->use && fp.counts_kept;
-    if (records) records->from_image = from_image && fp.counts_kept;
-    if (kept) {
-        aa.counts = fp.counts_kept;
-        aa.keep = 1u;
-    }
-    if (grid && !kept) {
-        if (fp.acc_parts > 1 && !fp.accumulate && !count_only) {  // (a later group of paths adds to what is there)
-            sa.zero_a = depth_out;
-            sa.zero_b = uniq_out;
-        }
-        ProfScope pscope(from_image ? "k_scan_runs" : fp.dense ? "k_scan_dense" : "k_scan", stream);
-        if (from_image) {
-            launch_scan_runs(fp, sa, grid, stream);
-        } else {
-            const int rc = launch_scan(fp, sa, tagged, grid, stream);
-            if (rc != FLATGFA_OK) return rc;
-        }
-    }
-    if (count_only) return hipGetLastError() == hipSuccess ? FLATGFA_OK : FLATGFA_ERR_HIP;  // (the counting call of a packed plan: pass 1 alone)
-    if (fp.acc_parts > 1 && (!grid || kept) && !fp.accumulate) {  // the window's workgroups add to the outputs: cleared by k_scan, or here when it does not run
+    if (s.outputs == Zeroes::k_scan) {
+        sa.zero_a = depth_out;
+        sa.zero_b = uniq_out;
+    } else if (s.outputs == Zeroes::memset) {
         ProfScope pscope("memset_outputs", stream);
         if (hipMemsetAsync(depth_out, 0, (size_t)fp.n_range * 4, stream) != hipSuccess) return FLATGFA_ERR_HIP;
         if (uniq_out && hipMemsetAsync(uniq_out, 0, (size_t)fp.n_range * 4, stream) != hipSuccess) return FLATGFA_ERR_HIP;
     }
+    if (s.scans()) {  // pass 1 for the items
+        ProfScope pscope(s.from_image ? "k_scan_runs" : fp.dense ? "k_scan_dense" : "k_scan", stream);
+        if (s.from_image) launch_scan_runs(fp, sa, s.grid, stream);
+        else if (const int rc = launch_scan(fp, sa, scan_mode(fp, s), s.grid, stream)) return rc;
+    }
+    if (count_only) return hipGetLastError() == hipSuccess ? FLATGFA_OK : FLATGFA_ERR_HIP;  // (the counting call of a packed plan: pass 1 alone)
     {
-        ProfScope pscope(uniq_out ? "k_accum<uniq>" : (ps ? "k_accum<depth+paths>" : "k_accum<depth>"), stream);
-        launch_accum(fp, aa, uniq_out != nullptr, tagged, ps != nullptr, stream);
+        ProfScope pscope(uniq ? "k_accum<uniq>" : (ps ? "k_accum<depth+paths>" : "k_accum<depth>"), stream);
+        launch_accum(fp, aa, uniq, s.tagged, ps != nullptr, stream);
     }
     if (ps && fp.n_items) {
         ProfScope pscope("k_path_reduce", stream);
@@ -1577,68 +1590,9 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
         set_error("fast_seg_depth: kernel launch failed");
         return FLATGFA_ERR_HIP;
     }
-    if (sa.tprof) {  // diagnostic: when the workgroups of k_scan start, when their first wave runs out of work, when they end
-        constexpr size_t kRow = kTprofRow;
-        std::vector<unsigned long long> raw(kRow * (size_t)fp.n_slots);
-        (void)hipStreamSynchronize(stream);
-        (void)staged_copy(raw.data(), sa.tprof, raw.size() * 8, hipMemcpyDeviceToHost, nullptr);
-        (void)hipFree(sa.tprof);
-        unsigned long long t0 = ~0ull;
-        for (uint32_t i = 0; i < grid; ++i) t0 = std::min(t0, raw[kRow * i]);
-        std::vector<double> st, fw, lw, en;
-        for (uint32_t i = 0; i < grid; ++i) {
-            st.push_back((raw[kRow * i] - t0) / 100.0);
-            en.push_back((raw[kRow * i + 1] - t0) / 100.0);
-            unsigned long long a = ~0ull, b = 0;
-            for (size_t k = 0; k < kWaves; ++k) {
-                a = std::min(a, raw[kRow * i + 4 + k]);
-                b = std::max(b, raw[kRow * i + 4 + k]);
-            }
-            fw.push_back((a - t0) / 100.0);
-            lw.push_back((b - t0) / 100.0);
-        }
-        const auto pct = [](std::vector<double> v, double q) { std::sort(v.begin(), v.end()); return v[(size_t)(q * (v.size() - 1))]; };
-        fprintf(stderr, "k_scan%s workgroups (us since the first one started): start p50 %.1f max %.1f | first wave out of work p5 %.1f p50 %.1f p95 %.1f | last wave p5 %.1f p50 %.1f p95 %.1f max %.1f | end p50 %.1f max %.1f\n",
-                tagged ? " [tagged]" : "", pct(st, 0.5), pct(st, 1.0), pct(fw, 0.05), pct(fw, 0.5), pct(fw, 0.95), pct(lw, 0.05), pct(lw, 0.5), pct(lw, 0.95), pct(lw, 1.0), pct(en, 0.5), pct(en, 1.0));
-        // FLATGFA_SCAN_TIME=<file>: one line per workgroup and call -- call, workgroup, XCC, HW_ID, items, start, first / last wave out of work, end (us)
-        static int call_no = 0;
-        const char *where = test_hook("FLATGFA_SCAN_TIME");
-        if (where && strchr(where, '/')) {
-            if (FILE *f = fopen(where, "a")) {
-                for (uint32_t i = 0; i < grid; ++i)
-                    fprintf(f, "%d,%u,%u,0x%08x,%u,%.2f,%.2f,%.2f,%.2f\n", call_no, i, (unsigned)(raw[kRow * i + 2] >> 32) & 15u, (unsigned)raw[kRow * i + 2],
-                            (unsigned)raw[kRow * i + 3], st[i], fw[i], lw[i], en[i]);
-                fclose(f);
-            }
-        }
-        call_no += 1;
-    }
-    if (aa.tprof) {  // diagnostic: where the waves of pass 2 spend their time
-        std::vector<uint32_t> raw(tprof_words);
-        (void)hipStreamSynchronize(stream);
-        (void)staged_copy(raw.data(), aa.tprof, tprof_words * 4, hipMemcpyDeviceToHost, nullptr);
-        (void)hipFree(aa.tprof);
-        const size_t waves = tprof_words / 16;
-        double sum[16] = {}, mx[16] = {};
-        for (size_t w = 0; w < waves; ++w)
-            for (int k = 0; k < 16; ++k) {
-                sum[k] += raw[w * 16 + k];
-                mx[k] = std::max<double>(mx[k], raw[w * 16 + k]);
-            }
-        static const char *names[5] = {"setup", "flat", "walk", "barrier", "scan+store"};
-        fprintf(stderr, "k_accum%s per wave, us avg (max):", tagged ? " [tagged]" : "");
-        for (int k = 0; k < 5; ++k) fprintf(stderr, "  %s %.2f (%.2f)", names[k], sum[k] / waves / 100.0, mx[k] / 100.0);
-        fprintf(stderr, "  | per wave avg (max): steps %.1f (%.0f) rounds %.1f flushes %.1f (%.0f)\n", sum[8] / waves, mx[8], sum[9] / waves, sum[10] / waves, mx[10]);
-    }
-    if (fp.dbg & kDbgTime) {  // diagnostic: where the waves of k_scan spend their cycles
-        unsigned long long acc[8] = {};
-        (void)hipStreamSynchronize(stream);
-        (void)staged_copy(acc, status + 8, sizeof acc, hipMemcpyDeviceToHost, nullptr);
-        (void)hipMemset(status + 8, 0, sizeof acc);
-        const double waves = (double)grid * kWaves;
-        fprintf(stderr, "k_scan cycles per wave: wait_block %.0f  epoch_wait %.0f  passA+B %.0f  drain %.0f  other %.0f  item switch %.0f\n",
-                acc[0] / waves, acc[1] / waves, acc[2] / waves, acc[3] / waves, acc[4] / waves, acc[5] / waves);
-    }
+    scan_time.report(s.grid, s.tagged, stream);
+    acc_time.report(s.tagged, stream);
+    if (fp.dbg & kDbgTime) report_scan_cycles(status, s.grid, stream);
     return FLATGFA_OK;
 }
 

@@ -32,7 +32,30 @@ int device_cu_count(int device);
 // FLATGFA_TIMING=1: prints what the calling thread spent since its last tick (the device drained first), to stderr; `what` == nullptr restarts the clock
 void plan_tick(const char *what);
 
-// ---- what the plan decides by (depth_plan_host.hpp); the kernels' own constants are in depth_fast_kernels.hpp ----
+// ---- what the plan and a call decide by (depth_plan_host.hpp, depth_call_host.hpp); the kernels' own constants are in depth_fast_kernels.hpp ----
+constexpr int kThreads = 1024;
+constexpr int kWaves = kThreads / 64;
+// status word bits (flatgfa_dev_status)
+constexpr uint32_t kStBounds = 1u, kStDebug = 2u, kStOverflow = 4u, kStInternal = 8u, kStBackOverflow = 16u, kStStale = 32u;  // (32: FLATGFA_CHECK_NO_CLAIM=1 found the step values changed behind the plan)  // (16: more short paths handed back than the list holds: larger buckets would not help, the atomic kernels complete the call)  // (8: an invariant between the two passes did not hold -- a bug, reported as an error rather than as counts)
+// The medium-path variant of k_scan_short: hash sets of 2048 entries, for paths whose run count (known to the plan) fits
+// one -- seven sets and fourteen waves per workgroup, two waves per path (eight and eight, one wave per
+// path, when built with -DFGFA_MEDIUM_PAIRED=0).
+#ifndef FGFA_MEDIUM_PAIRED
+#define FGFA_MEDIUM_PAIRED 1
+#endif
+constexpr bool kMediumPaired = FGFA_MEDIUM_PAIRED != 0;  // two waves per path and hash set (k_scan_short<..., PAIRED>)
+constexpr int kMediumHash = 11, kMediumWaves = kMediumPaired ? 14 : 8;
+#ifndef FGFA_SHORT_WAVES
+#define FGFA_SHORT_WAVES 16
+#endif
+constexpr int kShortWaves = FGFA_SHORT_WAVES;  // waves of a k_scan_short workgroup (measurements: fewer = lower occupancy)
+// k_scan's builds: plain, diagnostic (FLATGFA_DEBUG_SKIP), ranged (one of several walks of a graph beyond 16 M segments)
+constexpr int kModePlain = 0, kModeDbg = 1, kModeRanged = 2, kModeBig = 3, kModeRangedBig = 4, kModePacked = 5, kModePackedRanged = 6, kModePlainFlags = 7, kModePackedFlags = 8, kModePlainNarrow = 9;  // (...Flags: the plain and the packed build for plans with per-block no-claim flags, ScanArgs::cflags)  // (Big: builds of their own for bucket arrays of 2^30 records or more, see put(); Packed: sub-buckets of exactly the size their records need, items dealt in a fixed order)
+constexpr bool mode_ranged(int m) { return m == kModeRanged || m == kModeRangedBig || m == kModePackedRanged; }
+constexpr bool mode_big(int m) { return m == kModeBig || m == kModeRangedBig; }
+constexpr bool mode_packed(int m) { return m == kModePacked || m == kModePackedRanged || m == kModePackedFlags; }
+constexpr bool mode_flags(int m) { return m == kModePlainFlags || m == kModePackedFlags; }
+constexpr bool mode_plain(int m) { return m == kModePlain || m == kModePlainNarrow; }
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 constexpr uint32_t kAccWaves = 16;         // waves of a pass-2 workgroup
 constexpr uint32_t kShortMax = 2048;       // steps; longer paths go through k_scan (or the medium variant)
@@ -250,9 +273,11 @@ struct PathSums {
 };
 // Allocates (once) the scratch `ps` needs; false = not possible for this plan.
 bool fast_plan_want_path_sums(FastPlan *fp);
-// Enqueues the kernels.  uniq_out may be NULL (seg_depth); `ps` only with uniq_out == NULL and
+// Enqueues the kernels, one range after the other.  uniq_out may be NULL (seg_depth); `ps` only with uniq_out == NULL and
 // after fast_plan_want_path_sums.  `records`: see RecordsUse; nullptr = pass 1 runs, and the caller must take its
-// scratch for overwritten.
+// scratch for overwritten.  What a call is made of is decided first (depth_call_host.hpp: decide_call -- which launches, how
+// large, who zeroes what, which build of k_scan); a call it refuses (FLATGFA_ERR_ARG: path sums outside their precondition, a
+// packed plan or a bucket array of 2^30 records called untagged) has enqueued nothing for the range that refused it.
 int fast_seg_depth(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t *depth_out, uint32_t *uniq_out,
                    uint32_t *status, hipStream_t stream, const PathSums *ps = nullptr, RecordsUse *records = nullptr);
 

@@ -5,7 +5,8 @@
 //   depth_scan_paths.hip  pass 1 for short paths: k_scan_short / k_scan_medium / k_scan_tiny (a wave per path)
 //   depth_accum.hip       pass 2: k_accum, k_path_reduce
 //   depth_fast.hip        the plan (which kernel walks which path, the scratch) and the launches; what it decides on
-//                         the host is in depth_plan_host.hpp, the constants it decides by in depth_fast.hpp
+//                         the host is in depth_plan_host.hpp (a plan) and depth_call_host.hpp (a call), the constants it
+//                         decides by in depth_fast.hpp
 // DESIGN.md section 3 is the long version.  Constants, inline device functions and plain structs only (the same in every
 // translation unit that includes it).
 #pragma once
@@ -13,20 +14,17 @@
 
 #include <cstdint>
 
+#include "depth_call_host.hpp"
 #include "depth_fast.hpp"
 #include "device_common.hpp"
 
 namespace fgfa_dev {
 
 
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / 64;
 constexpr uint32_t kMaxSlots = 1024;  // sub-buckets per window (= workgroups of pass 1) k_accum can stage
 constexpr int kAccThreads = 1024;
 static_assert(kAccThreads == 64 * (int)kAccWaves, "pass 2's workgroup is the waves the plan deals to");
 constexpr uint32_t kLdsLimit = 160 * 1024;
-// status word bits (flatgfa_dev_status)
-constexpr uint32_t kStBounds = 1u, kStDebug = 2u, kStOverflow = 4u, kStInternal = 8u, kStBackOverflow = 16u, kStStale = 32u;  // (32: FLATGFA_CHECK_NO_CLAIM=1 found the step values changed behind the plan)  // (16: more short paths handed back than the list holds: larger buckets would not help, the atomic kernels complete the call)  // (8: an invariant between the two passes did not hold -- a bug, reported as an error rather than as counts)
 
 // ---- the wave-per-path kernels (k_scan_short): windows of 4096 segments, at most 256 of them ----
 constexpr uint32_t kRunBits = 11;  // a run of a depth-only call is cut at multiples of 2^11 ids (it then never crosses a window's end)
@@ -43,19 +41,7 @@ constexpr uint32_t kShortMaxWin = 256;     // LDS cursor table entries of k_scan
 constexpr uint32_t kShortMaxSegs = 1u << 20;
 constexpr uint32_t kDummyBase = 1u << 20;  // ids from here up stand in for steps outside the path (never emitted)
 constexpr int kShortHash = 9;              // per-wave hash set of 512 (bitset word index + 1, bits) pairs
-// The medium-path variant: hash sets of 2048 entries, for paths whose run count (known to the plan) fits
-// one -- seven sets and fourteen waves per workgroup, two waves per path (eight and eight, one wave per
-// path, when built with -DFGFA_MEDIUM_PAIRED=0).
-#ifndef FGFA_MEDIUM_PAIRED
-#define FGFA_MEDIUM_PAIRED 1
-#endif
-constexpr bool kMediumPaired = FGFA_MEDIUM_PAIRED != 0;  // two waves per path and hash set (k_scan_short<..., PAIRED>)
-constexpr int kMediumHash = 11, kMediumWaves = kMediumPaired ? 14 : 8;
 constexpr uint32_t kQPaired = 328;  // a paired wave's run queue: 64 left over + up to 256 from sixteen lanes + the entry that closes a block
-#ifndef FGFA_SHORT_WAVES
-#define FGFA_SHORT_WAVES 16
-#endif
-constexpr int kShortWaves = FGFA_SHORT_WAVES;  // waves of a k_scan_short workgroup (measurements: fewer = lower occupancy)
 
 // ---- tagged records ----
 // A record of k_scan is (window-relative first segment) | (length - 1) << wb.  In a *tagged* call it
@@ -389,13 +375,6 @@ __device__ __forceinline__ uint32_t take_slots(uint32_t *bcur, int lane, bool va
 // LDS control words of k_scan, behind the two cursor tables: the next block of the current /
 // next item nobody has taken yet (two cells, by item parity), how many waves have left the item
 // (two cells), and how many items are complete.
-// k_scan's builds: plain, diagnostic (FLATGFA_DEBUG_SKIP), ranged (one of several walks of a graph beyond 16 M segments)
-constexpr int kModePlain = 0, kModeDbg = 1, kModeRanged = 2, kModeBig = 3, kModeRangedBig = 4, kModePacked = 5, kModePackedRanged = 6, kModePlainFlags = 7, kModePackedFlags = 8, kModePlainNarrow = 9;  // (...Flags: the plain and the packed build for plans with per-block no-claim flags, ScanArgs::cflags)  // (Big: builds of their own for bucket arrays of 2^30 records or more, see put(); Packed: sub-buckets of exactly the size their records need, items dealt in a fixed order)
-constexpr bool mode_ranged(int m) { return m == kModeRanged || m == kModeRangedBig || m == kModePackedRanged; }
-constexpr bool mode_big(int m) { return m == kModeBig || m == kModeRangedBig; }
-constexpr bool mode_packed(int m) { return m == kModePacked || m == kModePackedRanged || m == kModePackedFlags; }
-constexpr bool mode_flags(int m) { return m == kModePlainFlags || m == kModePackedFlags; }
-constexpr bool mode_plain(int m) { return m == kModePlain || m == kModePlainNarrow; }
 // A wave's run queue.  A packed call keeps two LDS tables for up to 4096 windows (cursors and the sub-buckets'
 // offsets), which leaves its queues 88 entries less: a block of (nearly) all starts is then queued behind a
 // drain down to one entry, and one of more than 1005 starts -- ids without any run at all, which such a plan is
@@ -516,8 +495,8 @@ inline uint32_t dense_lds_bytes(uint32_t nwp) { return (6u * nwp + 64u + kDenseT
 bool scan_kernels_setup();        // depth_scan.hip
 bool path_kernels_setup();        // depth_scan_paths.hip
 bool accum_kernels_setup();       // depth_accum.hip
-// pass 1 over the plan's long items: k_scan in the build the plan needs (tagged / ranged / packed / big), or k_scan_dense
-int launch_scan(const FastPlan &fp, const ScanArgs &sa, bool tagged, uint32_t grid, hipStream_t stream);
+// pass 1 over the plan's long items: k_scan in the build scan_mode names (tagged / ranged / packed / big), or k_scan_dense
+int launch_scan(const FastPlan &fp, const ScanArgs &sa, ScanMode mode, uint32_t grid, hipStream_t stream);
 // pass 1 of a tagged call from the plan's run-length image (FastPlan::run_ent): k_scan_runs
 void launch_scan_runs(const FastPlan &fp, const ScanArgs &sa, uint32_t grid, hipStream_t stream);
 // the wave-per-path kernels: paths a wave holds whole (k_scan_tiny), short and medium ones (k_scan_short's two builds)

@@ -937,25 +937,25 @@ bool scan_kernels_setup() {
     return ok;
 }
 
-int launch_scan(const FastPlan &fp, const ScanArgs &sa, bool tagged, uint32_t grid, hipStream_t stream) {
-    const dim3 g(grid), b(kThreads);
-    const uint32_t lds = fp.lds_bytes_scan;
-    if (fp.dense) hipLaunchKernelGGL(k_scan_dense, g, b, dense_lds_bytes(fp.nwp), stream, sa);
+int launch_scan(const FastPlan &fp, const ScanArgs &sa, ScanMode m, uint32_t grid, hipStream_t stream) {
+#define FGFA_SCAN(MODE, TAGGED) hipLaunchKernelGGL((k_scan<MODE, TAGGED>), dim3(grid), dim3(kThreads), fp.lds_bytes_scan, stream, sa)
+    switch (m.mode) {  // (scan_mode: depth_call_host.hpp)
+    case kModeDense: hipLaunchKernelGGL(k_scan_dense, dim3(grid), dim3(kThreads), dense_lds_bytes(fp.nwp), stream, sa); break;
 #ifdef FGFA_MEASURE
-    else if (fp.dbg) hipLaunchKernelGGL((k_scan<kModeDbg, false>), g, b, lds, stream, sa);
+    case kModeDbg: FGFA_SCAN(kModeDbg, false); break;
 #endif
-    else if (sa.cflags && tagged && !sa.ranged && fp.packed) hipLaunchKernelGGL((k_scan<kModePackedFlags, true>), g, b, lds, stream, sa);  // (a packed call's offsets are its region's: `big` is not its business)
-    else if (sa.cflags && tagged && !sa.ranged && !sa.big && !fp.packed) hipLaunchKernelGGL((k_scan<kModePlainFlags, true>), g, b, lds, stream, sa);
-    else if (fp.packed && sa.ranged) hipLaunchKernelGGL((k_scan<kModePackedRanged, true>), g, b, lds, stream, sa);
-    else if (fp.packed) hipLaunchKernelGGL((k_scan<kModePacked, true>), g, b, lds, stream, sa);
-    else if (sa.big && !tagged) { set_error("fast_seg_depth: a bucket array this large needs a tagged call"); return FLATGFA_ERR_ARG; }
-    else if (sa.big && sa.ranged) hipLaunchKernelGGL((k_scan<kModeRangedBig, true>), g, b, lds, stream, sa);
-    else if (sa.big) hipLaunchKernelGGL((k_scan<kModeBig, true>), g, b, lds, stream, sa);
-    else if (sa.ranged && tagged) hipLaunchKernelGGL((k_scan<kModeRanged, true>), g, b, lds, stream, sa);
-    else if (sa.ranged) hipLaunchKernelGGL((k_scan<kModeRanged, false>), g, b, lds, stream, sa);
-    else if (tagged && fp.narrow_emit) hipLaunchKernelGGL((k_scan<kModePlainNarrow, true>), g, b, lds, stream, sa);
-    else if (tagged) hipLaunchKernelGGL((k_scan<kModePlain, true>), g, b, lds, stream, sa);
-    else hipLaunchKernelGGL((k_scan<kModePlain, false>), g, b, lds, stream, sa);
+    case kModePackedFlags: FGFA_SCAN(kModePackedFlags, true); break;
+    case kModePlainFlags: FGFA_SCAN(kModePlainFlags, true); break;
+    case kModePackedRanged: FGFA_SCAN(kModePackedRanged, true); break;
+    case kModePacked: FGFA_SCAN(kModePacked, true); break;
+    case kModeRangedBig: FGFA_SCAN(kModeRangedBig, true); break;
+    case kModeBig: FGFA_SCAN(kModeBig, true); break;
+    case kModeRanged: if (m.tagged) FGFA_SCAN(kModeRanged, true); else FGFA_SCAN(kModeRanged, false); break;
+    case kModePlainNarrow: FGFA_SCAN(kModePlainNarrow, true); break;
+    case kModePlain: if (m.tagged) FGFA_SCAN(kModePlain, true); else FGFA_SCAN(kModePlain, false); break;
+    default: set_error("fast_seg_depth: no build of k_scan takes this call"); return FLATGFA_ERR_ARG;  // (decide_call refuses such a call)
+    }
+#undef FGFA_SCAN
     return FLATGFA_OK;
 }
 
