@@ -293,6 +293,28 @@ int flatgfa_inject_bed(flatgfa_t gfa, const char *bed, size_t bed_len, int links
  * read.  A segment span that leaves seq_data: FLATGFA_ERR_BOUNDS, before any device work; more than 2^32 - 1 kept bytes:
  * FLATGFA_ERR_TOO_LARGE, found before any output is allocated. */
 int flatgfa_crush(flatgfa_t gfa, flatgfa_t *out);
+/* flip (slow_odgi/flip.py, `odgi flip`; `fgfa flip`): a path whose backward steps cover more bases than its forward steps
+ * (64-bit sums of Segment::len(); strictly more: a tie, an empty path or a path of empty segments stays) is turned around --
+ * its steps in reverse order, each orientation toggled -- and gets `_inv` appended to its name; for every consecutive pair
+ * (a, b) of a turned path's new steps the link a -> b with the overlap 0M joins the links, behind the old ones, in path order
+ * then step order; then the links are de-duplicated: two links are one when their overlaps are equal op for op and they have
+ * the same (from, to) or one is the other's reverse complement (flip(to), flip(from)), and the first of each class stays, in
+ * that order -- among the old links too, and whether or not any path turns.  *out is a new heap handle that owns its pools and
+ * outlives `gfa`: the steps are the paths one behind another in path order, whatever the input spans were (they may be out of
+ * order, overlap or leave gaps); name_data is the paths' names one behind another; kept old links keep their overlap spans,
+ * and the new ones share one 0M op appended to the alignment pool (appended only when a new link is kept); paths lose their
+ * overlaps and segments their optional fields; header, segments and seq_data are copies of the input's; overlaps,
+ * optional_data and line_order are empty (the text comes out in normalized order), as flatgfa_crush leaves them.  Every path
+ * is kept, also where several share a name (the reference keys paths by name and keeps one).  The weighing, the rewrite, the
+ * grouping of the links by canonical key, the decisions and the compaction run on the GPU (the device `gfa` is resident on,
+ * else device 0), on the steps the handle keeps there when it has them; `gfa` is only read.  A step or link that names a
+ * segment >= the segment count, a path span that leaves the steps, a segment span that leaves seq_data, a link whose overlap
+ * span leaves the alignment pool: FLATGFA_ERR_BOUNDS; more links and steps together than 2^32 - 2 (every step may add a link,
+ * and the ordinals are 32 bits wide), more than 2^32 - 1 bytes of names, or -- where links and steps together are more than
+ * 2^27 -- more than 2^26 links and step pairs on one handle: FLATGFA_ERR_TOO_LARGE; all before any output exists.  flatgfa_flip_count is the count alone: how many paths would turn and how many links the output would have (either
+ * pointer may be NULL). */
+int flatgfa_flip(flatgfa_t gfa, flatgfa_t *out);
+int flatgfa_flip_count(flatgfa_t gfa, uint64_t *n_turned, uint64_t *n_links_out);
 /* extract (flatgfa/src/ops/extract.rs; `fgfa extract -n NAME -c DIST [-d N] [-e N]`, cli/cmds.rs:174-215): the subgraph
  * around one segment.  flatgfa_find_seg is FlatGFA::find_seg (flatgfa.rs:380-384): the id of the first segment with that
  * name, or -1.  The new graph holds the old header; the origin as segment 0 and every segment within link_distance links
@@ -723,6 +745,30 @@ int flatgfa_dev_crush_count(const uint32_t *seg_seq, const uint8_t *seq_data, ui
                             void *stream, flatgfa_dev_crush_t **job, uint64_t *bytes_out, uint64_t *dropped_out);
 int flatgfa_dev_crush_fill(flatgfa_dev_crush_t *job, uint8_t *seq_out, uint32_t *seg_seq_out, void *stream);
 void flatgfa_dev_crush_free(flatgfa_dev_crush_t *job);
+/* flip (flatgfa_flip) of a graph image in device memory, in two stream-ordered calls modelled on the crush pair.  Path p walks
+ * steps[path_begin[p] .. path_begin[p] + n_p) of steps u32[n_steps], n_p = path_start[p + 1] - path_start[p]: path_start
+ * u32[n_paths + 1] numbers the steps of all paths one behind another, from 0 to n_lin, while the spans themselves may be out
+ * of order, overlap or leave gaps.  seg_len u32[n_segs]; links u32[4 * n_links] are the Link records (from, to,
+ * overlap.start, overlap.end) and alignment u32[n_align] the pool their overlaps point into.  Empty pools may be NULL.
+ * flatgfa_dev_flip_count checks ids and spans, weighs the paths, forms and de-duplicates the links, waits for `stream` once
+ * to read the totals -- *n_turned turned paths, *links_out links kept, *links_new of them new -- and returns a job in *job;
+ * an id or span out of range: FLATGFA_ERR_BOUNDS, n_links + n_lin > 2^32 - 2: FLATGFA_ERR_TOO_LARGE, both with no job.
+ * round_keys is 0 (2^26) or, for tests and measurements, how many keys of the link table a round takes: where n_links + n_lin
+ * is more than two rounds' keys, the table is grouped and decided a round at a time in scratch for two rounds' keys -- the
+ * answer is the same -- and more links and step pairs on one handle than a round holds are FLATGFA_ERR_TOO_LARGE.
+ * flatgfa_dev_flip_fill enqueues on `stream` the new steps into steps_out u32[n_lin] (path p at [path_start[p],
+ * path_start[p + 1]): with path_start as begins and ends it is a flatgfa_dev_graph_t's image), the flags into turned_out
+ * u32[n_paths] (0 or 1) and the kept Link records into links_out u32[4 * *links_out] -- the old ones first, with their
+ * spans; a new one's overlap is [n_align, n_align + 1), the 0M op (the word 0) that the caller appends to its alignment pool
+ * when *links_new is not 0 -- and does not wait.  The inputs must stay as they are until the fill is done.
+ * flatgfa_dev_flip_free waits for the job's stream and releases its scratch. */
+typedef struct flatgfa_dev_flip flatgfa_dev_flip_t;
+int flatgfa_dev_flip_count(const uint32_t *steps, uint64_t n_steps, const uint32_t *path_start, const uint32_t *path_begin, uint32_t n_paths,
+                           uint64_t n_lin, const uint32_t *seg_len, uint32_t n_segs, const uint32_t *links, uint64_t n_links,
+                           const uint32_t *alignment, uint64_t n_align, uint64_t round_keys, void *stream, flatgfa_dev_flip_t **job, uint64_t *n_turned,
+                           uint64_t *links_out, uint64_t *links_new);
+int flatgfa_dev_flip_fill(flatgfa_dev_flip_t *job, uint32_t *steps_out, uint32_t *turned_out, uint32_t *links_out, void *stream);
+void flatgfa_dev_flip_free(flatgfa_dev_flip_t *job);
 /* The packed-sequence codec (flatgfa_seq_export, flatgfa_seq_import) on text and packed bytes in device memory; offsets and
  * counts are 64-bit throughout.  flatgfa_dev_seq_pack_count classifies text[0, n) (at any alignment; n == 0 with NULL is
  * valid), counts the kept bases, waits for `stream` once and returns a job in *job and the count in *n_bases; a byte that is

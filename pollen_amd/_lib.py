@@ -85,6 +85,8 @@ SIGNATURES = {
                                POINTER(c_void_p)]),
     "flatgfa_inject_bed": (c_int, [c_void_p, c_char_p, c_size_t, c_int, POINTER(c_void_p)]),
     "flatgfa_crush": (c_int, [c_void_p, POINTER(c_void_p)]),
+    "flatgfa_flip": (c_int, [c_void_p, POINTER(c_void_p)]),
+    "flatgfa_flip_count": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "flatgfa_find_seg": (c_int64, [c_void_p, c_uint64]),
     "flatgfa_extract": (c_int, [c_void_p, c_uint32, c_uint64, c_uint64, c_uint64, POINTER(c_void_p)]),
     "flatgfa_position": (c_int, [c_void_p, c_uint32, c_uint64, POINTER(c_uint32), POINTER(c_uint64), POINTER(c_int)]),
@@ -161,6 +163,10 @@ SIGNATURES = {
                                         POINTER(c_uint64), POINTER(c_uint64)]),
     "flatgfa_dev_crush_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "flatgfa_dev_crush_free": (None, [c_void_p]),
+    "flatgfa_dev_flip_count": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p,
+                                       c_uint64, c_uint64, c_void_p, POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    "flatgfa_dev_flip_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "flatgfa_dev_flip_free": (None, [c_void_p]),
     "flatgfa_dev_seq_pack_count": (c_int, [c_void_p, c_uint64, c_void_p, POINTER(c_void_p), POINTER(c_uint64)]),
     "flatgfa_dev_seq_pack_fill": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "flatgfa_dev_seq_pack_free": (None, [c_void_p]),

@@ -1,7 +1,7 @@
 // extern "C" surface of libflatgfa.so: the flatgfa-c drop-in (Part 1 of include/flatgfa.h)
 // plus the additive loaders, the depth queries and the host routes of the other features (Part 2).  The kernels live in the
 // .hip files -- depth_device.hip and its kin for depth, gaf_device.hip, gaf_lookup_device.hip, chop_device.hip,
-// extract_device.hip, topology_device.hip, flatten_device.hip, crush_device.hip, seq_device.hip, print_device.hip for the rest -- and are reached through their headers; this file uses the HIP runtime
+// extract_device.hip, topology_device.hip, flatten_device.hip, crush_device.hip, flip_device.hip, seq_device.hip, print_device.hip for the rest -- and are reached through their headers; this file uses the HIP runtime
 // API only.  Every host route that is not a depth query holds what it has on the device in one DevScope (below).
 #include <hip/hip_runtime_api.h>
 
@@ -41,6 +41,8 @@
 #include "interval_device.hpp"
 #include "flatten_device.hpp"
 #include "crush_device.hpp"
+#include "flip_device.hpp"
+#include "flip_host.hpp"
 #include "seq_device.hpp"
 #include "print_device.hpp"
 #include "parse_device.hpp"
@@ -172,7 +174,7 @@ int count_devices(const std::string &who, int *ndev) {
     return FLATGFA_OK;
 }
 
-// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree, flatten, crush, seq-export, seq-import, the GFA printer, bed -- holds on the device,
+// What one host call of a route -- pangenotype, GAF lookup, chop, extract, position, validate, degree, flatten, crush, flip, seq-export, seq-import, the GFA printer, bed -- holds on the device,
 // given back on every way out: the work stream is waited for, then the job, the events and the memory go, then the streams
 // return to the pool.  A thread that still copies on one of the streams is joined first: its joiner is declared after the scope.
 struct DevScope {
@@ -1988,6 +1990,104 @@ int flatgfa_crush(flatgfa_t gfa, flatgfa_t *out) {
     cs->view = h.view();
     *out = cs.release();
     return FLATGFA_OK;
+}
+
+// ---- flip (slow_odgi/flip.py) ----
+
+extern "C++" {
+namespace {
+// How many keys of the link table a round takes: kFlipRoundKeys, or what the tests ask for.
+uint64_t flip_round_keys() {
+    if (const char *h = test_hook("FLATGFA_FLIP_ROUND_KEYS")) return std::max<uint64_t>(1, strtoull(h, nullptr, 10));
+    return fgfa_dev::kFlipRoundKeys;
+}
+
+// The count (always) and the new store (where cs_out is given): the pools are checked and the paths laid out on the host
+// (flip_host.hpp), steps, spans, lengths, links and alignment go up -- the steps and lengths of a resident graph are read in
+// place -- and the device does the rest (flip_device.hip); the names are made on the host from the turned flags.
+int flip_locked(CStore *gfa, uint64_t *n_turned_out, uint64_t *n_links_out, std::unique_ptr<CStore> *cs_out) {
+    const fgfa::View &v = gfa->view;
+    fgfa_flip::Lay lay;
+    std::string why;
+    switch (fgfa_flip::check_and_lay(v, &lay, &why)) {
+        case fgfa_flip::Verdict::kBounds: set_error("flip: " + why); return FLATGFA_ERR_BOUNDS;
+        case fgfa_flip::Verdict::kTooLarge: set_error("flip: " + why); return FLATGFA_ERR_TOO_LARGE;
+        case fgfa_flip::Verdict::kOk: break;
+    }
+    const size_t P = v.paths.len, N = v.steps.len, S = v.segs.len, L = v.links.len, A = v.alignment.len;
+    DevScope sc;
+    if (int rc = open_scope(gfa, &sc, "flip")) return rc;
+    hipStream_t st = sc.stream;
+    fgfa_dev::FlipIn in;
+    uint32_t *d_pstart = nullptr, *d_pbegin = nullptr, *d_steps = nullptr, *d_seg_len = nullptr, *d_links = nullptr, *d_align = nullptr;
+    CAPI_HIP(sc.upload(&d_pstart, lay.pstart.data(), P + 1));
+    CAPI_HIP(sc.upload(&d_pbegin, lay.pbegin.data(), P + 1));
+    if (sc.resident) {  // (read in place)
+        d_steps = gfa->d_steps;
+        d_seg_len = gfa->d_seg_len;
+    } else {
+        std::vector<uint32_t> seg_len(S);
+        for (size_t s = 0; s < S; ++s) seg_len[s] = v.segs[s].seq.len();
+        CAPI_HIP(sc.upload(&d_steps, v.steps.data, N));
+        CAPI_HIP(sc.upload(&d_seg_len, seg_len.data(), S));
+    }
+    CAPI_HIP(sc.alloc(&d_links, L * 4));
+    if (L) CAPI_HIP(fgfa_dev::staged_copy(d_links, v.links.data, L * 16, hipMemcpyHostToDevice, st));
+    CAPI_HIP(sc.alloc(&d_align, A));
+    if (A) CAPI_HIP(fgfa_dev::staged_copy(d_align, v.alignment.data, A * 4, hipMemcpyHostToDevice, st));
+    in.steps = d_steps, in.n_steps = N;
+    in.pstart = d_pstart, in.pbegin = d_pbegin, in.n_paths = (uint32_t)P, in.n_lin = lay.n_lin;
+    in.seg_len = d_seg_len, in.n_segs = (uint32_t)S;
+    in.links = d_links, in.n_links = L;
+    in.alignment = d_align, in.n_align = A;
+    fgfa_dev::FlipJob *job = sc.hold<fgfa_dev::FlipJob, fgfa_dev::flip_free>(fgfa_dev::flip_new(flip_round_keys()));
+    uint64_t n_turned = 0, links_out = 0, links_new = 0;
+    if (int rc = fgfa_dev::flip_count(job, in, st, &n_turned, &links_out, &links_new)) return rc;
+    if (n_turned_out) *n_turned_out = n_turned;
+    if (n_links_out) *n_links_out = links_out;
+    if (!cs_out) return FLATGFA_OK;
+    // the names are the host's: their size is known, and checked, before any output is allocated
+    std::vector<uint32_t> turned(P + 1, 0);
+    if (P) CAPI_HIP(fgfa_dev::staged_copy(turned.data(), fgfa_dev::flip_turned(job), P * 4, hipMemcpyDeviceToHost, st));
+    if (fgfa_flip::names_bytes(v, turned.data()) > 0xFFFFFFFFull) {
+        set_error("flip: the names of the turned paths would take name_data past 2^32 - 1 bytes");
+        return FLATGFA_ERR_TOO_LARGE;
+    }
+    uint32_t *d_steps_out = nullptr, *d_turned_out = nullptr, *d_links_out = nullptr;
+    CAPI_HIP(sc.alloc(&d_steps_out, (size_t)lay.n_lin));
+    CAPI_HIP(sc.alloc(&d_turned_out, P));
+    CAPI_HIP(sc.alloc(&d_links_out, (size_t)links_out * 4));
+    if (int rc = fgfa_dev::flip_fill(job, d_steps_out, d_turned_out, d_links_out, st)) return rc;
+    // (the host pools are made beside the kernels)
+    std::vector<fgfa::Handle> steps((size_t)lay.n_lin);
+    std::vector<fgfa::Link> links((size_t)links_out);
+    CAPI_HIP(fgfa_dev::staged_copy(steps.data(), d_steps_out, (size_t)lay.n_lin * 4, hipMemcpyDeviceToHost, st));
+    CAPI_HIP(fgfa_dev::staged_copy(links.data(), d_links_out, (size_t)links_out * 16, hipMemcpyDeviceToHost, st));
+    auto cs = std::make_unique<CStore>();
+    fgfa_flip::assemble(v, lay, turned.data(), std::move(steps), std::move(links), links_new != 0, &cs->heap);
+    cs->view = cs->heap.view();
+    *cs_out = std::move(cs);
+    return FLATGFA_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int flatgfa_flip(flatgfa_t gfa, flatgfa_t *out) {
+    if (out) *out = nullptr;
+    if (!gfa || !out) { set_error("flatgfa_flip: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    std::unique_ptr<CStore> cs;
+    if (int rc = flip_locked(gfa, nullptr, nullptr, &cs)) return rc;
+    *out = cs.release();
+    return FLATGFA_OK;
+}
+
+int flatgfa_flip_count(flatgfa_t gfa, uint64_t *n_turned, uint64_t *n_links_out) {
+    if (n_turned) *n_turned = 0;
+    if (n_links_out) *n_links_out = 0;
+    if (!gfa) { set_error("flatgfa_flip_count: NULL argument"); return FLATGFA_ERR_ARG; }
+    std::lock_guard<std::mutex> op(gfa->op_mu);
+    return flip_locked(gfa, n_turned, n_links_out, nullptr);
 }
 
 // ---- the packed-sequence codec (packedseq.rs, cli/cmds.rs:415-452) ----

@@ -3,7 +3,7 @@
 //
 //   fgfa [-i FILE.flatgfa | -I FILE.gfa] [-D] [-o OUT.flatgfa] [-O OUT.gfa] [COMMAND]
 //   COMMAND: toc [-b] | paths | stats -S | depth [-d] [-r NAME]... [-b FILE.bed] [--bed-paths FILE.bed] [-s PATHS]
-//            | window-depth PATH SIZE | window-depth-all SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l] | inject -b BED [-l] | crush
+//            | window-depth PATH SIZE | window-depth-all SIZE | overlap --paths FILE | matrix GAF | gaf GAF [-s] [-b] [-p] | chop -c N [-l] | inject -b BED [-l] | crush | flip
 //            | extract -n NAME -c DIST [-d N] [-e N] | position -p PATH,OFFSET,+ | validate | degree
 //            | flatten [-n NAME] [-f FASTA] [-b BED] | print [-O OUT.gfa]
 //   fgfa seq-export INPUT OUTPUT | fgfa seq-import FILE | fgfa bed -a FILE -b FILE        (no graph is read)
@@ -13,7 +13,7 @@
 // (-o binary, -O text, otherwise text on stdout).  `depth` output is byte-identical to the
 // reference's and is computed on the GPU, as are `matrix` (cmds.rs:453-475), `position` (cmds.rs:105-152), and `chop`
 // (cli/main.rs:139-159) and `extract` (cmds.rs:174-215), whose graph is written out as the input graph would be; `validate` and `degree` print what slow_odgi's validate.py and
-// degree.py print, `crush` writes out the graph of its crush.py, `flatten` what its flatten.py prints (or, with -f / -b, what `odgi flatten` writes to those files).
+// degree.py print, `crush` writes out the graph of its crush.py, `flip` that of its flip.py, `flatten` what its flatten.py prints (or, with -f / -b, what `odgi flatten` writes to those files).
 // `seq-export` and `seq-import` (cmds.rs:415-452) are the packed-sequence codec of packedseq.rs, on the GPU as well; like the
 // reference's they take files, not a graph, and stdin is never read.  So does `bed` (cmds.rs:378-413, bed-intersect): the lines
 // of -b that lie under the intervals of -a, found and printed on the GPU.  Of the reference CLI that leaves `bench`.
@@ -146,7 +146,7 @@ int main(int argc, char **argv) {
     // up in a cold process, the staging buffers, the first copy and the first launch another thirty
     // milliseconds.  All of that starts now, on a thread of its own, while this one maps or parses
     // the graph (and, for a mapped file, has the kernel map the step pool's pages in).
-    const bool wants_device = device_parse || cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "crush" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten" || cmd == "print" || cmd == "seq-export" || cmd == "seq-import" || cmd == "bed";
+    const bool wants_device = device_parse || cmd == "depth" || cmd == "window-depth" || cmd == "window-depth-all" || cmd == "overlap" || cmd == "matrix" || cmd == "gaf" || cmd == "chop" || cmd == "inject" || cmd == "crush" || cmd == "flip" || cmd == "extract" || cmd == "position" || cmd == "validate" || cmd == "degree" || cmd == "flatten" || cmd == "print" || cmd == "seq-export" || cmd == "seq-import" || cmd == "bed";
     // (`fgfa` only ever uses device 0: on a node with several GPUs the runtime need not bring the others up.  Set
     // before the first HIP call; a caller's or scheduler's own choice of visible devices -- by any of the variables the
     // HIP runtime honours: CUDA_VISIBLE_DEVICES and GPU_DEVICE_ORDINAL index into what ROCr exposes, so narrowing
@@ -287,7 +287,7 @@ int main(int argc, char **argv) {
     };
 
     // dump (cli/main.rs:192-212): -o FILE as .flatgfa, else -O FILE as GFA text, else GFA text on stdout.  The text of a
-    // command that has brought the device up (chop, inject, crush, extract) is formatted there; a bare `fgfa` prints on the
+    // command that has brought the device up (chop, inject, crush, flip, extract) is formatted there; a bare `fgfa` prints on the
     // host, where a small graph does not pay for the HIP runtime coming up.
     auto dump = [&](flatgfa_t gr) -> int {
         if (out_flat) return flatgfa_write_flatgfa(gr, out_flat) ? die("write") : 0;
@@ -373,6 +373,16 @@ int main(int argc, char **argv) {
         flatgfa_t crushed = nullptr;
         if (flatgfa_crush(g, &crushed)) rc = die("crush");
         else rc = dump(crushed);
+    } else if (cmd == "flip") {
+        // slow_odgi flip (`odgi flip`): reverse-heavy paths are turned around and the links they need added; written out as chop's is
+        if (i != argc) {
+            fprintf(stderr, "usage: fgfa flip\n");
+            flatgfa_free(g);
+            return 2;
+        }
+        flatgfa_t flipped = nullptr;
+        if (flatgfa_flip(g, &flipped)) rc = die("flip");
+        else rc = dump(flipped);
     } else if (cmd == "extract") {
         // cli/cmds.rs:174-215: fgfa extract -n NAME -c DIST [-d N] [-e N]
         uint64_t name = 0, dist = 0, max_dist = 300000, iters = 6;

@@ -413,6 +413,54 @@ def crush(graph: DeviceGraph, seg_seq, seq_data, stream=None):
         return new, seq_out, seg_seq_out
 
 
+def flip(graph: DeviceGraph, links, stream=None, alignment=None, round_keys: int = 0):
+    """flip (slow_odgi/flip.py) of a resident graph image and its links, on the device: links is int32[4 * n_links], the
+    Link records (from, to, overlap.start, overlap.end), and alignment the int32 pool their overlaps point into (None: an
+    empty pool, for links whose overlap spans are all empty), both CUDA tensors.  Returns (the flipped image, links_out,
+    turned): a DeviceGraph whose steps are the paths one behind another in path order -- the turned ones reversed, every
+    orientation toggled -- and which shares graph's seg_len (a valid input to DepthPlan); the kept Link records (int32[4 *
+    n]: the old links without their duplicates, then the new ones, whose overlap [len(alignment), len(alignment) + 1) is
+    the one 0M op, the word 0, that the caller appends to its pool); and the turned flags (int32[n_paths], 0 or 1).  Needs
+    graph.seg_len.  round_keys (0: the library's 2^26) is for tests and measurements: how many keys of the link table a round
+    of the grouping takes; it never changes the answer.  Waits for the stream once, to learn the sizes (flatgfa_dev_flip_count); the rest is enqueued on it
+    (torch's current stream by default)."""
+    torch = _torch()
+    if graph.seg_len is None:
+        raise FlatGFAError("flip: the graph has no seg_len", -1)
+    assert links.dtype == torch.int32 and links.is_cuda and links.is_contiguous() and links.numel() % 4 == 0
+    if alignment is not None:
+        assert alignment.dtype == torch.int32 and alignment.is_cuda and alignment.is_contiguous()
+    P = graph.n_paths
+    lens = graph.h_path_end.astype(np.int64) - graph.h_path_begin.astype(np.int64)
+    if (lens < 0).any() or int(lens.sum()) > 0xFFFFFFFF:
+        raise FlatGFAError("flip: a path span ends before it begins, or the paths hold more than 2^32 - 1 steps", -2)
+    h_start = np.zeros(P + 1, dtype=np.uint32)
+    h_start[1:] = np.cumsum(lens, dtype=np.int64).astype(np.uint32)
+    n_lin = int(h_start[P])
+    with torch.cuda.device(graph.device):
+        st = stream if stream is not None else torch.cuda.current_stream(graph.device)
+        st_ptr = ctypes.c_void_p(st.cuda_stream)
+        job = ctypes.c_void_p()
+        n_turned, n_out, n_new = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        L = _lib.lib()
+        n_align = 0 if alignment is None else int(alignment.numel())
+        with torch.cuda.stream(st):  # (the outputs are the stream's: torch's allocator may hand their memory on behind it)
+            start = _as_i32(h_start).to(graph.device)
+            _check(L.flatgfa_dev_flip_count(_ptr(graph.steps), graph.n_steps, start.data_ptr(), _ptr(graph.path_begin), P, n_lin,
+                                            _ptr(graph.seg_len), graph.n_segs, _ptr(links), int(links.numel()) // 4,
+                                            None if alignment is None else _ptr(alignment), n_align, int(round_keys), st_ptr, ctypes.byref(job),
+                                            ctypes.byref(n_turned), ctypes.byref(n_out), ctypes.byref(n_new)), "dev_flip_count")
+            try:
+                steps = torch.empty(n_lin, dtype=torch.int32, device=graph.device)
+                turned = torch.empty(P, dtype=torch.int32, device=graph.device)
+                links_out = torch.empty(4 * n_out.value, dtype=torch.int32, device=graph.device)
+                _check(L.flatgfa_dev_flip_fill(job, _ptr(steps), _ptr(turned), _ptr(links_out), st_ptr), "dev_flip_fill")
+            finally:
+                L.flatgfa_dev_flip_free(job)  # (waits for the fill, on this stream only)
+            new = DeviceGraph.from_tensors(steps, start[:P].contiguous(), start[1:].contiguous(), graph.n_segs, graph.seg_len, h_start[:P], h_start[1:])
+        return new, links_out, turned
+
+
 def seq_pack(text, stream=None, carry: int = -1):
     """The packed-sequence codec's pack (packedseq.rs) of nucleotide text on the device: text is a uint8 CUDA tensor, at any
     alignment (a slice will do).  Returns (packed, n_bases): a uint8 tensor of (n_bases + (carry >= 0) + 1) // 2 bytes -- two

@@ -501,6 +501,24 @@ class FlatGFA:
         _check(_lib.lib().flatgfa_crush(self._h, ctypes.byref(h)), "crush")
         return FlatGFA(h.value)
 
+    # ---- flip (slow_odgi/flip.py) ----
+    def flip(self) -> "FlatGFA":
+        """`fgfa flip`: a new graph in which every path that walks more bases backward than forward is turned around --
+        its steps reversed, every orientation toggled, `_inv` appended to its name -- and the links the turned paths need
+        are added (overlap 0M) and all links de-duplicated, a link and its reverse complement being one (slow_odgi/flip.py,
+        `odgi flip`), computed on the GPU.  Paths lose their overlaps and segments their optional fields; the steps are laid
+        out again in path order.  The result owns its pools and outlives this graph."""
+        h = ctypes.c_void_p()
+        _check(_lib.lib().flatgfa_flip(self._h, ctypes.byref(h)), "flip")
+        return FlatGFA(h.value)
+
+    def flip_count(self) -> Tuple[int, int]:
+        """What :meth:`flip` would do, counted on the GPU without building the graph: (paths that turn, links of the
+        result)."""
+        turned, links = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(_lib.lib().flatgfa_flip_count(self._h, ctypes.byref(turned), ctypes.byref(links)), "flip_count")
+        return int(turned.value), int(links.value)
+
     # ---- inject (slow_odgi/inject.py) ----
     def inject(self, bed, links: bool = False) -> "FlatGFA":
         """`fgfa inject -b BED [-l]`: a new graph in which every BED line "path start end new_name" is a path of its own:
