@@ -600,7 +600,12 @@ typedef struct flatgfa_dev_graph_t {
  * those the image and the run records were made of: such a plan turns the image into records in
  * the first of a row of node-depth calls and counts the calls behind it from those records without
  * reading the steps at all (no answer is kept: every call counts anew, into the caller's buffers;
- * another kind of call, a status that reports anything, or changed steps end the row).  A caller that DOES change step values
+ * another kind of call, a status that reports anything, or changed steps end the row).  Device memory such a
+ * plan holds beside its record buckets: its share of the image (8 bytes a run, one copy for all plans of a
+ * step array), 8 bytes an item, and -- where its description says pass2=sorted -- the same records once more,
+ * sorted by window, path and start for pass 2 (4 bytes a record and 4 a chunk of 64: sorted_image=<MiB>, 40 at
+ * a million segments and 100 M steps; about nine times that transiently while it is made, behind the first
+ * answer; plans of one step array over the same paths, a pipeline's lanes among them, share one).  A caller that DOES change step values
  * under a live plan says so with flatgfa_dev_plan_steps_changed (below), which makes the plan
  * again from the steps as they are; FLATGFA_CHECK_NO_CLAIM=1 in the environment (read when a plan
  * is made; a debugging aid, three more reads of the steps per call) re-derives those facts before

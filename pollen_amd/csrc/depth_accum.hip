@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "depth_fast_kernels.hpp"
+#include "depth_sorted_host.hpp"
 
 namespace fgfa_dev {
 namespace {
@@ -224,6 +225,42 @@ __device__ __forceinline__ void add_n(uint32_t *out, uint32_t i0, uint32_t nvali
         if (a[k] && i0 + k < nvalid) atomicAdd(out + i0 + k, a[k]);
 }
 
+// Pass 2's epilogue, shared by every build of it: the window's counts from its difference arrays (thread t holds the kPer cells
+// from kPer * t on) -- with unique depth one scan for both, depth in the low word and revisits in the high word of a 64-bit
+// value (every prefix has both counts non-negative, so the words do not disturb each other) -- and their way out.
+template <bool UNIQ, int kPer>
+__device__ __forceinline__ void window_counts(const int *D, const int *R, unsigned long long *wave_tot, uint32_t i0, uint32_t (&d)[kPer], uint32_t (&rv)[kPer]) {
+    if (UNIQ) {
+        unsigned long long v[kPer];
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) v[k] = (unsigned long long)(long long)D[i0 + k] + ((unsigned long long)(long long)R[i0 + k] << 32);
+        block_scan<unsigned long long, kPer>(wave_tot, v);
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) {
+            d[k] = (uint32_t)v[k];
+            rv[k] = (uint32_t)(v[k] >> 32);
+        }
+    } else {
+        int v[kPer];
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) v[k] = D[i0 + k];
+        block_scan<int, kPer>(reinterpret_cast<int *>(wave_tot), v);
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) d[k] = (uint32_t)v[k];
+    }
+}
+// (add: several workgroups share the window, or the outputs hold the counts of the paths walked before)
+template <bool UNIQ, int kPer>
+__device__ __forceinline__ void write_counts(const AccArgs &A, uint32_t w0, uint32_t i0, uint32_t nvalid, bool add, const uint32_t (&d)[kPer], const uint32_t (&u)[kPer]) {
+    if (add) {
+        add_n<kPer>(A.depth_out + w0, i0, nvalid, d);
+        if (UNIQ) add_n<kPer>(A.uniq_out + w0, i0, nvalid, u);
+    } else {
+        store_n<kPer>(A.depth_out + w0, i0, nvalid, d);
+        if (UNIQ) store_n<kPer>(A.uniq_out + w0, i0, nvalid, u);
+    }
+}
+
 // Apply the records [0, scnt[slot]) of every sub-bucket of the window as they are (they say what
 // they count for).  Each wave takes sixteen sub-buckets per round and requests the first 64 x 16
 // bytes of every one before it applies any, so a round pays the memory latency once.
@@ -293,17 +330,6 @@ __device__ __forceinline__ uint32_t rec_take() {
     else if (K == 1) asm volatile("s_waitcnt vmcnt(2)\n\tv_mov_b32 %0, v121" : "=v"(r)::"memory");
     else asm volatile("s_waitcnt vmcnt(2)\n\tv_mov_b32 %0, v122" : "=v"(r)::"memory");
     return r;
-}
-
-// inclusive prefix maximum across the wave
-__device__ __forceinline__ uint32_t wave_scan_max(uint32_t x) {
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x111 /* row_shr:1 */, 0xf, 0xf, true));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x112 /* row_shr:2 */, 0xf, 0xf, true));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x114 /* row_shr:4 */, 0xf, 0xf, true));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x118 /* row_shr:8 */, 0xf, 0xf, true));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x142 /* row_bcast:15 */, 0xa, 0xf, true));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x143 /* row_bcast:31 */, 0xc, 0xf, true));
-    return x;
 }
 
 // Walk this wave's stretch of k_scan's items (plus its share of the handed-back ones).  Their
@@ -1198,21 +1224,13 @@ __device__ __forceinline__ void accum_body(const AccArgs &A) {
     if (UNIQ) {
         // one scan for both: depth in the low word, revisits in the high word of a 64-bit value
         // (every prefix has both counts non-negative, so the words do not disturb each other)
-        unsigned long long v[kPer];
+        uint32_t rv[kPer];
+        window_counts<true, kPer>(D, R, wave_tot, i0, d, rv);
 #pragma unroll
-        for (int k = 0; k < kPer; ++k) v[k] = (unsigned long long)(long long)D[i0 + k] + ((unsigned long long)(long long)R[i0 + k] << 32);
-        block_scan<unsigned long long, kPer>(wave_tot, v);
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            d[k] = (uint32_t)v[k];
-            u[k] = d[k] - (uint32_t)(v[k] >> 32);
-        }
+        for (int k = 0; k < kPer; ++k) u[k] = d[k] - rv[k];
         if (PAIR) {
             // this workgroup's half: depth and revisits, in scratch; whoever finds the other half there adds it up
             __shared__ uint32_t second;
-            uint32_t rv[kPer];
-#pragma unroll
-            for (int k = 0; k < kPer; ++k) rv[k] = (uint32_t)(v[k] >> 32);
             uint32_t *mine = A.pair_part + ((size_t)win * 2u + blockIdx.y) * (2u * kW);
             const uint32_t *theirs = A.pair_part + ((size_t)win * 2u + (1u - blockIdx.y)) * (2u * kW);
             // The two workgroups may sit on different XCDs, whose L2s do not see each other's lines within
@@ -1245,24 +1263,14 @@ __device__ __forceinline__ void accum_body(const AccArgs &A) {
                 }
                 if (tid == 0) __hip_atomic_store(&A.pair_flag[win], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (clean for the next call)
             }
-        } else if (A.parts > 1 || A.accumulate) {
-            add_n<kPer>(A.depth_out + w0, i0, nvalid, d);
-            add_n<kPer>(A.uniq_out + w0, i0, nvalid, u);
         } else {
-            store_n<kPer>(A.depth_out + w0, i0, nvalid, d);
-            store_n<kPer>(A.uniq_out + w0, i0, nvalid, u);
+            write_counts<true, kPer>(A, w0, i0, nvalid, A.parts > 1 || A.accumulate, d, u);
         }
         tm.mark(4);
         tm.finish();
     } else {
-        int v[kPer];
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) v[k] = D[i0 + k];
-        block_scan<int, kPer>(reinterpret_cast<int *>(wave_tot), v);
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) d[k] = (uint32_t)v[k];
-        if (!PSUM && (A.parts > 1 || A.accumulate)) add_n<kPer>(A.depth_out + w0, i0, nvalid, d);
-        else store_n<kPer>(A.depth_out + w0, i0, nvalid, d);
+        window_counts<false, kPer>(D, R, wave_tot, i0, d, u);
+        write_counts<false, kPer>(A, w0, i0, nvalid, !PSUM && (A.parts > 1 || A.accumulate), d, u);
         if (PSUM) {
             unsigned long long l[kPer], w[kPer];
 #pragma unroll
@@ -1304,6 +1312,95 @@ __global__ __launch_bounds__(kAccThreads) __attribute__((amdgpu_waves_per_eu(8, 
     accum_body<true, WB, false, false, false, true, false, (int)kTagSlots, true, true>(A);
 }
 #endif
+
+// ============================================================ pass 2 on the sorted record image ===
+//   The plan's records, sorted once by (window, path, start) and cut into chunks of 64 (depth_sorted.hip):
+// a cell of a record [s, e) has been visited before by its path exactly if it lies below M, the largest end among the path's
+// earlier records in that order -- so the record's revisits are the one stretch [s, min(e, M)), and uniq = depth - revisits
+// as in every other build.  M is a running maximum over the lanes of one path: a plain prefix maximum of
+// (ordinal of the lane's path among the chunk's records) << 14 | e, with the chunk's carry word for the path that was under
+// way when the chunk began.  No bitset, no returning LDS operation, no hand-over: a step is a coalesced load, a ballot, seven
+// DPP operations and two to four LDS adds.  Chunks are independent; a workgroup's waves take the window's in a stride, the
+// records of eight chunks requested ahead of their use (two sets of four registers taking turns: no copy waits for a load).
+constexpr int kSortedAhead = 4;
+template <bool NT>
+__device__ __forceinline__ uint32_t sorted_load(const uint32_t *p) { return NT ? __builtin_nontemporal_load(p) : *p; }
+
+template <bool UNIQ, int WB>
+__device__ __forceinline__ void sweep_chunk(int *D, int *R, uint32_t rec, uint32_t carry, int lane) {
+    constexpr uint32_t kW = 1u << WB, kEndMask = (1u << kSortedEndBits) - 1u;
+    const bool valid = !(rec & kSortedPad);
+    const uint32_t s = rec & (kW - 1u), e = s + ((rec >> WB) & 1023u) + 1u;  // e <= window size; that cell is a sink
+    if (valid) {
+        atomicAdd(&D[s], 1);
+        atomicAdd(&D[e], -1);
+    }
+    if (UNIQ) {
+        const unsigned long long fm = __builtin_amdgcn_ballot_w64(valid && (rec & kSortedFirst));
+        const uint32_t ord = (uint32_t)__builtin_popcountll(fm & (~0ull >> (63 - lane)));  // which of the chunk's paths the lane's record belongs to (0: the one under way)
+        const uint32_t x = valid ? (ord << kSortedEndBits) | e : 0u;
+        // the maximum over the lanes BEFORE this one: the values move up a lane, then the inclusive scan
+        const uint32_t before = wave_scan_max((uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x138 /* wave_shr:1 */, 0xf, 0xf, true));
+        uint32_t M = (before >> kSortedEndBits) == ord ? before & kEndMask : 0u;
+        if (ord == 0u) M = max(M, carry);
+        if (valid && M > s) {
+            atomicAdd(&R[s], 1);
+            atomicAdd(&R[min(e, M)], -1);
+        }
+    }
+}
+
+template <bool UNIQ, int WB, bool NT>
+__global__ __launch_bounds__(kAccThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_accum_sorted(const AccArgs A) {
+    constexpr uint32_t kW = 1u << WB;
+    constexpr int kPer = kW / kAccThreads;
+    __shared__ __attribute__((aligned(16))) int cells[(UNIQ ? 2 : 1) * (kW + 64)];
+    __shared__ unsigned long long wave_tot[kAccWaves];
+    int *D = cells, *R = cells + (UNIQ ? kW + 64 : 0);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t win = blockIdx.x, w0 = win * kW;
+    const uint32_t c1 = __builtin_amdgcn_readfirstlane(A.swin_chunk[win + 1]);
+    uint32_t c = __builtin_amdgcn_readfirstlane(A.swin_chunk[win]) + wave;
+    uint32_t ra[kSortedAhead], rb[kSortedAhead], ca[kSortedAhead], cb[kSortedAhead];
+    // (chunks behind the window's last read as padding; the addresses stay inside the image)
+    const auto request = [&](uint32_t (&r)[kSortedAhead], uint32_t (&cy)[kSortedAhead], uint32_t at) {
+#pragma unroll
+        for (int k = 0; k < kSortedAhead; ++k) {
+            const uint32_t ck = at + (uint32_t)k * kAccWaves;
+            const bool in = ck < c1;
+            const uint32_t v = sorted_load<NT>(A.srec + (size_t)(in ? ck : 0u) * kSortedChunk + lane);
+            r[k] = in ? v : kSortedPad;
+            cy[k] = UNIQ && in ? A.scarry[ck] : 0u;
+        }
+    };
+    const auto sweep = [&](const uint32_t (&r)[kSortedAhead], const uint32_t (&cy)[kSortedAhead]) {
+#pragma unroll
+        for (int k = 0; k < kSortedAhead; ++k) sweep_chunk<UNIQ, WB>(D, R, r[k], cy[k], lane);
+    };
+    constexpr uint32_t kStride = kSortedAhead * kAccWaves;
+    if (c < c1) request(ra, ca, c);  // (on its way while the workgroup clears its arrays)
+    for (uint32_t i = tid; i < (UNIQ ? 2u : 1u) * (kW + 64); i += kAccThreads) cells[i] = 0;
+    __syncthreads();
+    while (c < c1) {
+        if (c + kStride < c1) request(rb, cb, c + kStride);
+        sweep(ra, ca);
+        c += kStride;
+        if (c >= c1) break;
+        if (c + kStride < c1) request(ra, ca, c + kStride);
+        sweep(rb, cb);
+        c += kStride;
+    }
+    __syncthreads();
+    const uint32_t nvalid = min(kW, A.n_segs - w0), i0 = kPer * tid;
+    uint32_t d[kPer], u[kPer];
+    window_counts<UNIQ, kPer>(D, R, wave_tot, i0, d, u);  // (u: the revisits)
+    if (UNIQ) {
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) u[k] = d[k] - u[k];
+    }
+    write_counts<UNIQ, kPer>(A, w0, i0, nvalid, A.accumulate != 0u, d, u);
+}
 
 }  // namespace
 
@@ -1356,7 +1453,20 @@ bool accum_kernels_setup() {
         if (nc) hipLaunchKernelGGL((k_accum<true, WB_, false, false, false, true, SLOTS_, true, true>), GRID, dim3(kAccThreads), LDS, stream, aa);  \
         else hipLaunchKernelGGL((k_accum<true, WB_, false, false, false, true, SLOTS_, false, true>), GRID, dim3(kAccThreads), LDS, stream, aa);    \
     } while (0)
-void launch_accum(const FastPlan &fp, AccArgs &aa, bool uniq, bool tagged, bool psum, hipStream_t stream) {
+#define FGFA_SORTED_LAUNCH(WB_)                                                                                                  \
+    do {                                                                                                                        \
+        if (uniq && fp.sorted_nt) hipLaunchKernelGGL((k_accum_sorted<true, WB_, true>), dim3(fp.n_win), dim3(kAccThreads), 0, stream, aa);        \
+        else if (uniq) hipLaunchKernelGGL((k_accum_sorted<true, WB_, false>), dim3(fp.n_win), dim3(kAccThreads), 0, stream, aa);                  \
+        else if (fp.sorted_nt) hipLaunchKernelGGL((k_accum_sorted<false, WB_, true>), dim3(fp.n_win), dim3(kAccThreads), 0, stream, aa);          \
+        else hipLaunchKernelGGL((k_accum_sorted<false, WB_, false>), dim3(fp.n_win), dim3(kAccThreads), 0, stream, aa);                           \
+    } while (0)
+void launch_accum(const FastPlan &fp, AccArgs &aa, bool uniq, bool tagged, bool psum, hipStream_t stream, bool sorted) {
+    if (sorted) {  // (decide_call: one workgroup per window, 2048- to 8192-segment windows, no path sums)
+        if (fp.wb == 11) FGFA_SORTED_LAUNCH(11);
+        else if (fp.wb == 12) FGFA_SORTED_LAUNCH(12);
+        else FGFA_SORTED_LAUNCH(13);
+        return;
+    }
     const dim3 agrid(fp.n_win, fp.acc_parts);
     const bool pair = uniq && tagged && fp.acc_pair;
     const bool nc = fp.n_noclaim != 0 || fp.n_flag_chunks != 0;
@@ -1405,6 +1515,7 @@ void launch_accum(const FastPlan &fp, AccArgs &aa, bool uniq, bool tagged, bool 
 }
 #undef FGFA_TAGGED_LAUNCH
 #undef FGFA_OWN_LAUNCH
+#undef FGFA_SORTED_LAUNCH
 
 void launch_path_reduce(const FastPlan &fp, unsigned long long *len_out, unsigned long long *weighted_out, hipStream_t stream) {
     hipLaunchKernelGGL(k_path_reduce, dim3((fp.n_items + 3) / 4), dim3(256), 0, stream, reinterpret_cast<const uint4 *>(fp.items), fp.elist, fp.n_items,

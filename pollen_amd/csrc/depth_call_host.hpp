@@ -38,6 +38,7 @@ struct CallShape {
     bool tagged = false, ranged = false, big = false, cflags = false;
     bool from_image = false;  // pass 1 reads the steps' run-length image (k_scan_runs)
     bool kept = false;        // ... whose records of the call before are still there: pass 1 is left out
+    bool sorted = false;      // ... and pass 2 sweeps the plan's sorted record image (k_accum_sorted) instead of walking the kept records
     uint32_t has_pre2 = 0;    // pass 2: 0 = all records are k_scan's, 1 = the wave-per-path kernels' lie before them, 2 = there are no others
     uint32_t max_back = 0;    // paths that may be handed back to k_scan, as both passes see it
     Zeroes outputs = Zeroes::nobody, sums = Zeroes::nobody;
@@ -102,6 +103,9 @@ inline CallShape decide_call(const FastPlan &fp, const GraphFacts &g, const Call
     // ... and where the records of the image call before this one are still in the scratch (RecordsUse: the handle knows), it
     // would write the same records into the same slots: pass 1 is left out, pass 2 reads the kept cursors and leaves them.
     s.kept = s.from_image && records_use && fp.counts_kept;
+    // ... and exactly those calls, once the plan's sorted record image is installed (one pass-2 workgroup per window, the window
+    // widths it has builds for), sweep that.  Pass 1 runs wherever it ran: whatever drops the kept records brings it back.
+    s.sorted = s.kept && fp.sorted_rec && fp.sorted_carry && fp.sorted_win_chunk && fp.acc_parts == 1 && fp.wb >= 11 && fp.wb <= 13;
     if (s.scans() && !s.from_image && scan_mode(fp, s).mode == kModeRefused) {
         CallShape no;
         no.refusal = "fast_seg_depth: a bucket array this large needs a tagged call";

@@ -23,6 +23,7 @@
 #include "../../include/flatgfa.h"
 #include "depth_call_host.hpp"
 #include "depth_fast.hpp"
+#include "depth_sorted_host.hpp"
 #include "temp_arena.hpp"
 #include "host_copy.hpp"
 #include "device_common.hpp"
@@ -299,6 +300,13 @@ struct flatgfa_dev_plan {
     // kernels, by plan_grow, with the plan's scratch (steps_changed), and by a status that reads anything but zero.
     bool records_kept = false;
     bool keep_records = true;          // FLATGFA_KEEP_RECORDS=0 as it was when the plan was made: every image call runs pass 1
+    // The sorted record image (sorted_poll): the plan's reference to the one that the plans of its run
+    // image with the same paths, windows and segment range share; made on the side stream behind the items' entries of the plan
+    // that asked first, valid exactly as long as the run image is -- dropped with it (steps_changed, the rebuild, destroy).
+    struct SortedShare *sorted = nullptr;
+    int sorted_state = 0;              // 0: not looked at yet, 1: being made, 3: installed, -1: none
+    const char *sorted_off = "";       // ... and why not
+    int sorted_hook = -1;              // FLATGFA_SORTED_RECORDS as it was when the plan was made (0, 1; -1: unset)
 };
 
 // Every call of a plan through the bucketed kernels: it says whether the scratch holds an image call's records, and takes
@@ -436,6 +444,19 @@ struct RunShare {
     int users;
     bool listed;
     bool any_ratio;  // (FLATGFA_RUN_IMAGE=1 of the plan that asked first: no limit on entries per step)
+    std::vector<struct SortedShare *> sorted;  // the sorted record images made of this run image, one per set of paths and window layout
+};
+// One sorted record image for the plans of one run image that have the same path spans, window width and
+// segment range: the lanes of a pipeline, a stand-alone plan beside them.  It is made of the items of the plan that asked first
+// (`builder`, while it is being made: the build reads that plan's items and their entries); how another plan cuts the same paths
+// into items does not matter -- an item's edge splits a run into two records that abut, which count the same depth and no
+// revisit.  Reference-counted; the last plan to go frees it.  Guarded by g_run_mu.
+struct SortedShare {
+    fgfa_dev::SortedImage *img;
+    flatgfa_dev_plan_t *builder;
+    uint32_t wb, n_win, n_range, n_segs;
+    std::vector<uint32_t> hb, he;
+    int users;
 };
 static std::mutex g_run_mu;
 static std::vector<RunShare *> g_run_shares;
@@ -463,7 +484,32 @@ static void side_work_enqueued(int device) {
 }
 constexpr bool kRunImageDefault = true;        // plans that qualify get the image without being asked (FLATGFA_RUN_IMAGE=0|1 decides otherwise)
 
+// The plan's reference to its sorted record image goes before its run-image state does (a build under way reads the items and the
+// entries of the plan that started it: that plan sees it through first); the last reference frees the image.
+static void sorted_release(flatgfa_dev_plan_t *pl) {
+    pl->fast.sorted_rec = pl->fast.sorted_carry = pl->fast.sorted_win_chunk = nullptr;
+    if (SortedShare *ss = pl->sorted) {
+        std::lock_guard<std::mutex> lk(g_run_mu);
+        if (ss->builder == pl) {
+            (void)sorted_image_poll(ss->img, pl->fast, pl->side, true, kRunImageReserve, pl->sorted_hook == 1);
+            ss->builder = nullptr;
+        }
+        if (--ss->users == 0) {
+            if (pl->run) {
+                auto &list = pl->run->sorted;
+                list.erase(std::remove(list.begin(), list.end(), ss), list.end());
+            }
+            sorted_image_free(ss->img, pl->side);
+            delete ss;
+        }
+        pl->sorted = nullptr;
+    }
+    pl->sorted_state = 0;
+    pl->sorted_off = "";
+}
+
 static void run_release(flatgfa_dev_plan_t *pl, bool steps_changed) {
+    sorted_release(pl);
     if (pl->run_items_done) {
         (void)hipEventSynchronize(pl->run_items_done);
         (void)hipEventDestroy(pl->run_items_done);
@@ -528,11 +574,13 @@ static const char *run_image_refused(flatgfa_dev_plan_t *pl) {
 // installs both.  Called between two calls of the plan, once its no-claim marks are settled.  The image's kernels are first
 // enqueued at the END of a call (`behind`: the stream that call's kernels went to, which the side stream then waits for -- the
 // answer of the call that starts them is not slowed by them), or where no call is in flight (`may_start`: status, describe).
+static void sorted_poll(flatgfa_dev_plan_t *pl, bool wait);
 static void run_poll(flatgfa_dev_plan_t *pl, bool wait, bool may_start, hipStream_t behind = nullptr) {
-    if (pl->run_state == 3 || pl->run_state < 0) return;
+    if (pl->run_state < 0 || (pl->run_state == 3 && (pl->sorted_state == 3 || pl->sorted_state < 0))) return;
     if (pl->run_state == 0 && !may_start) return;
     DeviceGuard guard;
     if (guard.dev < 0 || !guard.switch_to(pl->device)) { (void)hipGetLastError(); return; }
+    if (pl->run_state == 3) { sorted_poll(pl, wait); return; }
     const auto give_up = [&](const char *why) {
         run_release(pl, false);
         pl->run_state = -1;
@@ -554,7 +602,7 @@ static void run_poll(flatgfa_dev_plan_t *pl, bool wait, bool may_start, hipStrea
         for (RunShare *sh : g_run_shares)
             if (sh->device == pl->device && sh->steps == pl->g.steps && sh->n_steps == pl->g.n_steps) pl->run = sh;
         if (!pl->run) {
-            pl->run = new RunShare{pl->device, pl->g.steps, pl->g.n_steps, run_image_start(pl->g, side), side, 0, true, pl->run_hook == 1};
+            pl->run = new RunShare{pl->device, pl->g.steps, pl->g.n_steps, run_image_start(pl->g, side), side, 0, true, pl->run_hook == 1, {}};
             g_run_shares.push_back(pl->run);
             side_work_enqueued(pl->device);
         }
@@ -612,7 +660,55 @@ static void run_poll(flatgfa_dev_plan_t *pl, bool wait, bool may_start, hipStrea
         }
         run_image_install(&pl->fast, pl->run->img, pl->run_item_ent, nt);
         pl->run_state = 3;
+        sorted_poll(pl, wait);
     }
+}
+
+// ... and behind the run image, as a further state of the same machine, the plan's sorted record image:
+// counted, then -- the host has to know how many records there are before it gives them room -- emitted, sorted and finalised,
+// all on the side stream and under the side stream's rule (no call runs beside it: side_work_enqueued / side_work_wait), and
+// installed between two calls.  The plan's device is current.
+static void sorted_poll(flatgfa_dev_plan_t *pl, bool wait) {
+    if (pl->sorted_state == 3 || pl->sorted_state < 0 || pl->run_state != 3) return;
+    const auto give_up = [&](const char *why) {
+        sorted_release(pl);
+        pl->sorted_state = -1;
+        pl->sorted_off = why;
+    };
+    const FastPlan &f = pl->fast;
+    hipStream_t side = pl->run->side;
+    if (pl->sorted_state == 0) {
+        if (const char *why = sorted_refused(pl->sorted_hook, f.acc_parts, f.n_groups, f.n_more, f.wb, pl->keep_records && f.counts_kept)) { give_up(why); return; }
+        std::lock_guard<std::mutex> lk(g_run_mu);
+        for (SortedShare *ss : pl->run->sorted)
+            if (ss->wb == f.wb && ss->n_win == f.n_win && ss->n_range == f.n_range && ss->n_segs == pl->g.n_segs && ss->hb == pl->hb && ss->he == pl->he) pl->sorted = ss;
+        if (!pl->sorted) {
+            pl->sorted = new SortedShare{sorted_image_start(f, pl->g.n_paths, side), pl, f.wb, f.n_win, f.n_range, pl->g.n_segs, pl->hb, pl->he, 0};
+            pl->run->sorted.push_back(pl->sorted);
+            side_work_enqueued(pl->device);
+        }
+        pl->sorted->users += 1;
+        pl->sorted_state = 1;
+    }
+    int r;
+    const char *why = "";
+    {
+        std::lock_guard<std::mutex> lk(g_run_mu);
+        SortedShare *ss = pl->sorted;
+        const int before = sorted_image_phase(ss->img);
+        r = sorted_image_poll(ss->img, ss->builder ? ss->builder->fast : f, side, wait, kRunImageReserve, pl->sorted_hook == 1);
+        if (before == 1 && sorted_image_phase(ss->img) == 2) side_work_enqueued(pl->device);  // (this poll enqueued its second stage)
+        if (r != 0) ss->builder = nullptr;  // (there, or not to be had: nothing reads the builder's items any more)
+        if (r < 0) why = sorted_image_why(ss->img);
+    }
+    if (r == 0) return;
+    if (r < 0) { give_up(why); return; }
+    // plain reads while image and results fit what the steps' claim on the Infinity Cache is budgeted against (the run image's rule)
+    const int64_t traffic = (int64_t)sorted_image_bytes(pl->sorted->img) + 8ll * (int64_t)pl->g.n_segs;
+    const char *mall = getenv("FLATGFA_MALL_MB");
+    const bool nt = traffic > (244ll << 20) || (mall && strtoull(mall, nullptr, 10) == 0);
+    sorted_image_install(&pl->fast, pl->sorted->img, nt);
+    pl->sorted_state = 3;
 }
 
 // The per-block no-claim marks are made on a stream of the plan's own, behind its creation:
@@ -948,6 +1044,8 @@ static bool plan_build_fast(flatgfa_dev_plan_t *pl, uint32_t *first_depth, uint3
     pl->run_hook = hook ? (hook[0] == '1' ? 1 : 0) : -1;
     const char *keep = test_hook("FLATGFA_KEEP_RECORDS");  // (0: every image call runs pass 1)
     pl->keep_records = !(keep && keep[0] == '0');
+    const char *sorted = test_hook("FLATGFA_SORTED_RECORDS");  // (0: pass 2 keeps its walk everywhere; 1: the sorted image whatever memory its build leaves free)
+    pl->sorted_hook = sorted ? (sorted[0] == '1' ? 1 : 0) : -1;
     return true;
 }
 
@@ -1319,8 +1417,18 @@ extern "C" int flatgfa_dev_plan_describe(flatgfa_dev_plan_t *pl, char *out, int 
             if (pl->run_state == 3) {  // (its size in MB, the steps it was made of, the plans that hold it now, how k_scan_runs reads it)
                 std::lock_guard<std::mutex> lk(g_run_mu);
                 s += " run_image=" + std::to_string((run_image_bytes(pl->run->img) + (1u << 20) - 1) >> 20) + " run_image_steps=" + std::to_string(pl->run->n_steps) +
-                     " run_image_plans=" + std::to_string(pl->run->users) + " run_image_reads=" + (f.run_nt ? "nt" : "plain") +
-                     " records=" + (pl->keep_records && f.counts_kept ? "kept" : "rewritten");  // (pass 1 once per run of image calls, or in every call)
+                     " run_image_plans=" + std::to_string(pl->run->users) + " run_image_reads=" + (f.run_nt ? "nt" : "plain");
+                // (which pass 2 the calls on kept records run: the sweep over the plan's sorted record image -- what that holds of the
+                // device's memory, in MB -- or the walk as ever, and why; FLATGFA_SORTED_RECORDS=0: the walk, nothing said)
+                // (MB the image holds, MB its build held beside that while it ran, the plans that share it now)
+                const auto mb = [](uint64_t bytes) { return std::to_string((bytes + (1u << 20) - 1) >> 20); };
+                if (pl->sorted_state == 3 && f.sorted_rec) {
+                    s += " sorted_image=" + mb(sorted_image_bytes(pl->sorted->img)) + " sorted_image_build=" + mb(sorted_image_transient(pl->sorted->img)) +
+                         " sorted_image_plans=" + std::to_string(pl->sorted->users) + " sorted_chunk=" + std::to_string(kSortedChunk) + " pass2=sorted";
+                } else if (pl->sorted_hook != 0) {
+                    s += std::string(" pass2=walk(") + (pl->sorted_state < 0 ? pl->sorted_off : "pending") + ")";
+                }
+                s += std::string(" records=") + (pl->keep_records && f.counts_kept ? "kept" : "rewritten");  // (pass 1 once per run of image calls, or in every call)
             } else {
                 s += std::string(" run_image=off(") + (pl->run_state < 0 ? pl->run_off : "pending") + ")";
             }

@@ -1499,6 +1499,9 @@ static AccArgs acc_args(const FastPlan &fp, const flatgfa_dev_graph_t &g, const 
     aa.fullest = fp.taken ? fp.taken + fp.n_slots : nullptr;
     aa.pk = fp.packed ? reinterpret_cast<const uint2 *>(fp.pk) : nullptr;
     aa.keep = s.kept ? 1u : 0u;
+    aa.srec = fp.sorted_rec;
+    aa.scarry = fp.sorted_carry;
+    aa.swin_chunk = fp.sorted_win_chunk;
     return aa;
 }
 
@@ -1580,7 +1583,7 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
     if (count_only) return hipGetLastError() == hipSuccess ? FLATGFA_OK : FLATGFA_ERR_HIP;  // (the counting call of a packed plan: pass 1 alone)
     {
         ProfScope pscope(uniq ? "k_accum<uniq>" : (ps ? "k_accum<depth+paths>" : "k_accum<depth>"), stream);
-        launch_accum(fp, aa, uniq, s.tagged, ps != nullptr, stream);
+        launch_accum(fp, aa, uniq, s.tagged, ps != nullptr, stream, s.sorted);
     }
     if (ps && fp.n_items) {
         ProfScope pscope("k_path_reduce", stream);

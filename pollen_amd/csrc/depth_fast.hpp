@@ -174,6 +174,11 @@ struct FastPlan {
     // u32[n_win * n_slots] the cursors k_scan_runs left, a second time: pass 2 zeroes `counts` behind every call, a call that
     // runs on the records of the image call before it (RecordsUse) reads these and leaves them.  nullptr: records are never kept.
     uint32_t *counts_kept = nullptr;
+    // The plan's sorted record image, once it is installed (sorted_image_install): the same records in the
+    // order pass 2 sweeps them in, a carry word per chunk of them, and every window's chunks.  The calls that would run pass 2
+    // alone on the kept records run k_accum_sorted on these.  The plan's handle's; not freed by fast_plan_destroy.
+    const uint32_t *sorted_rec = nullptr, *sorted_carry = nullptr, *sorted_win_chunk = nullptr;
+    bool sorted_nt = false;              // read past the caches (image and results do not fit the Infinity Cache)
 };
 
 // What a plan's handle tells a call about the records in the plan's scratch, and what the call tells it back.  k_scan_runs'
@@ -250,6 +255,21 @@ bool run_items_start(const FastPlan &fp, const RunImage *im, hipStream_t side, v
 uint32_t run_room_needed(const FastPlan &fp, const void *room);
 // From the plan's next tagged call on, pass 1 reads the image.  (No call of the plan may be enqueued concurrently from another thread.)
 void run_image_install(FastPlan *fp, const RunImage *im, void *item_ent, bool nt);
+
+// The sorted record image of a plan whose run image is installed (depth_sorted.hip): made on `side` in two
+// stages with the host in between -- the records are counted per window, then emitted as (key, record) pairs, sorted, and
+// finalised into chunks.  Never null; one that cannot be had says so when it is polled.
+struct SortedImage;
+SortedImage *sorted_image_start(const FastPlan &fp, uint32_t n_paths, hipStream_t side);
+// 1 = there, 0 = not yet, -1 = not to be had (sorted_image_why: "bounds" -- a record was dropped, pass 1 has an error to raise --,
+// "memory" -- the build would leave less than `reserve` bytes free, unless `waived` --, "size", "error")
+int sorted_image_poll(SortedImage *si, const FastPlan &fp, hipStream_t side, bool wait, uint64_t reserve, bool waived);
+const char *sorted_image_why(const SortedImage *si);
+uint64_t sorted_image_bytes(const SortedImage *si);      // what the plan keeps, once it is there
+uint64_t sorted_image_transient(const SortedImage *si);  // what the build held beside that (the description reports both)
+int sorted_image_phase(const SortedImage *si);           // 1: counted (enqueued), 2: emitted, sorted, finalised (enqueued), 3: there, -1: not to be had
+void sorted_image_install(FastPlan *fp, const SortedImage *si, bool nt);
+void sorted_image_free(SortedImage *si, hipStream_t side);
 
 // Decides eligibility (16-byte aligned steps, directories that stay small next to the steps) and
 // allocates the scratch: one range of at most 2048 windows, or several.  Returns false only on a HIP error.

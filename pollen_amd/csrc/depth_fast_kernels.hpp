@@ -404,6 +404,19 @@ constexpr uint32_t kJobEmpty = 0xFFFFFFFFu, kJobPending = 0xFFFFFFFEu;  // nobod
 
 // ------------------------------------------------------------------ pass 2 ---
 
+#ifdef __HIPCC__
+// inclusive prefix maximum across the wave (pass 2's walks and sweep, the sorted image's finaliser)
+__device__ __forceinline__ uint32_t wave_scan_max(uint32_t x) {
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x111 /* row_shr:1 */, 0xf, 0xf, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x112 /* row_shr:2 */, 0xf, 0xf, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x114 /* row_shr:4 */, 0xf, 0xf, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x118 /* row_shr:8 */, 0xf, 0xf, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x142 /* row_bcast:15 */, 0xa, 0xf, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x143 /* row_bcast:31 */, 0xc, 0xf, true));
+    return x;
+}
+#endif
+
 struct AccArgs {
     uint32_t n_segs, n_win, n_slots, cap;
     uint32_t *counts;         // [n_win][n_slots] final cursors (zeroed here: self-cleaning scratch)
@@ -442,6 +455,8 @@ struct AccArgs {
     uint32_t *fullest;      // this range's fullest sub-bucket beyond half the capacity (read and cleared by fast_plan_grow)
     const uint2 *pk;        // packed buckets: [n_win][n_slots] {where the sub-bucket starts in `buckets`, its room}; else null
     uint32_t keep;          // `counts` is the plan's kept copy (FastPlan::counts_kept): read, not zeroed
+    // the plan's sorted record image (k_accum_sorted; depth_sorted_host.hpp): the records, a carry word per chunk, every window's chunks
+    const uint32_t *srec, *scarry, *swin_chunk;
 };
 
 // FLATGFA_ACC_TIME: charge the time since the last mark to phase `ph` of this wave; the wave's
@@ -503,7 +518,8 @@ void launch_scan_runs(const FastPlan &fp, const ScanArgs &sa, uint32_t grid, hip
 void launch_scan_tiny(const FastPlan &fp, const ScanArgs &sk, bool uniq, uint32_t grid, hipStream_t stream);
 void launch_scan_short(const FastPlan &fp, const ScanArgs &sk, bool medium, bool uniq, uint32_t grid, hipStream_t stream);
 // pass 2 in the build the call needs (unique depth or not, tagged walk or directory walk, path sums, window size)
-void launch_accum(const FastPlan &fp, AccArgs &aa, bool uniq, bool tagged, bool psum, hipStream_t stream);
+// (sorted: the sweep over the plan's sorted record image, k_accum_sorted, instead of any walk)
+void launch_accum(const FastPlan &fp, AccArgs &aa, bool uniq, bool tagged, bool psum, hipStream_t stream, bool sorted = false);
 void launch_path_reduce(const FastPlan &fp, unsigned long long *len_out, unsigned long long *weighted_out, hipStream_t stream);
 
 }  // namespace fgfa_dev
