@@ -1317,41 +1317,60 @@ __global__ __launch_bounds__(kAccThreads) __attribute__((amdgpu_waves_per_eu(8, 
 //   The plan's records, sorted once by (window, path, start) and cut into chunks of 64 (depth_sorted.hip):
 // a cell of a record [s, e) has been visited before by its path exactly if it lies below M, the largest end among the path's
 // earlier records in that order -- so the record's revisits are the one stretch [s, min(e, M)), and uniq = depth - revisits
-// as in every other build.  M is a running maximum over the lanes of one path: a plain prefix maximum of
-// (ordinal of the lane's path among the chunk's records) << 14 | e, with the chunk's carry word for the path that was under
-// way when the chunk began.  No bitset, no returning LDS operation, no hand-over: a step is a coalesced load, a ballot, seven
-// DPP operations and two to four LDS adds.  Chunks are independent; a workgroup's waves take the window's in a stride, the
-// records of eight chunks requested ahead of their use (two sets of four registers taking turns: no copy waits for a load).
-constexpr int kSortedAhead = 4;
+// as in every other build.  M is a running maximum over the records of one path.  A step takes a GROUP of four consecutive
+// chunks of the window: a lane holds four consecutive records (one 16-byte load), all of chunk q = lane >> 4; a record's key is
+// q | the ordinal of its path among its chunk's records (which the image carries) | e, from the top, and a chunk's carry word
+// -- for the path that was under way when the chunk began -- is one more key before the chunk's first (depth_sorted_host.hpp
+// has the arithmetic, which tests/host_check/sorted_group_check.cpp runs as well).  One exclusive prefix maximum of the lanes'
+// largest keys per group, then a running maximum inside the lane.  No bitset, no returning LDS operation, no hand-over, no
+// ballot: a step is one load of the records, one of the carries, seven DPP operations, and two to four LDS adds a record.
+// Groups are independent; a workgroup's waves take the window's in a stride, the records of two groups (eight chunks) requested
+// ahead of their use (two sets of registers taking turns: no copy waits for a load).  Only the group that holds the window's
+// last chunk can hold padding, or lanes behind the window's end: that one runs the CHECKED build, the others test nothing.
+typedef uint32_t sorted_u32x4 __attribute__((ext_vector_type(4)));
 template <bool NT>
-__device__ __forceinline__ uint32_t sorted_load(const uint32_t *p) { return NT ? __builtin_nontemporal_load(p) : *p; }
+__device__ __forceinline__ sorted_u32x4 sorted_load4(const sorted_u32x4 *p) { return NT ? __builtin_nontemporal_load(p) : *p; }
 
-template <bool UNIQ, int WB>
-__device__ __forceinline__ void sweep_chunk(int *D, int *R, uint32_t rec, uint32_t carry, int lane) {
-    constexpr uint32_t kW = 1u << WB, kEndMask = (1u << kSortedEndBits) - 1u;
-    const bool valid = !(rec & kSortedPad);
-    const uint32_t s = rec & (kW - 1u), e = s + ((rec >> WB) & 1023u) + 1u;  // e <= window size; that cell is a sink
-    if (valid) {
-        atomicAdd(&D[s], 1);
-        atomicAdd(&D[e], -1);
-    }
+template <bool UNIQ, int WB, bool CHECKED>
+__device__ __forceinline__ void sweep_group(int *D, int *R, const sorted_u32x4 &r4, uint32_t carry, bool in, int lane) {
+    // (in: the lane's chunk lies inside the window -- CHECKED only; a lane behind the end holds padding whatever it read)
+    const uint32_t pad = CHECKED && !in ? kSortedPad : 0u;
+    const uint32_t rec[kSortedGroup] = {r4.x | pad, r4.y | pad, r4.z | pad, r4.w | pad};
     if (UNIQ) {
-        const unsigned long long fm = __builtin_amdgcn_ballot_w64(valid && (rec & kSortedFirst));
-        const uint32_t ord = (uint32_t)__builtin_popcountll(fm & (~0ull >> (63 - lane)));  // which of the chunk's paths the lane's record belongs to (0: the one under way)
-        const uint32_t x = valid ? (ord << kSortedEndBits) | e : 0u;
-        // the maximum over the lanes BEFORE this one: the values move up a lane, then the inclusive scan
-        const uint32_t before = wave_scan_max((uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x138 /* wave_shr:1 */, 0xf, 0xf, true));
-        uint32_t M = (before >> kSortedEndBits) == ord ? before & kEndMask : 0u;
-        if (ord == 0u) M = max(M, carry);
-        if (valid && M > s) {
-            atomicAdd(&R[s], 1);
-            atomicAdd(&R[min(e, M)], -1);
+        const uint32_t q = (uint32_t)lane >> 4, seed = CHECKED && !in ? 0u : sorted_seed(q, carry);
+        SortedLane ln;
+        sorted_lane_keys<CHECKED>(rec, q, (uint32_t)WB, seed, ln);
+        // the largest key over the lanes BEFORE this one: the values move up a lane, then the inclusive scan
+        uint32_t p = sorted_umax(seed, wave_scan_max((uint32_t)__builtin_amdgcn_update_dpp(0u, ln.t, 0x138 /* wave_shr:1 */, 0xf, 0xf, true)));
+#pragma unroll
+        for (uint32_t k = 0; k < kSortedGroup; ++k) {
+            uint32_t end;
+            const bool hit = sorted_record_step<CHECKED>(p, ln.x[k], ln.len[k], end);
+            if (!CHECKED || ln.x[k] != 0u) {
+                atomicAdd(&D[ln.s[k]], 1);
+                atomicAdd(&D[ln.s[k] + ln.len[k] + 1u], -1);  // e <= window size; that cell is a sink
+            }
+            if (hit) {
+                atomicAdd(&R[ln.s[k]], 1);
+                atomicAdd(&R[end], -1);
+            }
+        }
+    } else {
+        constexpr uint32_t kW = 1u << WB;
+#pragma unroll
+        for (uint32_t k = 0; k < kSortedGroup; ++k) {
+            const uint32_t s = rec[k] & (kW - 1u), e = s + ((rec[k] >> WB) & 1023u) + 1u;
+            if (!CHECKED || !(rec[k] & kSortedPad)) {
+                atomicAdd(&D[s], 1);
+                atomicAdd(&D[e], -1);
+            }
         }
     }
 }
 
 template <bool UNIQ, int WB, bool NT>
 __global__ __launch_bounds__(kAccThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_accum_sorted(const AccArgs A) {
+    static_assert(kSortedChunk == 64u && kSortedGroup == 4u, "a lane holds four consecutive records of one chunk: sixteen lanes a chunk");
     constexpr uint32_t kW = 1u << WB;
     constexpr int kPer = kW / kAccThreads;
     __shared__ __attribute__((aligned(16))) int cells[(UNIQ ? 2 : 1) * (kW + 64)];
@@ -1360,36 +1379,38 @@ __global__ __launch_bounds__(kAccThreads) __attribute__((amdgpu_waves_per_eu(8, 
     const int tid = threadIdx.x, lane = tid & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t win = blockIdx.x, w0 = win * kW;
-    const uint32_t c1 = __builtin_amdgcn_readfirstlane(A.swin_chunk[win + 1]);
-    uint32_t c = __builtin_amdgcn_readfirstlane(A.swin_chunk[win]) + wave;
-    uint32_t ra[kSortedAhead], rb[kSortedAhead], ca[kSortedAhead], cb[kSortedAhead];
-    // (chunks behind the window's last read as padding; the addresses stay inside the image)
-    const auto request = [&](uint32_t (&r)[kSortedAhead], uint32_t (&cy)[kSortedAhead], uint32_t at) {
-#pragma unroll
-        for (int k = 0; k < kSortedAhead; ++k) {
-            const uint32_t ck = at + (uint32_t)k * kAccWaves;
-            const bool in = ck < c1;
-            const uint32_t v = sorted_load<NT>(A.srec + (size_t)(in ? ck : 0u) * kSortedChunk + lane);
-            r[k] = in ? v : kSortedPad;
-            cy[k] = UNIQ && in ? A.scarry[ck] : 0u;
-        }
+    const uint32_t c0 = __builtin_amdgcn_readfirstlane(A.swin_chunk[win]), c1 = __builtin_amdgcn_readfirstlane(A.swin_chunk[win + 1]);
+    const uint32_t ng = (c1 - c0 + kSortedGroup - 1u) / kSortedGroup;  // the window's groups; the last one is the only one that may hold padding
+    const sorted_u32x4 *img = reinterpret_cast<const sorted_u32x4 *>(A.srec);  // (a chunk is 256 bytes, a window's first chunk aligned to that)
+    const uint32_t q = (uint32_t)lane >> 4;
+    uint32_t g = wave;
+    sorted_u32x4 ra, rb;
+    uint32_t ca = 0u, cb = 0u;
+    // (lanes whose chunk lies behind the window's last read the window's last records and carry, which the CHECKED build takes
+    // for padding: the addresses stay inside the image)
+    const auto request = [&](sorted_u32x4 &r, uint32_t &cy, uint32_t at) {
+        const uint32_t ck = c0 + at * kSortedGroup;
+        r = sorted_load4<NT>(img + min(ck * (kSortedChunk / kSortedGroup) + (uint32_t)lane, c1 * (kSortedChunk / kSortedGroup) - 1u));
+        if (UNIQ) cy = A.scarry[min(ck + q, c1 - 1u)];
     };
-    const auto sweep = [&](const uint32_t (&r)[kSortedAhead], const uint32_t (&cy)[kSortedAhead]) {
-#pragma unroll
-        for (int k = 0; k < kSortedAhead; ++k) sweep_chunk<UNIQ, WB>(D, R, r[k], cy[k], lane);
+    const auto sweep = [&](const sorted_u32x4 &r, uint32_t cy, uint32_t at) {
+        if (at + 1u == ng) sweep_group<UNIQ, WB, true>(D, R, r, cy, c0 + at * kSortedGroup + q < c1, lane);
+        else sweep_group<UNIQ, WB, false>(D, R, r, cy, true, lane);
     };
-    constexpr uint32_t kStride = kSortedAhead * kAccWaves;
-    if (c < c1) request(ra, ca, c);  // (on its way while the workgroup clears its arrays)
+    // A request is made whether or not its group exists (one behind the window's last reads the window's last records, which
+    // nobody looks at): with a request under a condition the compiler waits for EVERY load before a sweep, the one just made
+    // included, and a wave stands through a whole trip to memory per group.
+    if (ng) request(ra, ca, g);  // (on its way while the workgroup clears its arrays; a window without records has no address to read)
     for (uint32_t i = tid; i < (UNIQ ? 2u : 1u) * (kW + 64); i += kAccThreads) cells[i] = 0;
     __syncthreads();
-    while (c < c1) {
-        if (c + kStride < c1) request(rb, cb, c + kStride);
-        sweep(ra, ca);
-        c += kStride;
-        if (c >= c1) break;
-        if (c + kStride < c1) request(ra, ca, c + kStride);
-        sweep(rb, cb);
-        c += kStride;
+    while (g < ng) {
+        request(rb, cb, g + kAccWaves);
+        sweep(ra, ca, g);
+        g += kAccWaves;
+        if (g >= ng) break;
+        request(ra, ca, g + kAccWaves);
+        sweep(rb, cb, g);
+        g += kAccWaves;
     }
     __syncthreads();
     const uint32_t nvalid = min(kW, A.n_segs - w0), i0 = kPer * tid;

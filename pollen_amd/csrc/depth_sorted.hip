@@ -111,7 +111,8 @@ __global__ __launch_bounds__(256) void sorted_image_emit(const uint4 *__restrict
     }
 }
 
-// One wave per window walks the window's sorted pairs a chunk at a time: the first record of every path gets its flag, the
+// One wave per window walks the window's sorted pairs a chunk at a time: the first record of every path gets its flag, every
+// record the ordinal of its path among its chunk's records (kSortedOrdShift: what the sweep's keys are made of), the
 // window is padded to whole chunks, and every chunk gets its carry word -- the largest end among the earlier records, in this
 // window, of the path the chunk begins with; 0 where the chunk begins a path.
 __global__ __launch_bounds__(64) void sorted_image_finalise(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ recs, const uint32_t *__restrict__ rec_off,
@@ -137,7 +138,8 @@ __global__ __launch_bounds__(64) void sorted_image_finalise(const uint64_t *__re
             const uint32_t ord = (uint32_t)__builtin_popcountll(fm & (~0ull >> (63 - lane)));
             const uint32_t e = (rec & wmask) + ((rec >> wb) & 1023u) + 1u;
             const uint32_t incl = wave_scan_max(have ? (ord << kSortedEndBits) | e : 0u);
-            img[(size_t)(c0 + c) * kSortedChunk + lane] = have ? rec | (first ? kSortedFirst : 0u) : kSortedPad;
+            // (the record carries its path's ordinal in its chunk, so the sweep reads it and does not count flags: an index, as the flag is)
+            img[(size_t)(c0 + c) * kSortedChunk + lane] = have ? rec | (first ? kSortedFirst : 0u) | (ord << kSortedOrdShift) : kSortedPad;
             if (lane == 0) carry[c0 + c] = first ? 0u : carry_m;
             // what the next chunk starts from: the last record's path, and the largest end of that path's records so far
             const uint32_t last = min(cnt - c * kSortedChunk, kSortedChunk) - 1u;

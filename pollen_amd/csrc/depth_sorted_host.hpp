@@ -3,7 +3,8 @@
 // with a carry word -- an index for pass 2 (k_accum_sorted), never an answer.  Here: what the host decides about it, as
 // functions over plain data -- the sort key and how many bits it takes, where every window's chunks lie, what the build needs
 // of the device's memory and when that is refused.  No HIP runtime call and no environment variable in here;
-// tests/host_check/sorted_check.cpp runs these functions without a GPU.
+// tests/host_check/sorted_check.cpp runs these functions without a GPU.  At the end: the sweep's arithmetic per lane, one text for
+// k_accum_sorted and for tests/host_check/sorted_group_check.cpp.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -23,6 +24,11 @@ constexpr uint32_t kSortedChunk = 64u * kSortedK;   // records per chunk
 constexpr uint32_t kSortedFirst = 1u << 23;         // ... the first record of its path in its window
 constexpr uint32_t kSortedPad = 1u << 31;           // ... a record that counts nothing (a window is padded to whole chunks)
 constexpr uint32_t kSortedEndBits = 14;             // a record's end is at most 8192: the sweep's scan keeps it below its path's ordinal
+constexpr uint32_t kSortedOrdShift = 24;            // ... bits 24..30: how many of the chunk's records up to this one are the first of their path (0..64; 0: the path was under way when the chunk began)
+constexpr uint32_t kSortedOrdMask = 0x7Fu;
+constexpr uint32_t kSortedGroup = 4;                // consecutive chunks of a window the sweep takes in one step: a lane holds four consecutive records
+constexpr uint32_t kSortedQShift = kSortedEndBits + 7;  // the sweep's key: chunk within the group | ordinal | end, from the top
+static_assert(kSortedOrdShift + 7 == 31 && kSortedQShift + 2 <= 24, "the ordinal lies between the first-of-path flag and the padding flag; the key fits a word");
 
 inline uint32_t bits_for(uint64_t n_values) {  // bits that hold 0 .. n_values - 1
     uint32_t b = 0;
@@ -91,6 +97,42 @@ inline const char *sorted_refused(int hook, uint32_t acc_parts, uint32_t n_group
     if (n_groups > 1 || n_more) return "ranges";
     if (wb < 11 || wb > 13) return "windows";
     return nullptr;
+}
+
+// ---- the sweep's arithmetic per lane (k_accum_sorted; tests/host_check/sorted_group_check.cpp runs the same text) ----
+// A step of the sweep takes a group of kSortedGroup consecutive chunks of a window; lane L holds records 4L .. 4L+3 of the
+// group, all of chunk q = L >> 4.  A record's key x = q | its ordinal in its chunk | its end, from the top, never falls along
+// the group's records of one path and rises from path to path and chunk to chunk; so with p the largest key among the records
+// before it -- and the chunk's seed, its carry word as a record of ordinal 0 before the chunk's first -- a record revisits cells
+// exactly if p >= x - len (the same chunk, the same path, an earlier end beyond its start), and the stretch ends at the smaller
+// of the two ends.  CHECKED: the build for the one group of a window that may hold padding (key 0: it counts nothing).
+FGFA_SORTED_HD inline uint32_t sorted_umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+FGFA_SORTED_HD inline uint32_t sorted_umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
+FGFA_SORTED_HD inline uint32_t sorted_seed(uint32_t q, uint32_t carry) { return (q << kSortedQShift) | carry; }
+
+struct SortedLane {
+    uint32_t s[kSortedGroup], len[kSortedGroup], x[kSortedGroup];  // start, length - 1, key (0: padding)
+    uint32_t t;                                                      // the largest of the lane's keys and its chunk's seed
+};
+template <bool CHECKED>
+FGFA_SORTED_HD inline void sorted_lane_keys(const uint32_t (&rec)[kSortedGroup], uint32_t q, uint32_t wb, uint32_t seed, SortedLane &ln) {
+    ln.t = seed;  // (at every lane of the chunk: the seed stands before all of them, and a maximum takes it twice as once)
+    for (uint32_t k = 0; k < kSortedGroup; ++k) {
+        ln.s[k] = rec[k] & ((1u << wb) - 1u);
+        ln.len[k] = (rec[k] >> wb) & 1023u;
+        const uint32_t x = ((rec[k] >> (kSortedOrdShift - kSortedEndBits)) & (kSortedOrdMask << kSortedEndBits)) | ((q << kSortedQShift) + ln.s[k] + ln.len[k] + 1u);
+        ln.x[k] = CHECKED && (rec[k] & kSortedPad) ? 0u : x;
+        ln.t = sorted_umax(ln.t, ln.x[k]);
+    }
+}
+// One record against p, the largest key before it (the lane's first starts from the larger of the wave's exclusive prefix
+// maximum of t and the seed): whether it revisits cells, and where that stretch [s, end) ends; p takes the record in.
+template <bool CHECKED>
+FGFA_SORTED_HD inline bool sorted_record_step(uint32_t &p, uint32_t x, uint32_t len, uint32_t &end) {
+    const bool hit = (!CHECKED || x != 0u) && p >= x - len;
+    end = sorted_umin(x, p) & ((1u << kSortedEndBits) - 1u);
+    p = sorted_umax(p, x);
+    return hit;
 }
 
 }  // namespace fgfa_dev
