@@ -5,6 +5,16 @@ neighbouring segments that end and start with N, whose runs must not join -- 3 p
 
     <stem>.crush.gfa      the graph as the reference prints it
 
+Three small random graphs (tests/random_pools.py, profile "text", seeds TEXT_SEEDS: N runs at segment ends and starts and on both
+sides of a seam, sparse names, ties, palindromes, hub rows) are crushed too.  Their GFA text is regenerated from the seed and not
+kept, and the outputs end in .txt because tests/test_parse_shapes.py counts every *.gfa under tests/golden:
+
+    random_<seed>.crush.txt
+
+mygfa splits a line on blanks and admits only ATGCN, so the text profile has no empty segment; it has no path without steps and no
+path name that is empty or taken either (the reference keys paths by name and prints steps[0]).  The palindromic link x- -> x+ is left
+out as well, as a link and as a pair of steps: mygfa's Link.__str__ (gfa.py:196-201) reverses it into itself without end.
+
 MANIFEST.json records the sha256 and size of every output, how many bases the crush dropped (the S lines of the input and
 of the output, compared) and whether the input ends in a newline (the reference's parser and this project's read an
 unterminated last line differently; the tests hold the device against these bytes where it does and against
@@ -18,11 +28,14 @@ import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.dirname(HERE)
+ROOT = os.path.dirname(os.path.dirname(GOLDEN))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 SYNTH_CRUSH = {"seed": 17, "S": 300, "P": 3, "L": 60, "links": 40}
 
@@ -89,6 +102,21 @@ def main():
         manifest[stem + ".crush.gfa"] = {"sha256": hashlib.sha256(out).hexdigest(), "bytes": len(out), "dropped": bases(src) - bases(out),
                                          "input_ends_in_newline": src.endswith(b"\n")}
         print(stem, len(out), manifest[stem + ".crush.gfa"]["dropped"])
+    import random_pools as rp
+    largest = max(v["bytes"] for v in manifest.values())
+    with tempfile.TemporaryDirectory() as d:
+        for seed in rp.TEXT_SEEDS:
+            stem = "random_%d" % seed
+            text = rp.gfa_text(rp.make(seed, "text"))
+            with open(os.path.join(d, stem + ".gfa"), "wb") as f:
+                f.write(text)
+            out = slow_odgi_crush(os.path.join(d, stem + ".gfa"))
+            assert len(out) <= largest
+            with open(os.path.join(HERE, stem + ".crush.txt"), "wb") as f:
+                f.write(out)
+            manifest[stem + ".gfa"] = {"sha256": hashlib.sha256(text).hexdigest(), "bytes": len(text), "profile": "text", "seed": seed, "committed": False}
+            manifest[stem + ".crush.txt"] = {"sha256": hashlib.sha256(out).hexdigest(), "bytes": len(out), "dropped": bases(text) - bases(out)}
+            print(stem, len(out), bases(text) - bases(out))
     with open(os.path.join(HERE, "MANIFEST.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
         f.write("\n")

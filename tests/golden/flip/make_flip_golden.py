@@ -18,6 +18,16 @@ and planted by hand, beside twelve seeded random walks of which about half turn:
 
 (The names end in .txt because tests/test_parse_shapes.py counts every *.gfa under tests/golden.)
 
+Three small random graphs (tests/random_pools.py, profile "text", seeds TEXT_SEEDS: ties of the two weights, one pair walked by two
+turned paths and by a path that stays, self-loops, the palindromic x+ -> x-, old links in both spellings and with 5M beside 0M, a hub
+row, sparse names) are flipped too; their GFA text is regenerated from the seed and not kept:
+
+    random_<seed>.flip.txt
+
+mygfa splits a line on blanks and admits only ATGCN, so the text profile has no empty segment; it has no path without steps and no
+path name that is empty or taken either (the reference keys paths by name).  The palindromic link x- -> x+ is left out as well, as a
+link and as a pair of steps, which flip would make one: mygfa's Link.__str__ (gfa.py:196-201) reverses it into itself without end.
+
 MANIFEST.json records the sha256 and size of every output, how many paths turned (the P lines named `_inv` that the input
 does not have), the L lines of the input and of the output, and whether the input ends in a newline (the reference's parser
 and this project's read an unterminated last line differently; the tests hold the device against these bytes where it does
@@ -32,11 +42,14 @@ import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.dirname(HERE)
+ROOT = os.path.dirname(os.path.dirname(GOLDEN))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 SYNTH_FLIP = {"seed": 23, "S": 300, "walks": 12, "L": 60, "links": 40}
 
@@ -103,6 +116,23 @@ def main():
                                         "links_in": len(lines_of(src, b"L")), "links_out": len(lines_of(out, b"L")),
                                         "input_ends_in_newline": src.endswith(b"\n")}
         print(stem, len(out), turned, manifest[stem + ".flip.gfa.txt"]["links_in"], manifest[stem + ".flip.gfa.txt"]["links_out"])
+    import random_pools as rp
+    largest = max(v["bytes"] for v in manifest.values())
+    with tempfile.TemporaryDirectory() as d:
+        for seed in rp.TEXT_SEEDS:
+            stem = "random_%d" % seed
+            text = rp.gfa_text(rp.make(seed, "text"))
+            with open(os.path.join(d, stem + ".gfa"), "wb") as f:
+                f.write(text)
+            out = slow_odgi_flip(os.path.join(d, stem + ".gfa"))
+            assert len(out) <= largest
+            with open(os.path.join(HERE, stem + ".flip.txt"), "wb") as f:
+                f.write(out)
+            turned = sum(1 for ln in lines_of(out, b"P") if ln.split(b"\t")[1].endswith(b"_inv"))
+            manifest[stem + ".gfa"] = {"sha256": hashlib.sha256(text).hexdigest(), "bytes": len(text), "profile": "text", "seed": seed, "committed": False}
+            manifest[stem + ".flip.txt"] = {"sha256": hashlib.sha256(out).hexdigest(), "bytes": len(out), "turned": turned,
+                                            "links_in": len(lines_of(text, b"L")), "links_out": len(lines_of(out, b"L"))}
+            print(stem, len(out), turned, len(lines_of(text, b"L")), len(lines_of(out, b"L")))
     with open(os.path.join(HERE, "MANIFEST.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
         f.write("\n")

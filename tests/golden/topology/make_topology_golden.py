@@ -5,7 +5,11 @@ tests/turnt.toml validate and degree environments -- on every tests/golden/*.gfa
     <name>.validate.txt  <name>.degree.tsv  <name>.dropped.gfa  <name>.dropped.validate.txt
 
 and on the mid-size synthetic graph of tests/topology_shapes.py (synth_mid), whose GFA text is regenerated from its spec and
-not kept: synth_mid.validate.txt, synth_mid.degree.tsv.  MANIFEST.json records the sha256 of every output.  Needs the
+not kept: synth_mid.validate.txt, synth_mid.degree.tsv; and on three small random graphs (tests/random_pools.py, profile "text", seeds
+TEXT_SEEDS: a quarter of the induced links dropped, each written in one spelling, duplicates in both spellings, self-loops, the
+palindromic x+ -> x-, a hub row past the linear-probe threshold, sparse names), regenerated from the seed and not kept either:
+random_<seed>.validate.txt, random_<seed>.degree.tsv.  mygfa splits a line on blanks and admits only ATGCN, so the text profile
+has no empty segment; it has no path without steps and no path name that is empty or taken either.  MANIFEST.json records the sha256 of every output.  Needs the
 reference's slow_odgi and mygfa on PYTHONPATH; the tests only read the outputs.
 
     PYTHONPATH=REFERENCE/slow_odgi:REFERENCE/mygfa python tests/golden/topology/make_topology_golden.py
@@ -54,6 +58,18 @@ def main():
         write("synth_mid.degree.tsv", slow_odgi("degree", path))
     manifest["synth_mid.gfa"] = {"sha256": hashlib.sha256(text).hexdigest(), "bytes": len(text), "spec": ts.SYNTH_MID, "committed": False}
     print("synth_mid", manifest["synth_mid.validate.txt"])
+    import random_pools as rp
+    with tempfile.TemporaryDirectory() as d:
+        for seed in rp.TEXT_SEEDS:
+            stem = "random_%d" % seed
+            text = rp.gfa_text(rp.make(seed, "text"))
+            path = os.path.join(d, stem + ".gfa")
+            with open(path, "wb") as f:
+                f.write(text)
+            write(stem + ".validate.txt", slow_odgi("validate", path))
+            write(stem + ".degree.tsv", slow_odgi("degree", path))
+            manifest[stem + ".gfa"] = {"sha256": hashlib.sha256(text).hexdigest(), "bytes": len(text), "profile": "text", "seed": seed, "committed": False}
+            print(stem, manifest[stem + ".validate.txt"]["lines"])
     with open(os.path.join(HERE, "MANIFEST.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
         f.write("\n")

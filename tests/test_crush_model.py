@@ -11,6 +11,7 @@ import pytest
 import crush_model as cm
 import crush_shapes as cs
 import pollen_amd as pa
+import random_pools as rp
 from conftest import GOLDEN, fixture_id, golden_gfas
 
 CRUSH = os.path.join(GOLDEN, "crush")
@@ -135,6 +136,23 @@ def test_model_text_is_the_references(path):
     want = cm.text_views(ref)
     for a, b, what in zip(got, want, ("S", "P", "L", "H")):
         assert a == b, (stem, what)
+
+
+@pytest.mark.parametrize("seed", rp.TEXT_SEEDS)
+def test_model_text_is_the_references_on_random_graphs(seed):
+    """random_pools' text profile: N on both sides of a seam, runs at segment ends, segments of one N, sparse names."""
+    p = rp.make(seed, "text")
+    src = MANIFEST["random_%d.gfa" % seed]
+    assert hashlib.sha256(rp.gfa_text(p)).hexdigest() == src["sha256"]  # the graph the reference was given
+    rec = MANIFEST["random_%d.crush.txt" % seed]
+    with open(os.path.join(CRUSH, "random_%d.crush.txt" % seed), "rb") as f:
+        ref = f.read()
+    assert hashlib.sha256(ref).hexdigest() == rec["sha256"] and len(ref) == rec["bytes"]
+    q = cm.crush(p)
+    cm.assert_same_pools(q, cm.crush_fast(p), seed)
+    assert cm.dropped(p) == rec["dropped"] > 50
+    for a, b, what in zip(cm.text_views(cm.text(q), ours=True), cm.text_views(ref), ("S", "P", "L", "H")):
+        assert a == b, (seed, what)
 
 
 def test_at_least_two_fixtures_drop_bytes():

@@ -10,6 +10,7 @@ import pytest
 
 import chop_shapes as cs
 import flatten_model as fm
+import random_pools as rp
 from conftest import GOLDEN
 from oracle import flatgfa_oracle as fo
 
@@ -49,6 +50,18 @@ def test_model_is_the_reference(stem, gfa):
     p = fo.parse_gfa(text)
     assert fm.flatten(p, stem.encode() + b".og") == want
     assert fm.bed_fast(p, stem.encode() + b".og") == fm.bed(p, stem.encode() + b".og")
+
+
+@pytest.mark.parametrize("seed", rp.TEXT_SEEDS)
+def test_model_is_the_reference_on_random_graphs(seed):
+    """random_pools' text profile: sparse names, segments of one base, paths of one and two steps between long ones."""
+    p = rp.make(seed, "text")
+    assert hashlib.sha256(rp.gfa_text(p)).hexdigest() == MANIFEST["random_%d.gfa" % seed]["sha256"]  # the graph the reference was given
+    with open(os.path.join(FLAT, "random_%d.flattened.txt" % seed), "rb") as f:
+        want = f.read()
+    assert hashlib.sha256(want).hexdigest() == MANIFEST["random_%d.flattened.txt" % seed]["sha256"]
+    assert fm.flatten(p, b"random_%d.og" % seed) == want
+    assert fm.bed_fast(p, b"random_%d.og" % seed) == fm.bed(p, b"random_%d.og" % seed)
 
 
 def test_synth_flat_wraps_and_ranks():

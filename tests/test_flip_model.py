@@ -13,6 +13,7 @@ import crush_model as cm
 import flip_model as fm
 import flip_shapes as fs
 import pollen_amd as pa
+import random_pools as rp
 from conftest import GOLDEN, golden_gfas
 
 FLIP = os.path.join(GOLDEN, "flip")
@@ -162,6 +163,23 @@ def test_model_text_is_the_references(path):
     want = cm.text_views(ref)
     for a, b, what in zip(got, want, ("S", "P", "L", "H")):
         assert a == b, (stem, what)
+
+
+@pytest.mark.parametrize("seed", rp.TEXT_SEEDS)
+def test_model_text_is_the_references_on_random_graphs(seed):
+    """random_pools' text profile: ties, twins, self-loops, x+ -> x-, old links in both spellings and with 5M, a hub row."""
+    p = rp.make(seed, "text")
+    src = MANIFEST["random_%d.gfa" % seed]
+    assert hashlib.sha256(rp.gfa_text(p)).hexdigest() == src["sha256"]  # the graph the reference was given
+    rec = MANIFEST["random_%d.flip.txt" % seed]
+    with open(os.path.join(FLIP, "random_%d.flip.txt" % seed), "rb") as f:
+        ref = f.read()
+    assert hashlib.sha256(ref).hexdigest() == rec["sha256"] and len(ref) == rec["bytes"]
+    q = fm.flip(p)
+    fm.assert_same_pools(q, fm.flip(p, fast=False), seed)
+    assert fm.counts(p) == (rec["turned"], rec["links_out"]) and len(p.links) == rec["links_in"] and rec["turned"] >= 3
+    for a, b, what in zip(cm.text_views(fm.text(q), ours=True), cm.text_views(ref), ("S", "P", "L", "H")):
+        assert a == b, (seed, what)
 
 
 def test_the_goldens_turn_paths_and_add_links():

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import random_pools as rp
 import topology_model as tm
 import topology_shapes as ts
 from conftest import GOLDEN, fixture_id, golden_gfas
@@ -73,6 +74,16 @@ def test_model_equals_slow_odgi_on_the_synthetic_graph():
     assert text == golden("synth_mid.validate.txt") and text.count(b"\n") == 440
     assert tm.degree_text(p) == golden("synth_mid.degree.tsv")
     assert len(text) < os.path.getsize(os.path.join(GOLDEN, "synth_cfgS.depth.tsv"))
+
+
+@pytest.mark.parametrize("seed", rp.TEXT_SEEDS)
+def test_model_equals_slow_odgi_on_random_graphs(seed):
+    """random_pools' text profile: dropped links, both spellings, duplicates, self-loops, x+ -> x-, a hub row, sparse names."""
+    p = rp.make(seed, "text")
+    assert hashlib.sha256(rp.gfa_text(p)).hexdigest() == MANIFEST["random_%d.gfa" % seed]["sha256"]  # the graph the reference was given
+    text = tm.validate_text(p)
+    assert text == golden("random_%d.validate.txt" % seed) and text.count(b"\n") > 10
+    assert tm.degree_text(p) == golden("random_%d.degree.tsv" % seed)
 
 
 # ---- the rules, one by one: handles are segment << 1 | backward; segments 0, 1, 2 are named 1, 2, 3 ----
