@@ -6,6 +6,9 @@
 
 #include <cstdlib>
 
+#include <algorithm>
+
+#include "depth_call_host.hpp"
 #include "depth_fast_kernels.hpp"
 #include "depth_sorted_host.hpp"
 
@@ -247,6 +250,24 @@ __device__ __forceinline__ void window_counts(const int *D, const int *R, unsign
         block_scan<int, kPer>(reinterpret_cast<int *>(wave_tot), v);
 #pragma unroll
         for (int k = 0; k < kPer; ++k) d[k] = (uint32_t)v[k];
+    }
+}
+// The same from the sorted sweep's packed cells (depth_sorted_host.hpp: depth's difference in a cell's low half, the revisits' in
+// its high half, exact under the plan's rule): unpacked into the same 64-bit values, one scan.
+template <int kPer>
+__device__ __forceinline__ void window_counts_packed(const uint32_t *W, unsigned long long *wave_tot, uint32_t i0, uint32_t (&d)[kPer], uint32_t (&rv)[kPer]) {
+    unsigned long long v[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        int32_t dd, dr;
+        sorted_unpack(W[i0 + k], dd, dr);
+        v[k] = (unsigned long long)(long long)dd + ((unsigned long long)(long long)dr << 32);
+    }
+    block_scan<unsigned long long, kPer>(wave_tot, v);
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        d[k] = (uint32_t)v[k];
+        rv[k] = (uint32_t)(v[k] >> 32);
     }
 }
 // (add: several workgroups share the window, or the outputs hold the counts of the paths walked before)
@@ -1331,7 +1352,8 @@ typedef uint32_t sorted_u32x4 __attribute__((ext_vector_type(4)));
 template <bool NT>
 __device__ __forceinline__ sorted_u32x4 sorted_load4(const sorted_u32x4 *p) { return NT ? __builtin_nontemporal_load(p) : *p; }
 
-template <bool UNIQ, int WB, bool CHECKED>
+// (PACKED, with unique depth: D is the one array of packed cells and R is not there)
+template <bool UNIQ, int WB, bool CHECKED, bool PACKED>
 __device__ __forceinline__ void sweep_group(int *D, int *R, const sorted_u32x4 &r4, uint32_t carry, bool in, int lane) {
     // (in: the lane's chunk lies inside the window -- CHECKED only; a lane behind the end holds padding whatever it read)
     const uint32_t pad = CHECKED && !in ? kSortedPad : 0u;
@@ -1342,6 +1364,13 @@ __device__ __forceinline__ void sweep_group(int *D, int *R, const sorted_u32x4 &
         sorted_lane_keys<CHECKED>(rec, q, (uint32_t)WB, seed, ln);
         // the largest key over the lanes BEFORE this one: the values move up a lane, then the inclusive scan
         uint32_t p = sorted_umax(seed, wave_scan_max((uint32_t)__builtin_amdgcn_update_dpp(0u, ln.t, 0x138 /* wave_shr:1 */, 0xf, 0xf, true)));
+        if (PACKED) {
+            uint32_t *W = reinterpret_cast<uint32_t *>(D);
+#pragma unroll
+            for (uint32_t k = 0; k < kSortedGroup; ++k)
+                sorted_record_packed<CHECKED>(p, ln.s[k], ln.len[k], ln.x[k], [&](uint32_t cell, uint32_t v) { atomicAdd(&W[cell], v); });
+            return;
+        }
 #pragma unroll
         for (uint32_t k = 0; k < kSortedGroup; ++k) {
             uint32_t end;
@@ -1368,14 +1397,16 @@ __device__ __forceinline__ void sweep_group(int *D, int *R, const sorted_u32x4 &
     }
 }
 
-template <bool UNIQ, int WB, bool NT>
+template <bool UNIQ, int WB, bool NT, bool PACKED = false>
 __global__ __launch_bounds__(kAccThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_accum_sorted(const AccArgs A) {
+    static_assert(UNIQ || !PACKED, "packed cells hold depth and revisits: the depth-only builds have one array as it is");
     static_assert(kSortedChunk == 64u && kSortedGroup == 4u, "a lane holds four consecutive records of one chunk: sixteen lanes a chunk");
     constexpr uint32_t kW = 1u << WB;
     constexpr int kPer = kW / kAccThreads;
-    __shared__ __attribute__((aligned(16))) int cells[(UNIQ ? 2 : 1) * (kW + 64)];
+    constexpr uint32_t kCells = (UNIQ && !PACKED ? 2u : 1u) * (kW + 64);
+    __shared__ __attribute__((aligned(16))) int cells[kCells];
     __shared__ unsigned long long wave_tot[kAccWaves];
-    int *D = cells, *R = cells + (UNIQ ? kW + 64 : 0);
+    int *D = cells, *R = cells + (UNIQ && !PACKED ? kW + 64 : 0);
     const int tid = threadIdx.x, lane = tid & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t win = blockIdx.x, w0 = win * kW;
@@ -1394,14 +1425,14 @@ __global__ __launch_bounds__(kAccThreads) __attribute__((amdgpu_waves_per_eu(8, 
         if (UNIQ) cy = A.scarry[min(ck + q, c1 - 1u)];
     };
     const auto sweep = [&](const sorted_u32x4 &r, uint32_t cy, uint32_t at) {
-        if (at + 1u == ng) sweep_group<UNIQ, WB, true>(D, R, r, cy, c0 + at * kSortedGroup + q < c1, lane);
-        else sweep_group<UNIQ, WB, false>(D, R, r, cy, true, lane);
+        if (at + 1u == ng) sweep_group<UNIQ, WB, true, PACKED>(D, R, r, cy, c0 + at * kSortedGroup + q < c1, lane);
+        else sweep_group<UNIQ, WB, false, PACKED>(D, R, r, cy, true, lane);
     };
     // A request is made whether or not its group exists (one behind the window's last reads the window's last records, which
     // nobody looks at): with a request under a condition the compiler waits for EVERY load before a sweep, the one just made
     // included, and a wave stands through a whole trip to memory per group.
     if (ng) request(ra, ca, g);  // (on its way while the workgroup clears its arrays; a window without records has no address to read)
-    for (uint32_t i = tid; i < (UNIQ ? 2u : 1u) * (kW + 64); i += kAccThreads) cells[i] = 0;
+    for (uint32_t i = tid; i < kCells; i += kAccThreads) cells[i] = 0;
     __syncthreads();
     while (g < ng) {
         request(rb, cb, g + kAccWaves);
@@ -1415,7 +1446,8 @@ __global__ __launch_bounds__(kAccThreads) __attribute__((amdgpu_waves_per_eu(8, 
     __syncthreads();
     const uint32_t nvalid = min(kW, A.n_segs - w0), i0 = kPer * tid;
     uint32_t d[kPer], u[kPer];
-    window_counts<UNIQ, kPer>(D, R, wave_tot, i0, d, u);  // (u: the revisits)
+    if (PACKED) window_counts_packed<kPer>(reinterpret_cast<const uint32_t *>(D), wave_tot, i0, d, u);
+    else window_counts<UNIQ, kPer>(D, R, wave_tot, i0, d, u);  // (u: the revisits)
     if (UNIQ) {
 #pragma unroll
         for (int k = 0; k < kPer; ++k) u[k] = d[k] - u[k];
@@ -1424,6 +1456,15 @@ __global__ __launch_bounds__(kAccThreads) __attribute__((amdgpu_waves_per_eu(8, 
 }
 
 }  // namespace
+
+uint32_t device_cu_lds_bytes() {
+    int dev = 0, per_cu = 0, per_wg = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0u;
+    if (hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess) per_cu = 0;
+    if (hipDeviceGetAttribute(&per_wg, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) per_wg = 0;
+    (void)hipGetLastError();
+    return (uint32_t)std::max(0, std::max(per_cu, per_wg));  // (a workgroup may take a whole CU's on this part)
+}
 
 bool accum_kernels_setup() {
     // pass 2 of a tagged call keeps its bitsets in dynamic shared memory (next to about 60 KB of static arrays, 93 KB with 8192-segment windows)
@@ -1451,6 +1492,18 @@ bool accum_kernels_setup() {
         set((const void *)k_accum<true, 12, false, false, false, true, (int)kTagSlots, true, true>, tagged_lds_bytes(12, kMaxShared));
         set((const void *)k_accum<true, 12, false, false, false, true, 8, true, true>, tagged_lds_bytes(12, 64, 8));
         set((const void *)k_accum<true, 13, false, false, false, true, (int)kTagSlots, true, true>, tagged_lds_bytes(13, 0));
+        // (... and the sweeps of a pipeline's lanes, launched with half a CU's LDS on top of their own so that a CU holds one: depth_call_host.hpp)
+        const uint32_t solo = sorted_solo_lds(1, 2u, device_cu_lds_bytes());
+#define FGFA_SORTED_SET(WB_)                                                                                                    \
+        set((const void *)k_accum_sorted<true, WB_, false, true>, solo), set((const void *)k_accum_sorted<true, WB_, true, true>, solo),   \
+        set((const void *)k_accum_sorted<true, WB_, false>, solo), set((const void *)k_accum_sorted<true, WB_, true>, solo),               \
+        set((const void *)k_accum_sorted<false, WB_, false>, solo), set((const void *)k_accum_sorted<false, WB_, true>, solo)
+        if (solo) {
+            FGFA_SORTED_SET(11);
+            FGFA_SORTED_SET(12);
+            FGFA_SORTED_SET(13);
+        }
+#undef FGFA_SORTED_SET
 #ifdef FGFA_MEASURE
         set((const void *)k_accum_small<11>, tagged_lds_bytes(11, kMaxShared));
         set((const void *)k_accum_pair<12, false>, tagged_lds_bytes(12, 0));
@@ -1476,13 +1529,16 @@ bool accum_kernels_setup() {
     } while (0)
 #define FGFA_SORTED_LAUNCH(WB_)                                                                                                  \
     do {                                                                                                                        \
-        if (uniq && fp.sorted_nt) hipLaunchKernelGGL((k_accum_sorted<true, WB_, true>), dim3(fp.n_win), dim3(kAccThreads), 0, stream, aa);        \
-        else if (uniq) hipLaunchKernelGGL((k_accum_sorted<true, WB_, false>), dim3(fp.n_win), dim3(kAccThreads), 0, stream, aa);                  \
-        else if (fp.sorted_nt) hipLaunchKernelGGL((k_accum_sorted<false, WB_, true>), dim3(fp.n_win), dim3(kAccThreads), 0, stream, aa);          \
-        else hipLaunchKernelGGL((k_accum_sorted<false, WB_, false>), dim3(fp.n_win), dim3(kAccThreads), 0, stream, aa);                           \
+        if (uniq && packed && fp.sorted_nt) hipLaunchKernelGGL((k_accum_sorted<true, WB_, true, true>), dim3(fp.n_win), dim3(kAccThreads), sorted_lds, stream, aa);  \
+        else if (uniq && packed) hipLaunchKernelGGL((k_accum_sorted<true, WB_, false, true>), dim3(fp.n_win), dim3(kAccThreads), sorted_lds, stream, aa);            \
+        else if (uniq && fp.sorted_nt) hipLaunchKernelGGL((k_accum_sorted<true, WB_, true>), dim3(fp.n_win), dim3(kAccThreads), sorted_lds, stream, aa);   \
+        else if (uniq) hipLaunchKernelGGL((k_accum_sorted<true, WB_, false>), dim3(fp.n_win), dim3(kAccThreads), sorted_lds, stream, aa);                  \
+        else if (fp.sorted_nt) hipLaunchKernelGGL((k_accum_sorted<false, WB_, true>), dim3(fp.n_win), dim3(kAccThreads), sorted_lds, stream, aa);          \
+        else hipLaunchKernelGGL((k_accum_sorted<false, WB_, false>), dim3(fp.n_win), dim3(kAccThreads), sorted_lds, stream, aa);                           \
     } while (0)
-void launch_accum(const FastPlan &fp, AccArgs &aa, bool uniq, bool tagged, bool psum, hipStream_t stream, bool sorted) {
+void launch_accum(const FastPlan &fp, AccArgs &aa, bool uniq, bool tagged, bool psum, hipStream_t stream, bool sorted, uint32_t sorted_lds) {
     if (sorted) {  // (decide_call: one workgroup per window, 2048- to 8192-segment windows, no path sums)
+        const bool packed = fp.sorted_cells == kSortedCellsPacked;  // (unique depth in packed cells, where the image's rule allows it)
         if (fp.wb == 11) FGFA_SORTED_LAUNCH(11);
         else if (fp.wb == 12) FGFA_SORTED_LAUNCH(12);
         else FGFA_SORTED_LAUNCH(13);

@@ -39,6 +39,7 @@ struct CallShape {
     bool from_image = false;  // pass 1 reads the steps' run-length image (k_scan_runs)
     bool kept = false;        // ... whose records of the call before are still there: pass 1 is left out
     bool sorted = false;      // ... and pass 2 sweeps the plan's sorted record image (k_accum_sorted) instead of walking the kept records
+    uint32_t sorted_solo_lds = 0;  // ... launched with this much dynamic LDS: one sweep workgroup to a CU (a pipeline lane); 0: two share it
     uint32_t has_pre2 = 0;    // pass 2: 0 = all records are k_scan's, 1 = the wave-per-path kernels' lie before them, 2 = there are no others
     uint32_t max_back = 0;    // paths that may be handed back to k_scan, as both passes see it
     Zeroes outputs = Zeroes::nobody, sums = Zeroes::nobody;
@@ -65,6 +66,15 @@ inline ScanMode scan_mode(const FastPlan &fp, const CallShape &s) {
     if (s.ranged) return {kModeRanged, s.tagged};
     return {s.tagged && fp.narrow_emit ? kModePlainNarrow : kModePlain, s.tagged};
 }
+
+// ---- pipeline lanes: one sweep workgroup to a CU ----
+// Two sweeps queued by two lanes start side by side on the same CUs, share the LDS pipe that bounds both and reach their clears
+// and epilogues together; launched with enough dynamic LDS that static plus dynamic exceeds half a CU's, the lanes' sweeps
+// follow each other on every CU instead.  hook: FLATGFA_SORTED_SOLO as it was when the image was installed (0, 1; -1: unset);
+// lanes: the calls in flight of the pipeline that made the plan (0: a plan on its own, which keeps two workgroups to a CU).
+constexpr bool kSortedLanesSoloDefault = false;  // (profiles/NOTES.md R7.6: which setting measured faster)
+inline bool sorted_lanes_solo(int hook, uint32_t lanes) { return hook >= 0 ? hook == 1 : kSortedLanesSoloDefault && lanes >= 2u; }
+inline uint32_t sorted_solo_lds(int hook, uint32_t lanes, uint32_t cu_lds_bytes) { return sorted_lanes_solo(hook, lanes) ? cu_lds_bytes / 2u : 0u; }
 
 // ---- the shape of a call ----
 inline uint32_t wave_list_grid(uint32_t n, uint32_t per_wg, uint32_t n_slots) { return std::min<uint32_t>((n + per_wg - 1) / per_wg, n_slots); }
@@ -106,6 +116,7 @@ inline CallShape decide_call(const FastPlan &fp, const GraphFacts &g, const Call
     // ... and exactly those calls, once the plan's sorted record image is installed (one pass-2 workgroup per window, the window
     // widths it has builds for), sweep that.  Pass 1 runs wherever it ran: whatever drops the kept records brings it back.
     s.sorted = s.kept && fp.sorted_rec && fp.sorted_carry && fp.sorted_win_chunk && fp.acc_parts == 1 && fp.wb >= 11 && fp.wb <= 13;
+    s.sorted_solo_lds = s.sorted ? fp.sorted_solo_lds : 0u;
     if (s.scans() && !s.from_image && scan_mode(fp, s).mode == kModeRefused) {
         CallShape no;
         no.refusal = "fast_seg_depth: a bucket array this large needs a tagged call";

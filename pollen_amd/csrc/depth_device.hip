@@ -307,6 +307,8 @@ struct flatgfa_dev_plan {
     int sorted_state = 0;              // 0: not looked at yet, 1: being made, 3: installed, -1: none
     const char *sorted_off = "";       // ... and why not
     int sorted_hook = -1;              // FLATGFA_SORTED_RECORDS as it was when the plan was made (0, 1; -1: unset)
+    uint32_t lanes = 0;                // the calls in flight of the pipeline that made the plan (0: a plan on its own)
+    bool sorted_said = false;          // FLATGFA_SORTED_CELLS or FLATGFA_SORTED_SOLO was set when the image was installed: the description names cells and lanes
 };
 
 // Every call of a plan through the bucketed kernels: it says whether the scratch holds an image call's records, and takes
@@ -668,6 +670,12 @@ static void run_poll(flatgfa_dev_plan_t *pl, bool wait, bool may_start, hipStrea
 // counted, then -- the host has to know how many records there are before it gives them room -- emitted, sorted and finalised,
 // all on the side stream and under the side stream's rule (no call runs beside it: side_work_enqueued / side_work_wait), and
 // installed between two calls.  The plan's device is current.
+// A pipeline lane's sweep, one workgroup to a CU or two (depth_call_host.hpp: sorted_solo_lds; FLATGFA_SORTED_SOLO=0|1, a test
+// hook read here, forces one): decided when the image is installed, and again when a pipeline tells a plan that it is a lane.
+static void sorted_lanes_apply(flatgfa_dev_plan_t *pl) {
+    const char *hook = test_hook("FLATGFA_SORTED_SOLO");
+    pl->fast.sorted_solo_lds = sorted_solo_lds(!hook ? -1 : !strcmp(hook, "1") ? 1 : !strcmp(hook, "0") ? 0 : -1, pl->lanes, device_cu_lds_bytes());
+}
 static void sorted_poll(flatgfa_dev_plan_t *pl, bool wait) {
     if (pl->sorted_state == 3 || pl->sorted_state < 0 || pl->run_state != 3) return;
     const auto give_up = [&](const char *why) {
@@ -708,6 +716,8 @@ static void sorted_poll(flatgfa_dev_plan_t *pl, bool wait) {
     const char *mall = getenv("FLATGFA_MALL_MB");
     const bool nt = traffic > (244ll << 20) || (mall && strtoull(mall, nullptr, 10) == 0);
     sorted_image_install(&pl->fast, pl->sorted->img, nt);
+    sorted_lanes_apply(pl);
+    pl->sorted_said = test_hook("FLATGFA_SORTED_CELLS") || test_hook("FLATGFA_SORTED_SOLO");
     pl->sorted_state = 3;
 }
 
@@ -1429,6 +1439,11 @@ extern "C" int flatgfa_dev_plan_describe(flatgfa_dev_plan_t *pl, char *out, int 
                     s += std::string(" pass2=walk(") + (pl->sorted_state < 0 ? pl->sorted_off : "pending") + ")";
                 }
                 s += std::string(" records=") + (pl->keep_records && f.counts_kept ? "kept" : "rewritten");  // (pass 1 once per run of image calls, or in every call)
+                // (which cells the sweep for unique depth adds into, and why: said at the line's end, and only under the hook that
+                // forces one form, as it was when the image was installed -- without it the line stays what its readers know, word for
+                // word; and whether the sweep is launched one workgroup to a CU, likewise under FLATGFA_SORTED_SOLO)
+                if (pl->sorted_state == 3 && f.sorted_rec && pl->sorted_said)
+                    s += std::string(" sorted_cells=") + sorted_cells_name(f.sorted_cells) + " sorted_lanes=" + (f.sorted_solo_lds ? "solo" : "shared");
             } else {
                 s += std::string(" run_image=off(") + (pl->run_state < 0 ? pl->run_off : "pending") + ")";
             }
@@ -1555,6 +1570,8 @@ extern "C" flatgfa_dev_pipeline_t *flatgfa_dev_pipeline_create(const flatgfa_dev
         const uint32_t wgs = calls_in_flight < 2 ? 0u : (uint32_t)(calls_in_flight >= 3 && g->n_steps <= (1ull << 28) ? n_cus / 2 : n_cus * 11 / 16);
         flatgfa_dev_plan_t *pl = plan_create_impl(g, hb, he, wgs);
         if (!pl) { flatgfa_dev_pipeline_destroy(p); return nullptr; }
+        pl->lanes = (uint32_t)calls_in_flight;
+        if (pl->sorted_state == 3) sorted_lanes_apply(pl);
         p->plans.push_back(pl);
     }
     if (hipEventCreateWithFlags(&p->after, hipEventDisableTiming) != hipSuccess) { set_error("dev_pipeline_create: cannot create an event"); flatgfa_dev_pipeline_destroy(p); return nullptr; }

@@ -1583,7 +1583,7 @@ static int run_range(const FastPlan &fp, const flatgfa_dev_graph_t &g, uint32_t 
     if (count_only) return hipGetLastError() == hipSuccess ? FLATGFA_OK : FLATGFA_ERR_HIP;  // (the counting call of a packed plan: pass 1 alone)
     {
         ProfScope pscope(uniq ? "k_accum<uniq>" : (ps ? "k_accum<depth+paths>" : "k_accum<depth>"), stream);
-        launch_accum(fp, aa, uniq, s.tagged, ps != nullptr, stream, s.sorted);
+        launch_accum(fp, aa, uniq, s.tagged, ps != nullptr, stream, s.sorted, s.sorted_solo_lds);
     }
     if (ps && fp.n_items) {
         ProfScope pscope("k_path_reduce", stream);

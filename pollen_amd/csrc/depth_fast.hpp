@@ -29,6 +29,8 @@ struct OncePerDevice {
 
 // multiProcessorCount of a device, asked for once per device (depth_device.hip)
 int device_cu_count(int device);
+// the LDS of a CU of the current device, in bytes (depth_accum.hip; 0: not known)
+uint32_t device_cu_lds_bytes();
 // FLATGFA_TIMING=1: prints what the calling thread spent since its last tick (the device drained first), to stderr; `what` == nullptr restarts the clock
 void plan_tick(const char *what);
 
@@ -179,6 +181,12 @@ struct FastPlan {
     // alone on the kept records run k_accum_sorted on these.  The plan's handle's; not freed by fast_plan_destroy.
     const uint32_t *sorted_rec = nullptr, *sorted_carry = nullptr, *sorted_win_chunk = nullptr;
     bool sorted_nt = false;              // read past the caches (image and results do not fit the Infinity Cache)
+    // which cells the sweep for unique depth adds into (depth_sorted_host.hpp, kSortedCells...): packed where the image's build
+    // found the rule to hold; 0: not known, which sweeps wide cells
+    uint32_t sorted_cells = 0;
+    // dynamic LDS, in bytes, the sweep is launched with so that no second sweep workgroup fits its CU (a pipeline lane's plan,
+    // depth_call_host.hpp: sorted_solo_lds); 0: two workgroups share a CU
+    uint32_t sorted_solo_lds = 0;
 };
 
 // What a plan's handle tells a call about the records in the plan's scratch, and what the call tells it back.  k_scan_runs'

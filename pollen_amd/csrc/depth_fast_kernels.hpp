@@ -519,7 +519,8 @@ void launch_scan_tiny(const FastPlan &fp, const ScanArgs &sk, bool uniq, uint32_
 void launch_scan_short(const FastPlan &fp, const ScanArgs &sk, bool medium, bool uniq, uint32_t grid, hipStream_t stream);
 // pass 2 in the build the call needs (unique depth or not, tagged walk or directory walk, path sums, window size)
 // (sorted: the sweep over the plan's sorted record image, k_accum_sorted, instead of any walk)
-void launch_accum(const FastPlan &fp, AccArgs &aa, bool uniq, bool tagged, bool psum, hipStream_t stream, bool sorted = false);
+// (sorted_lds: dynamic LDS the sweep is launched with, CallShape::sorted_solo_lds)
+void launch_accum(const FastPlan &fp, AccArgs &aa, bool uniq, bool tagged, bool psum, hipStream_t stream, bool sorted = false, uint32_t sorted_lds = 0);
 void launch_path_reduce(const FastPlan &fp, unsigned long long *len_out, unsigned long long *weighted_out, hipStream_t stream);
 
 }  // namespace fgfa_dev

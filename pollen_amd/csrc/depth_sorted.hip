@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "depth_fast_kernels.hpp"
@@ -24,7 +26,8 @@ struct SortedImage {
     uint32_t *carry = nullptr;      // [n_chunks]
     uint32_t *win_chunk = nullptr;  // [n_win + 1]
     // while it is being made
-    uint32_t *cnt = nullptr;        // [n_win] records per window; [n_win]: records dropped for bounds; [n_win + 1]: pairs emitted; [n_win + 2]: a pair in the wrong window
+    uint32_t *cnt = nullptr;        // [n_win] records per window; [n_win]: records dropped for bounds; [n_win + 1]: pairs emitted; [n_win + 2]: a pair in the wrong window;
+                                    // [n_win + 3], [n_win + 4]: the most records that start at one cell of one window, and that end at one
     uint32_t *rec_off = nullptr;    // [n_win + 1]
     uint64_t *keys = nullptr;       // [2 n]: in, out
     uint32_t *recs = nullptr;       // [2 n]
@@ -33,6 +36,7 @@ struct SortedImage {
     SortedKey key;
     SortedLayout lay;
     uint64_t transient = 0;
+    uint32_t cell_max[2] = {0u, 0u};  // (sorted_image_cell_max; 0: not known)
     hipEvent_t done = nullptr;
     int phase = 0;                  // 1: counted (enqueued), 2: emitted, sorted, finalised (enqueued), 3: there, -1: not to be had
     const char *why = "";
@@ -151,6 +155,34 @@ __global__ __launch_bounds__(64) void sorted_image_finalise(const uint64_t *__re
     }
 }
 
+// The bound the sweep's packed cells rest on (depth_sorted_host.hpp, sorted_cells_fit): one workgroup per window counts, over the
+// window's finished chunks, the records that start at every cell and then those that end at every cell, and the largest of each
+// goes out.  A histogram maximum of the image; nothing of it reaches a result.
+constexpr uint32_t kSortedMaxWb = 13;
+__global__ __launch_bounds__(256) void sorted_image_cell_max(const uint32_t *__restrict__ img, const uint32_t *__restrict__ win_chunk, uint32_t wb, uint32_t *__restrict__ out) {
+    __shared__ uint32_t hist[(1u << kSortedMaxWb) + 1u];
+    __shared__ uint32_t top;
+    const uint32_t w = blockIdx.x, wmask = (1u << wb) - 1u, n_cells = (1u << wb) + 1u;  // (wb <= kSortedMaxWb: the host's business)
+    const uint32_t r0 = win_chunk[w] * kSortedChunk, r1 = win_chunk[w + 1u] * kSortedChunk;
+    for (uint32_t pass = 0; pass < 2u; ++pass) {
+        for (uint32_t i = threadIdx.x; i < n_cells; i += 256u) hist[i] = 0u;
+        if (threadIdx.x == 0) top = 0u;
+        __syncthreads();
+        for (uint32_t i = r0 + threadIdx.x; i < r1; i += 256u) {
+            const uint32_t rec = img[i];
+            const uint32_t s = rec & wmask, cell = pass ? s + ((rec >> wb) & 1023u) + 1u : s;
+            if (!(rec & kSortedPad) && cell < n_cells) atomicAdd(&hist[cell], 1u);
+        }
+        __syncthreads();
+        uint32_t m = 0u;
+        for (uint32_t i = threadIdx.x; i < n_cells; i += 256u) m = max(m, hist[i]);
+        if (m) atomicMax(&top, m);
+        __syncthreads();
+        if (threadIdx.x == 0 && top) atomicMax(&out[pass], top);
+        __syncthreads();
+    }
+}
+
 void sorted_release_scratch(SortedImage *si) {
     for (void **p : {(void **)&si->cnt, (void **)&si->rec_off, (void **)&si->keys, (void **)&si->recs, &si->scratch}) {
         if (*p) (void)hipFree(*p);
@@ -184,7 +216,7 @@ SortedImage *sorted_image_start(const FastPlan &fp, uint32_t n_paths, hipStream_
         sorted_fail(si, "size");
         return si;
     }
-    const size_t cnt_bytes = ((size_t)fp.n_win + 3) * 4;
+    const size_t cnt_bytes = ((size_t)fp.n_win + 5) * 4;
     if (hipMalloc(&si->cnt, cnt_bytes) != hipSuccess || hipEventCreateWithFlags(&si->done, hipEventDisableTiming) != hipSuccess) {
         sorted_fail(si, "memory");
         return si;
@@ -218,9 +250,11 @@ int sorted_image_poll(SortedImage *si, const FastPlan &fp, hipStream_t side, boo
             return 0;
         }
         if (si->phase == 2) {
-            uint32_t end[2] = {0u, 1u};  // pairs emitted; a pair in the wrong window
-            if (staged_copy(end, si->cnt + si->n_win + 1, 8, hipMemcpyDeviceToHost, nullptr) != hipSuccess) return sorted_fail(si, "error");
+            uint32_t end[4] = {0u, 1u, 0u, 0u};  // pairs emitted; a pair in the wrong window; the most starts at a cell, the most ends
+            if (staged_copy(end, si->cnt + si->n_win + 1, 16, hipMemcpyDeviceToHost, nullptr) != hipSuccess) return sorted_fail(si, "error");
             if (end[0] != si->lay.n_records || end[1]) return sorted_fail(si, "stale");  // (the steps changed while it was made)
+            si->cell_max[0] = end[2];
+            si->cell_max[1] = end[3];
             sorted_release_scratch(si);
             si->phase = 3;
             return 1;
@@ -268,6 +302,10 @@ int sorted_image_poll(SortedImage *si, const FastPlan &fp, hipStream_t side, boo
             hipLaunchKernelGGL(sorted_image_finalise, dim3(fp.n_win), dim3(64), 0, side, si->keys + n, si->recs + n, si->rec_off, si->win_chunk, fp.n_win, si->key,
                                si->rec, si->carry, si->cnt + si->n_win + 2);
         }
+        if (fp.wb <= kSortedMaxWb) {  // (wider windows: the words stay 0, "not known")
+            ProfScope ps("sorted_image_cell_max", side);
+            hipLaunchKernelGGL(sorted_image_cell_max, dim3(fp.n_win), dim3(256), 0, side, si->rec, si->win_chunk, fp.wb, si->cnt + si->n_win + 3);
+        }
         if (hipEventRecord(si->done, side) != hipSuccess || hipGetLastError() != hipSuccess) {
             (void)hipStreamSynchronize(side);
             return sorted_fail(si, "error");
@@ -286,6 +324,11 @@ void sorted_image_install(FastPlan *fp, const SortedImage *si, bool nt) {
     fp->sorted_carry = si->carry;
     fp->sorted_win_chunk = si->win_chunk;
     fp->sorted_nt = nt;
+    // FLATGFA_SORTED_CELLS=wide|packed (a test hook, read here): one form of the cells for unique depth -- packed only where the rule allows it
+    // (any other value is no hook at all)
+    const char *hook = std::getenv("FLATGFA_SORTED_CELLS");
+    const int forced = !hook ? -1 : !strcmp(hook, "packed") ? 1 : !strcmp(hook, "wide") ? 0 : -1;
+    fp->sorted_cells = sorted_cells_choice(forced, si->cell_max[0], si->cell_max[1]);
 }
 
 void sorted_image_free(SortedImage *si, hipStream_t side) {

@@ -4,7 +4,8 @@
 // functions over plain data -- the sort key and how many bits it takes, where every window's chunks lie, what the build needs
 // of the device's memory and when that is refused.  No HIP runtime call and no environment variable in here;
 // tests/host_check/sorted_check.cpp runs these functions without a GPU.  At the end: the sweep's arithmetic per lane, one text for
-// k_accum_sorted and for tests/host_check/sorted_group_check.cpp.
+// k_accum_sorted and for tests/host_check/sorted_group_check.cpp, and the packed cells it adds into with unique depth -- the
+// pack values, the unpack, and the rule under which a plan may use them (tests/host_check/packed_cells_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -133,6 +134,49 @@ FGFA_SORTED_HD inline bool sorted_record_step(uint32_t &p, uint32_t x, uint32_t 
     end = sorted_umin(x, p) & ((1u << kSortedEndBits) - 1u);
     p = sorted_umax(p, x);
     return hit;
+}
+
+// ---- packed cells (k_accum_sorted<true, ...>; tests/host_check/packed_cells_check.cpp runs the same text) ----
+// With unique depth a record adds to the difference arrays of depth and of revisits, and a revisiting record adds to the SAME
+// cell s of both.  So one array W: a cell holds dD + 65536 dR mod 2^32, depth's difference in the low half and the revisits'
+// in the high half; a record is two adds, and a third only where its revisits end before it does.  Unpacking is exact while
+// both halves stay inside 16 signed bits, and they do under the rule below: |dD[c]| <= max(starts(c), ends(c)), counting the
+// window's records that start or end at cell c; and |dR[c]| <= max(starts(c), 2 ends(c)), because a revisit's end is the
+// record's own end or an earlier end M of its path, and a path cuts at one value of M once -- the record that does raises M
+// beyond it -- so the cuts at c are no more than the paths with a record ending at c.
+constexpr uint32_t kSortedPackRevisit = 1u << 16;  // one revisit, in a cell
+constexpr uint32_t kSortedPackLimit = 1u << 14;    // the rule: fewer starts and fewer ends than this at every cell of every window
+FGFA_SORTED_HD inline uint32_t sorted_pack(int32_t dD, int32_t dR) { return (uint32_t)dD + ((uint32_t)dR << 16); }
+FGFA_SORTED_HD inline void sorted_unpack(uint32_t w, int32_t &dD, int32_t &dR) {
+    dD = (int32_t)(int16_t)(uint16_t)(w & 0xFFFFu);
+    dR = (int32_t)(int16_t)(uint16_t)((w - (uint32_t)dD) >> 16);  // (a negative low half borrowed from the high one)
+}
+FGFA_SORTED_HD inline uint32_t sorted_pack_start(bool hit) { return 1u + (hit ? kSortedPackRevisit : 0u); }         // what W[s] takes
+FGFA_SORTED_HD inline uint32_t sorted_pack_end(bool hit_to_e) { return 1u + (hit_to_e ? kSortedPackRevisit : 0u); }  // what W[e] gives: the revisits end with the record
+// One record of a lane, as sorted_record_step sees it, into the cells: add(cell, value) adds mod 2^32.
+template <bool CHECKED, class Add>
+FGFA_SORTED_HD inline void sorted_record_packed(uint32_t &p, uint32_t s, uint32_t len, uint32_t x, Add add) {
+    uint32_t end;
+    const bool hit = sorted_record_step<CHECKED>(p, x, len, end);
+    if (CHECKED && x == 0u) return;  // padding
+    const uint32_t e = s + len + 1u;  // (e <= window size; that cell is a sink)
+    add(s, sorted_pack_start(hit));
+    add(e, 0u - sorted_pack_end(hit && end == e));
+    if (hit && end != e) add(end, 0u - kSortedPackRevisit);
+}
+// The rule, from the largest number of records that start at one cell of one window and that end at one (sorted_image_cell_max:
+// a histogram maximum of the image, an index and not an answer).  No maximum (an image nobody measured): not known.
+inline bool sorted_cells_fit(uint32_t max_starts, uint32_t max_ends) { return max_starts != 0u && max_starts < kSortedPackLimit && max_ends < kSortedPackLimit; }
+// What FastPlan::sorted_cells says; 0 is "not known", which sweeps wide cells.
+constexpr uint32_t kSortedCellsUnknown = 0, kSortedCellsPacked = 1, kSortedCellsWideRule = 2, kSortedCellsWideHook = 3;
+// (hook: FLATGFA_SORTED_CELLS as it was when the image was installed -- 0: wide, 1: packed, which never overrides the rule; -1: unset)
+inline uint32_t sorted_cells_choice(int hook, uint32_t max_starts, uint32_t max_ends) {
+    if (max_starts == 0u) return kSortedCellsUnknown;
+    if (!sorted_cells_fit(max_starts, max_ends)) return kSortedCellsWideRule;
+    return hook == 0 ? kSortedCellsWideHook : kSortedCellsPacked;
+}
+inline const char *sorted_cells_name(uint32_t cells) {
+    return cells == kSortedCellsPacked ? "packed" : cells == kSortedCellsWideRule ? "wide(rule)" : cells == kSortedCellsWideHook ? "wide(hook)" : "wide(unknown)";
 }
 
 }  // namespace fgfa_dev
